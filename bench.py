@@ -2,6 +2,7 @@
 """bench.py -- FISTA-OS (+PD_TV) outer iterations per second on MI355X, BASELINE.json's metric.
 
     python bench.py --gpus N --steps K --warmup W [--config cfg1|cfg2|cfg3|cfg3-share|cfg5|cfg5-share] [--strong]
+                    [--dump-outputs DIR] [--full]
 
 N > 1: when the process was not started by a launcher (no RANK in the environment) it re-executes itself as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>`,
@@ -24,11 +25,18 @@ scalar reductions.
   weak   (default): one --nz-slice slab PER RANK; `value` = slab-iterations/s (at N=1 exactly outer iterations/s).
   strong (--strong): the --nz slices are split over the N ranks (balanced); `value` = outer iterations/s of the ONE
                     problem -- `--strong --config cfg5` is the north-star workload (2560^2 x 2160, 1800 angles).
-Per-rank exchange statistics (messages, bytes, host time posting / waiting, compute-stream stall) are in `halo`.
+Per-rank exchange statistics (messages, bytes, host time posting / waiting, compute-stream stall) are in `halo` (--full).
 
-One JSON line is printed by rank 0 (see the contract in the task statement) with extra objects: `roofline`
-(dominant kernel by time in the timed region, measured with HIP events on the launch stream by the library itself),
-`roofline_bp` / `roofline_fp` (the two projectors whatever dominates) and `cpu_baseline` (the CPU oracle, oracle/tomo_oracle.c, on the host cores for a z-subsample of the SAME sinogram).
+One JSON line is printed by rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of
+one timed step), the workload in `config` and the `placement` of the TV scratch arena.  A plain run does only that: set-up,
+warm-up, the --steps timed steps, the line.  --dump-outputs DIR also writes what the last timed call returned (the
+reconstruction, every rank its slab; see dump_outputs) as .npy files, after the timed region.
+
+--full adds everything beyond the headline, as extra objects of the same line: `roofline` (dominant kernel by time in the
+timed region, measured with HIP events on the launch stream by the library itself; default workload on one GPU: plus two
+rocprofv3 --pmc child passes), `kernels`, `roofline_bp` / `roofline_fp` (the two projectors whatever dominates),
+`cpu_baseline` (the CPU oracle, oracle/tomo_oracle.c, on the host cores for a z-subsample of the SAME sinogram), per-rank
+`halo` statistics and, for N > 1, the `north_star` child job.
 """
 import argparse
 import ctypes as C
@@ -124,10 +132,19 @@ def parse():
                         "`north_star` block.  On by default from 4 ranks on real GPUs (where every rank's share fits); "
                         "BENCH_NORTH_STAR=1 acts like the flag, BENCH_NORTH_STAR=0 / --no-north-star switch it off")
     p.add_argument("--no-north-star", action="store_true", help="never run the north-star child job")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: per-kernel event timings and roofline blocks (with the "
+                        "live --pmc passes), cpu_baseline, per-rank halo timings and the north-star child job.  --no-cpu, "
+                        "--no-pmc, --live-pmc, --north-star and their BENCH_* variables act only together with --full")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the reconstruction the last timed call returned to DIR/*.npy (float32; "
+                        "a fixed sample when the volume is larger than 32 MiB; every rank its own slab)")
     if len(sys.argv) == 1 and "TOMO_BENCH_ARGV" in os.environ and "RANK" in os.environ:  # rank started by self_launch()
         args = p.parse_args(json.loads(os.environ["TOMO_BENCH_ARGV"]))
     else:
         args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     # A driver that only varies --gpus can still reach the other workloads: BENCH_CONFIG=<preset> and BENCH_STRONG=1 act
     # like --config / --strong when the flags are absent (README.md, "Benchmark").
     if args.config is None and os.environ.get("BENCH_CONFIG"):
@@ -348,6 +365,40 @@ def footprint_bytes(args, nz):
     return vols + tv + s_full * (1.0 + 1.0 / max(args.os, 1)) + 3.0 * s_full
 
 
+DUMP_WHOLE_BYTES = 32 << 20   # --dump-outputs: a volume up to this size is written whole, a larger one as a sample of
+DUMP_SAMPLE = 1 << 20         # evenly spaced z-slices (this many bytes at most) + DUMP_SAMPLE voxels: < 64 MB in all
+
+
+def dump_outputs(out, path, name="recon", share=1):
+    """--dump-outputs: the volume [nz, N, N] that the last timed FISTA / ADMM call returned (this rank's slab), as float32
+    .npy files under `path`.  Up to DUMP_WHOLE_BYTES it is <name>.npy; above, <name>_slices.npy (evenly spaced z-slices,
+    their indices in <name>_slice_index.npy; none when one plane alone exceeds the budget) and <name>_sample.npy (the voxels
+    at sorted flat indices drawn with seed 0, listed in <name>_sample_index.npy).  `share` ranks dump at once: each gets
+    1/share of both budgets, so the files of all ranks stay under 64 MB.  The selection depends on the shape alone, so two
+    builds compare value for value."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    out = out.detach()
+    nz, plane = int(out.shape[0]), int(out[0].numel())
+    whole, sample = DUMP_WHOLE_BYTES // share, DUMP_SAMPLE // share
+    files = {}
+    if out.numel() * 4 <= whole:
+        files[name] = out.to(torch.float32).cpu().numpy()
+    else:
+        k = min(nz, whole // (4 * plane))
+        if k >= 1:
+            zsel = np.unique(np.linspace(0, nz - 1, k).round().astype(np.int64))
+            files[name + "_slices"] = out[torch.as_tensor(zsel, device=out.device)].to(torch.float32).cpu().numpy()
+            files[name + "_slice_index"] = zsel.astype(np.float64)
+        flat = np.unique(np.random.default_rng(0).integers(0, out.numel(), sample, dtype=np.int64))
+        files[name + "_sample"] = out.reshape(-1)[torch.as_tensor(flat, device=out.device)].to(torch.float32).cpu().numpy()
+        files[name + "_sample_index"] = flat.astype(np.float64)
+    for key, arr in files.items():
+        np.save(os.path.join(path, key + ".npy"), arr)
+    return sorted(files)
+
+
 def measure(args, env):
     """One workload: data synthesis, warm-up, the timed region, the JSON line (rank 0; None elsewhere)."""
     import numpy as np
@@ -377,7 +428,7 @@ def measure(args, env):
     rt = RecToolsIRCuPy(DetectorsDimH=n, DetectorsDimH_pad=0, DetectorsDimV=nz, CenterRotOffset=0.0, AnglesVec=angles,
                         ObjSize=n, device_projector=dev_index, OS_number=args.os if args.os > 1 else None)
     if slab is not None:
-        slab.timing = True
+        slab.timing = args.full   # HIP-event timing of the halo waits: only for the --full `halo` block
         rt.slab = slab
     if args.reg != "none" and slab is None and os.environ.get("BENCH_RESERVE_LATE", "0") in ("", "0"):
         # set-up, like the context and the sinogram: the library allocates and PLACES its TV scratch arena now (a search
@@ -437,7 +488,8 @@ def measure(args, env):
         for k in ("post_host_ms", "wait_host_ms"):
             slab.stats[k] = 0.0
         slab._wait_stream_ms = 0.0
-    lib.tomo_profile_enable(1)
+    if args.full:
+        lib.tomo_profile_enable(1)
     t0 = time.perf_counter()
     out = run(args.steps)
     barrier()
@@ -446,16 +498,28 @@ def measure(args, env):
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    prof = {k: prof_read(lib, k) for k in ("pdtv", "roftv", "bp", "fp")}
-    lib.tomo_profile_enable(0)
+    prof = None
+    if args.full:
+        prof = {k: prof_read(lib, k) for k in ("pdtv", "roftv", "bp", "fp")}
+        lib.tomo_profile_enable(0)
     finite = bool(torch.isfinite(out).all().item())
+    dumped = None
+    if args.dump_outputs:   # every rank its own slab; the line lists each rank's z-range and files
+        mine_d = {"rank": rank, "z_range": [z0, z1],
+                  "files": dump_outputs(out, args.dump_outputs, "recon" if world == 1 else f"recon_rank{rank}", world)}
+        dumped = [mine_d]
+        if dist is not None:
+            dumped = [None] * world
+            dist.all_gather_object(dumped, mine_d)
     halo = None
-    if dist is not None:
+    if dist is not None and args.full:
         mine = dict(rank=rank, slices=nz, **slab.timing_summary())
         halo = [None] * world
         dist.all_gather_object(halo, mine)
 
-    if rank == 0:
+    # --full: per-kernel figures of the timed region from the library's HIP-event profile
+    figures = {}
+    if rank == 0 and prof is not None:
         V = nz * n * n
         sub = -(-na // args.os)
         S_s = nz * sub * n
@@ -576,6 +640,13 @@ def measure(args, env):
                        "frac_lds_spec_2.4GHz": kf["frac_lds"], "frac_lds_sustained_2.03GHz": kf["frac_lds_sustained"],
                        "note": "one forward projection = its stepping-class launches; an LDS-gather kernel like the back projector "
                                "(8 B of ds_read_b128 per ray step), co-bound by VALU issue, staging 20-25 % of the call (docs/kernels/fp.md)"}
+        figures = {"roofline": roof, "kernels": kernels}
+        if roof_bp is not None:
+            figures["roofline_bp"] = roof_bp
+        if roof_fp is not None:
+            figures["roofline_fp"] = roof_fp
+
+    if rank == 0:
         units = args.steps if args.strong else args.steps * world
         what = (f"{nz_total} slices of {n}^2 split over {world} z-slab(s)" if args.strong
                 else f"{nz} slices of {n}^2 per GPU; slab-iterations/s over {world} z-slab(s)")
@@ -596,12 +667,10 @@ def measure(args, env):
                        "input": "analytic ellipsoid line integrals + Poisson noise (I0 2e4, peak attenuation 3)",
                        "backend": backend, "oversubscribed": oversubscribed,
                        **({"backend_note": backend_note} if backend_note else {})},
-            "roofline": roof, "kernels": kernels,
         }
-        if roof_bp is not None:
-            line["roofline_bp"] = roof_bp
-        if roof_fp is not None:
-            line["roofline_fp"] = roof_fp
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
+        line.update(figures)
         if halo is not None:
             line["halo"] = halo
         # where the library put its TV scratch arena (docs/kernels/placement.md); "fast": False explains a PD_TV launch
@@ -630,8 +699,9 @@ def north_star_child(args, world, ns_test, gpu_bytes):
     for k in ("n", "nz", "angles", "os", "inner", "reg", "method", "ring"):
         setattr(ns, k, None)
     ns.config, ns.strong, ns.half = "cfg5", True, False
+    # --full: the child reports its rooflines and per-rank halo statistics (--no-cpu / --no-pmc keep out the other legs)
     child_argv = ["--gpus", str(world), "--config", "cfg5", "--strong", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-pmc",
-                  "--no-north-star", "--backend", args.backend]
+                  "--no-north-star", "--backend", args.backend, "--full"]
     if ns_test:
         ns.n, ns.nz, ns.angles, ns.inner = 192, 12 * world, 96, 6
         child_argv += ["--n", "192", "--nz", str(12 * world), "--angles", "96", "--inner", "6"]
@@ -768,7 +838,7 @@ def main():
     env = dict(rank=rank, world=world, device=device, dev_index=dev_index, dist=dist, halo_group=halo_group,
                backend=backend, backend_note=backend_note, oversubscribed=oversubscribed)
     line, sino, lc = measure(args, env)
-    if rank == 0 and not args.no_cpu and world == 1:
+    if rank == 0 and args.full and not args.no_cpu and world == 1:
         line["cpu_baseline"] = cpu_baseline(args, sino, lc)
     del sino
     # N > 1: the headline value above is what the contract asks for (weak scaling of the default workload unless flags /
@@ -780,7 +850,7 @@ def main():
     # line into `north_star` -- or {"skipped": why} on a timeout / non-zero exit / a share that does not fit.
     ns_test = os.environ.get("BENCH_NORTH_STAR_TEST", "0") not in ("", "0")  # dry run of this block on a shared GPU, tiny shape
     ns_default = world >= 4 and not oversubscribed        # from 4 GPUs on every rank's share of configs[4] fits (<= 540 slices)
-    want_ns = (world > 1 and (args.north_star or ns_default) and not args.no_north_star and (ns_test or not oversubscribed)
+    want_ns = (world > 1 and args.full and (args.north_star or ns_default) and not args.no_north_star and (ns_test or not oversubscribed)
                and not (args.strong and args.config == "cfg5") and not os.environ.get("TOMO_BENCH_CHILD"))
     if want_ns:
         if rank == 0:

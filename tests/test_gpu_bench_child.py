@@ -17,7 +17,7 @@ def _run(extra_env, timeout=600):
     env = dict(os.environ, BENCH_NORTH_STAR_TEST="1", **extra_env)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "TOMO_BENCH_ARGV", "TOMO_BENCH_CHILD"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--north-star", "--n", "192", "--nz", "24", "--angles", "96",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--north-star", "--n", "192", "--nz", "24", "--angles", "96",
            "--os", "4", "--inner", "6", "--steps", "1", "--warmup", "1", "--no-cpu", "--no-pmc"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -320,6 +320,85 @@ def test_bench_environment_overrides_and_north_star_footprint(monkeypatch):
     assert fits == {1: False, 2: False, 4: True, 8: True}, fits
 
 
+def test_bench_full_and_dump_outputs(monkeypatch, tmp_path):
+    """A plain run measures only the headline (--full is off by default), --steps below 1 is refused, and --dump-outputs
+    writes float32 / float64 .npy files under 64 MB: a small volume whole, a large one as a fixed sample that does not
+    depend on the run."""
+    import sys
+    import torch
+    import bench
+    monkeypatch.delenv("RANK", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 1, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == str(tmp_path)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+    small = torch.arange(4 * 8 * 8, dtype=torch.float32).reshape(4, 8, 8)
+    assert bench.dump_outputs(small, str(tmp_path / "small")) == ["recon"]
+    np.testing.assert_array_equal(np.load(tmp_path / "small" / "recon.npy"), small.numpy())
+
+    big = torch.rand((9, 1024, 1024), generator=torch.Generator().manual_seed(1))   # 36 MiB: above the whole-volume limit
+    names = bench.dump_outputs(big, str(tmp_path / "big"))
+    assert names == ["recon_sample", "recon_sample_index", "recon_slice_index", "recon_slices"]
+    got = {k: np.load(tmp_path / "big" / f"{k}.npy") for k in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(os.path.getsize(tmp_path / "big" / f"{k}.npy") for k in names) < 64e6
+    zsel = got["recon_slice_index"].astype(np.int64)
+    assert zsel[0] == 0 and zsel[-1] == 8 and len(zsel) == 8
+    np.testing.assert_array_equal(got["recon_slices"], big.numpy()[zsel])
+    flat = got["recon_sample_index"].astype(np.int64)
+    assert len(flat) > 0.9 * bench.DUMP_SAMPLE and np.all(np.diff(flat) > 0)   # drawn with replacement, duplicates dropped
+    np.testing.assert_array_equal(got["recon_sample"], big.numpy().reshape(-1)[flat])
+    bench.dump_outputs(big * 2, str(tmp_path / "again"))   # same shape, other values: same selection
+    np.testing.assert_array_equal(np.load(tmp_path / "again" / "recon_sample_index.npy"), got["recon_sample_index"])
+
+    # one rank of 16: 1/16 of each budget; a 4 MiB plane no longer fits the 2 MiB slice budget, so only the voxel sample
+    names = bench.dump_outputs(big, str(tmp_path / "ranks"), "recon_rank3", 16)
+    assert names == ["recon_rank3_sample", "recon_rank3_sample_index"]
+    flat = np.load(tmp_path / "ranks" / "recon_rank3_sample_index.npy").astype(np.int64)
+    assert 0.9 * bench.DUMP_SAMPLE / 16 < len(flat) <= bench.DUMP_SAMPLE / 16
+    np.testing.assert_array_equal(np.load(tmp_path / "ranks" / "recon_rank3_sample.npy"), big.numpy().reshape(-1)[flat])
+
+
+def test_bench_plain_run_skips_the_full_legs(monkeypatch, capsys):
+    """main() on one rank: the CPU baseline runs only with --full, and measure() is told which kind of run it is (it gates
+    the library's event profile, the roofline blocks and the halo timings on args.full)."""
+    import json
+    import sys
+    import torch
+    import bench
+    calls = {"measure": [], "cpu": 0}
+
+    def measure(args, env):
+        calls["measure"].append(args.full)
+        return {"metric": "fista_os_iterations_per_sec", "value": 1.0}, "sino", 2.0
+
+    def cpu_baseline(args, sino, lc):
+        calls["cpu"] += 1
+        return {"value": 0.5}
+
+    monkeypatch.setattr(bench, "measure", measure)
+    monkeypatch.setattr(bench, "cpu_baseline", cpu_baseline)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 1)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda i: None)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "BENCH_CONFIG", "BENCH_STRONG", "BENCH_NORTH_STAR", "BENCH_LIVE_PMC"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert calls == {"measure": [False], "cpu": 0} and "cpu_baseline" not in line
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--full"])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert calls == {"measure": [False, True], "cpu": 1} and line["cpu_baseline"] == {"value": 0.5}
+
+
 def test_north_star_child_job_is_supervised(monkeypatch, tmp_path):
     """The north-star block of a multi-GPU run is a child job under a wall-clock limit: a child that hangs is killed with its
     whole process group and reported as skipped, a child that fails is reported with its exit code, a child that prints a
@@ -363,6 +442,7 @@ def test_north_star_child_job_is_supervised(monkeypatch, tmp_path):
     assert block["value"] == 1.25 and block["scaling"] == "strong" and "skipped" not in block, block
     argv = block["config"]["argv"]
     assert argv[:6] == ["--gpus", "8", "--config", "cfg5", "--strong", "--steps"] and "--no-north-star" in argv
+    assert "--full" in argv   # the child reports its rooflines and halo statistics, as before --full existed
     # (4) a share that cannot fit is not even started
     block = bench.north_star_child(args, 2, False, 288e9)
     assert "needs ~" in block["skipped"] and block["per_gpu_slices"] == 1080

@@ -286,90 +286,6 @@ __global__ __launch_bounds__(BT) void fp_tiled_kernel(FpTiledArgs a)
     }
 }
 
-// ---- per-angle lane -> pixel multiplier of the whole-row form (host).  Bank model of one ds_read_b128 service group: its 16
-// lanes hold 16 consecutive logical positions t, i.e. pixels m*t mod bt, i.e. LDS slots floor(x0 + s*pixel) with s = 1/|cos|
-// (|inv| of the angle record) in [1, 1.4143]; the LDS serves the group in as many cycles as the fullest of its 16 bank rows
-// (slot mod 16) holds DIFFERENT slots.  m = 1 spans up to 22 slots (two-way conflicts: 1.5-2.0 cycles at 20-45 degrees), the
-// best odd m < 64 per angle 1.5-1.7.  Measured on the kernel's own loop: tools/probes/fp_combo_probe.hip,
-// profiles/r6_fp_combo_probe.txt (sampling loop x 1.09 alone, x 1.215 together with 8 slices per thread).
-static double fp_bank_model(double s, int m, int bt)
-{
-    double total = 0.0;
-    int cnt = 0;
-    for (int ph = 0; ph < 8; ++ph) {
-        const double x0 = 3.0 + ph * 0.91;
-        for (int t0 = 0; t0 + 16 <= bt; t0 += 16 * 5) {   // every fifth service group
-            int distinct[16], nd = 0, rows[16] = {0};
-            for (int j = 0; j < 16; ++j) {
-                const int slot = (int)std::floor(x0 + s * (double)((m * (t0 + j)) % bt));
-                bool seen = false;
-                for (int q = 0; q < nd; ++q) seen |= distinct[q] == slot;   // same slot: one broadcast
-                if (!seen) { distinct[nd++] = slot; ++rows[slot & 15]; }
-            }
-            int worst = 1;
-            for (int r = 0; r < 16; ++r) worst = std::max(worst, rows[r]);
-            total += worst;
-            ++cnt;
-        }
-    }
-    return cnt ? total / cnt : 1.0;
-}
-
-// multiplier for stride s and tile width bt, memoised on a 1/512 grid of s (the model is smooth at that scale and a
-// context asks for up to a few thousand angles)
-static int fp_lane_mult(double s, int bt)
-{
-    static std::mutex mu;
-    static std::map<std::pair<int, int>, int> memo;
-    const int key = (int)std::lround((std::min(std::max(s, 1.0), 1.4143) - 1.0) * 512.0);
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = memo.find({bt, key});
-    if (it != memo.end()) return it->second;
-    const double sq = 1.0 + key / 512.0;
-    int best_m = 1;
-    double best = fp_bank_model(sq, 1, bt);
-    for (int m = 3; m < 64; m += 2) {
-        if (std::gcd(m, bt) != 1) continue;   // m*t mod bt must be a bijection (bt = 896 = 2^7 * 7 rules out 7, 21, ...)
-        const double c = fp_bank_model(sq, m, bt);
-        if (c < best - 1e-3) { best = c; best_m = m; }
-    }
-    memo[{bt, key}] = best_m;
-    return best_m;
-}
-
-// Upper bound (host, same float arithmetic as the kernel) of the staged window width over all groups / tiles / rows.
-// The width is a max of affine functions of the row index minus a min of affine functions, hence convex: its maximum
-// over the march is attained at the first or the last row.
-static int fp_window_bound(const tomo_angle_t *tab, const int *order, int n_class, int n, int nu, int tile = 256,
-                           int group = FP_A)
-{
-    const float half_n = 0.5f * (float)n - 0.5f, half_u = 0.5f * (float)nu - 0.5f;
-    int bound = 2;
-    const int nut = ceil_div(nu, tile);
-    for (int g = 0; g * group < n_class; ++g) {
-        const int ng = std::min(group, n_class - g * group);
-        for (int ut = 0; ut < nut; ++ut) {
-            for (int e = 0; e < 2; ++e) {
-                const float kw = (float)(e ? n - 1 : 0) - half_n;
-                float fmin = 3.0e38f, fmax = -3.0e38f;
-                for (int i = 0; i < ng; ++i) {
-                    const tomo_angle_t &t = tab[order[g * group + i]];
-                    const float o0 = std::fmaf(((float)(ut * tile) - half_u) + t.cor, t.inv, half_n);
-                    const float o1 = std::fmaf(((float)(ut * tile + tile - 1) - half_u) + t.cor, t.inv, half_n);
-                    const float f0 = std::fmaf(kw, t.slope, o0), f1 = std::fmaf(kw, t.slope, o1);
-                    fmin = std::min(fmin, std::min(f0, f1));
-                    fmax = std::max(fmax, std::max(f0, f1));
-                }
-                // UNCLIPPED width: only that is convex in the row index (clipping to the volume can make the end rows
-                // narrow while a middle row, fully inside the volume, is wide); the clip is applied once at the end
-                const double wdt = (double)std::floor(fmax) + 1.0 - (double)std::floor(fmin) + 1.0;
-                bound = std::max(bound, (int)std::min(wdt, (double)n + 4.0));
-            }
-        }
-    }
-    return std::min(bound + 2, n + 4);
-}
-
 // ---- synchronous (non-pipelined) form: stage kc rows, barrier, sample, barrier.  Small LDS footprint, so many
 //      workgroups per CU hide the staging latency instead of a register prefetch.  Fallback for windows wider than the
 //      pipelined kernel supports, and variant 2 for A/B measurement (1024^3 x 75 angles: 22.8 ms vs 15.6 ms pipelined).

@@ -649,6 +649,337 @@ int fp_scratch(tomo_ctx *ctx)
     return TOMO_OK;
 }
 
+// ------------------------------------------------------------------------------------------ FP form selection (host)
+// Every window bound the selection asks for depends on the geometry only: fp_tables computes them at context creation,
+// fp_plan turns them into at most four launches (or the march) without a HIP call, and fp_run launches the plan.
+
+// ---- per-angle lane -> pixel multiplier of the whole-row form (host).  Bank model of one ds_read_b128 service group: its 16
+// lanes hold 16 consecutive logical positions t, i.e. pixels m*t mod bt, i.e. LDS slots floor(x0 + s*pixel) with s = 1/|cos|
+// (|inv| of the angle record) in [1, 1.4143]; the LDS serves the group in as many cycles as the fullest of its 16 bank rows
+// (slot mod 16) holds DIFFERENT slots.  m = 1 spans up to 22 slots (two-way conflicts: 1.5-2.0 cycles at 20-45 degrees), the
+// best odd m < 64 per angle 1.5-1.7.  Measured on the kernel's own loop: tools/probes/fp_combo_probe.hip,
+// profiles/r6_fp_combo_probe.txt (sampling loop x 1.09 alone, x 1.215 together with 8 slices per thread).
+static double fp_bank_model(double s, int m, int bt)
+{
+    double total = 0.0;
+    int cnt = 0;
+    for (int ph = 0; ph < 8; ++ph) {
+        const double x0 = 3.0 + ph * 0.91;
+        for (int t0 = 0; t0 + 16 <= bt; t0 += 16 * 5) {   // every fifth service group
+            int distinct[16], nd = 0, rows[16] = {0};
+            for (int j = 0; j < 16; ++j) {
+                const int slot = (int)std::floor(x0 + s * (double)((m * (t0 + j)) % bt));
+                bool seen = false;
+                for (int q = 0; q < nd; ++q) seen |= distinct[q] == slot;   // same slot: one broadcast
+                if (!seen) { distinct[nd++] = slot; ++rows[slot & 15]; }
+            }
+            int worst = 1;
+            for (int r = 0; r < 16; ++r) worst = std::max(worst, rows[r]);
+            total += worst;
+            ++cnt;
+        }
+    }
+    return cnt ? total / cnt : 1.0;
+}
+
+// multiplier for stride s and tile width bt, memoised on a 1/512 grid of s (the model is smooth at that scale and a
+// context asks for up to a few thousand angles)
+static int fp_lane_mult(double s, int bt)
+{
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, int> memo;
+    const int key = (int)std::lround((std::min(std::max(s, 1.0), 1.4143) - 1.0) * 512.0);
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = memo.find({bt, key});
+    if (it != memo.end()) return it->second;
+    const double sq = 1.0 + key / 512.0;
+    int best_m = 1;
+    double best = fp_bank_model(sq, 1, bt);
+    for (int m = 3; m < 64; m += 2) {
+        if (std::gcd(m, bt) != 1) continue;   // m*t mod bt must be a bijection (bt = 896 = 2^7 * 7 rules out 7, 21, ...)
+        const double c = fp_bank_model(sq, m, bt);
+        if (c < best - 1e-3) { best = c; best_m = m; }
+    }
+    memo[{bt, key}] = best_m;
+    return best_m;
+}
+
+// Upper bound (host, same float arithmetic as the kernel) of the staged window width over all groups / tiles / rows.
+// The width is a max of affine functions of the row index minus a min of affine functions, hence convex: its maximum
+// over the march is attained at the first or the last row.
+static int fp_window_bound(const tomo_angle_t *tab, const int *order, int n_class, int n, int nu, int tile = 256,
+                           int group = FP_A)
+{
+    const float half_n = 0.5f * (float)n - 0.5f, half_u = 0.5f * (float)nu - 0.5f;
+    int bound = 2;
+    const int nut = ceil_div(nu, tile);
+    for (int g = 0; g * group < n_class; ++g) {
+        const int ng = std::min(group, n_class - g * group);
+        for (int ut = 0; ut < nut; ++ut) {
+            for (int e = 0; e < 2; ++e) {
+                const float kw = (float)(e ? n - 1 : 0) - half_n;
+                float fmin = 3.0e38f, fmax = -3.0e38f;
+                for (int i = 0; i < ng; ++i) {
+                    const tomo_angle_t &t = tab[order[g * group + i]];
+                    const float o0 = std::fmaf(((float)(ut * tile) - half_u) + t.cor, t.inv, half_n);
+                    const float o1 = std::fmaf(((float)(ut * tile + tile - 1) - half_u) + t.cor, t.inv, half_n);
+                    const float f0 = std::fmaf(kw, t.slope, o0), f1 = std::fmaf(kw, t.slope, o1);
+                    fmin = std::min(fmin, std::min(f0, f1));
+                    fmax = std::max(fmax, std::max(f0, f1));
+                }
+                // UNCLIPPED width: only that is convex in the row index (clipping to the volume can make the end rows
+                // narrow while a middle row, fully inside the volume, is wide); the clip is applied once at the end
+                const double wdt = (double)std::floor(fmax) + 1.0 - (double)std::floor(fmin) + 1.0;
+                bound = std::max(bound, (int)std::min(wdt, (double)n + 4.0));
+            }
+        }
+    }
+    return std::min(bound + 2, n + 4);
+}
+
+constexpr int FP_A16 = 16;   // angles per workgroup of the dense form
+// measured at 384..640-wide detectors (tools/kernel_bench.py): the whole-row form is 7-37 % faster than 256-pixel tiles
+// there as well, so it is considered from 128 pixels up (it used to start at 768)
+constexpr int FP_WIDE_MIN_NU = 128;
+// lane multipliers, measured A/B (profiles/r6_fp_lane_multiplier_ab.txt): x 1.024 at 1024 pixels (configs[2]), x 1.047 at
+// 896 (configs[4] share), 0.97-0.99 at 256-640 pixels where the un-permute of the epilogue is not paid back: from 768
+// pixels up only
+constexpr int FP_MULT_MIN_BT = 768;
+
+// whole-row form: tiles of equal width: 2560 pixels = 3 tiles of 896 (14 waves), not 2.5 tiles of 1024
+static int fp_wide_tiles(int nu) { return ceil_div(nu, 1024); }
+static int fp_wide_bt(int nu) { return std::min(1024, ceil_div(ceil_div(nu, fp_wide_tiles(nu)), 64) * 64); }
+
+enum FpForm { FP_WHOLE_ROW, FP_DENSE16, FP_TILED, FP_TILED_SYNC };
+
+// one launch of the forward projector: the angles of one stepping class or, whole-row form up to 1024 pixels, of both
+// sign classes of an axis
+struct FpLaunch {
+    FpForm form;
+    int cls;              // stepping class (the first of a merged axis); x-stepping classes (cls >> 1) read the transposed volume
+    bool merged;          // whole-row form: classes cls and cls + 1 in one launch
+    size_t order_off;     // first entry in the order table (and in the lane-multiplier table)
+    int n_angles;
+    int wpitch;           // LDS pitch (float4) per staged row
+    int threads;          // workgroup size = detector pixels per tile
+    int passes, kc;       // column passes per staged row, rows per chunk
+    int nut, ngroups;     // detector tiles, angle groups
+    size_t lds;           // dynamic LDS bytes
+    long blocks;
+    bool mult;            // per-angle lane -> pixel multipliers (whole-row form)
+};
+
+struct FpPlan {
+    bool march = false;   // the un-tiled march kernel over the whole subset instead
+    int count = 0;
+    FpLaunch l[4];
+};
+
+static long fp_blocks(int nz, int nut, int ngroups) { return 8L * (((long)ceil_div(nz, 4) * nut * ngroups + 7) / 8); }
+
+// Whole-row form (one workgroup per detector row tile, see fp_tiled.inl) for the `nc` angles at `off` of the order table,
+// window `wp`.  Chosen when the 256-pixel tiles would stage at least 0.9x what whole rows need (cost_tiles) and it fits
+// in LDS; false otherwise.
+static bool fp_plan_whole_row(const tomo_ctx *ctx, int variant, int cls, bool merged, size_t off, int nc, int wp,
+                              double cost_tiles, FpLaunch &l)
+{
+    const int nut = fp_wide_tiles(ctx->nu), bt = fp_wide_bt(ctx->nu);
+    const double cost_rows = (double)nut * ceil_div(nc, FP_A) * wp;
+    // measured: with equal staging volume the whole-row form is still the faster one (one workgroup per CU streams rows
+    // through a deep prefetch pipeline; BASELINE configs[3], 1500 dense angles at 2048: 0.59 -> 0.51 s per ADMM
+    // iteration), so it is taken whenever it does not stage clearly MORE than the 256-pixel tiles
+    const bool pays = cost_tiles >= 0.9 * cost_rows;
+    const int passes = ceil_div(wp, bt);
+    // rows per chunk: 4 (or 2) double-buffered rows up to two column passes; detectors wider than 2048
+    // (3-5 passes, BASELINE configs[4] is 2560 wide) keep ONE tile (two barriers per chunk) of as many
+    // rows as fit in the 160 KiB of LDS next to the per-row window tables
+    int kc = 4;
+    const size_t tab = (size_t)ctx->n * 8;
+    size_t lds = (size_t)2 * kc * wp * 16 + tab;
+    if (passes <= 2) {
+        if (lds > 160 * 1024) { kc = 2; lds = (size_t)2 * kc * wp * 16 + tab; }
+    } else {
+        kc = passes == 3 ? 2 : 1;  // 3 rows (9 float4 in flight per thread) spill at 1024 threads
+        while (kc > 1 && (size_t)kc * wp * 16 + tab > 160 * 1024) --kc;
+        lds = (size_t)kc * wp * 16 + tab;
+    }
+    if (!(pays && passes <= 5 && lds <= 160 * 1024)) return false;
+    // per-angle lane -> pixel multipliers (round 6, fp_tables; variant 4, dev flavour: pixel = lane): the un-permute of
+    // the epilogue needs two LDS rows of bt float4 inside the tile area
+    const bool mult = bt >= FP_MULT_MIN_BT && (size_t)2 * bt * 16 <= lds - tab && variant != 4;
+    l = {FP_WHOLE_ROW, cls, merged, off, nc, wp, bt, passes, kc, nut, ceil_div(nc, FP_A), lds,
+         fp_blocks(ctx->nz, nut, ceil_div(nc, FP_A)), mult};
+    return true;
+}
+
+// Dense form (round 4): 256 detector pixels x 16 angles per workgroup.  When neighbouring angles of the slope order are a
+// fraction of a degree apart (BASELINE configs[3]: 1500 angles, no subsets) a 16-angle group's window is hardly wider
+// than an 8-angle group's, so every staged volume row serves twice the rays: 0.12 staged columns per sample against
+// 0.18 for whole rows x 8 angles.  Three 256-thread workgroups per CU (12 waves, <= 168 registers).  False where it
+// does not apply.
+static bool fp_plan_dense16(const tomo_ctx *ctx, const tomo_subset &s, int variant, int cls, size_t off, FpLaunch &l)
+{
+    const int nc = s.n_class[cls], wp = s.wbound16[cls];
+    if (nc < 2 * FP_A16) return false;
+    if (wp > 512) return false;  // two column passes at most
+    const int passes = ceil_div(wp, 256);
+    const int kc = passes == 1 ? 4 : 2;  // four float4 staging items per thread and chunk either way
+    const size_t lds = (size_t)2 * kc * wp * 16 + (size_t)ctx->n * 8;
+    if (lds > 64 * 1024) return false;  // three workgroups per CU
+    const int nut = ceil_div(ctx->nu, 256), ngroups = ceil_div(nc, FP_A16);
+    const long wgs = (long)ceil_div(ctx->nz, 4) * nut * ngroups;
+    if (fp_blocks(ctx->nz, nut, ngroups) > 0x7fffffffL) return false;
+    // a launch per sign class must still fill the chip several times over (768 resident workgroups): on BASELINE
+    // configs[1] (256^3, 360 angles) the form left half the CUs idle -- 542 instead of 702 iterations/s
+    if (wgs < 4 * 768 && variant != 3) return false;
+    l = {FP_DENSE16, cls, false, off, nc, wp, 256, passes, kc, nut, ngroups, lds, fp_blocks(ctx->nz, nut, ngroups), false};
+    return true;
+}
+
+// 256-pixel tiles x 8 angles for one class.  Windows of up to 1280 columns run the register-prefetch pipeline
+// (double-buffered up to 512 columns, single-buffered beyond); wider ones (detectors wider than 1024 whose whole-row
+// form does not fit in LDS) and variant 2 run the synchronous form: stage, barrier, sample, barrier, with a small LDS
+// footprint so that several workgroups per CU hide the staging latency.
+static FpLaunch fp_plan_tiled(const tomo_ctx *ctx, const tomo_subset &s, int variant, int cls, size_t off)
+{
+    const int nc = s.n_class[cls], wp = s.wbound[cls], nut = ceil_div(ctx->nu, 256), ngroups = ceil_div(nc, FP_A);
+    const long blocks = fp_blocks(ctx->nz, nut, ngroups);
+    const int passes = ceil_div(wp, 256);
+    if (variant == 2 || wp > FP_MAX_WPITCH) {
+        const int kc = std::max(1, std::min(8, 40000 / (wp * 16)));
+        return {FP_TILED_SYNC, cls, false, off, nc, wp, 256, passes, kc, nut, ngroups, (size_t)kc * wp * 16, blocks, false};
+    }
+    // float4 staging items per thread and chunk (M = passes x rows per chunk) and double buffering, per pass count (1..5)
+    const int m = passes <= 2 ? 8 : (passes == 5 ? 10 : 12);
+    const int kc = m / passes;
+    const size_t lds = (size_t)(passes <= 2 ? 2 : 1) * kc * wp * 16 + (size_t)ctx->n * 8;
+    return {FP_TILED, cls, false, off, nc, wp, 256, passes, kc, nut, ngroups, lds, blocks, false};
+}
+
+// The forward projector's kernels for one subset (no HIP calls): per stepping axis the dense form or the whole-row form
+// where they pay, 256-pixel tiles for every class left over, or the march when a class's window does not fit in LDS.
+static int fp_plan(const tomo_ctx *ctx, const tomo_subset &s, int variant, FpPlan &plan)
+{
+    // dense form taken when it stages <= 0.75x what whole rows x 8 angles would
+    constexpr double FP_DENSE16_PAYS = 0.75;
+    plan = FpPlan();
+    // tiled forms unless a class's LDS window would not fit (very wide angular spread on a very wide volume): one staged
+    // row must fit in 64 KiB of LDS
+    plan.march = variant == 1;
+    for (int c = 0; c < 4; ++c) plan.march |= s.n_class[c] > 0 && s.wbound[c] > 4000;
+    if (plan.march) return TOMO_OK;
+    const int nu = ctx->nu;
+    size_t off[4] = {s.table_offset};
+    for (int c = 1; c < 4; ++c) off[c] = off[c - 1] + s.n_class[c - 1];
+    bool done[4] = {false, false, false, false};
+    for (int d = 0; d < 2 && (variant == 0 || variant == 3 || variant == 4) && nu >= FP_WIDE_MIN_NU; ++d) {
+        const int c0 = 2 * d, c1 = c0 + 1, nc0 = s.n_class[c0], nc1 = s.n_class[c1], nc = nc0 + nc1;
+        if (nc == 0) continue;
+        // dense form for both sign classes of the axis when it stages clearly less than whole rows x 8 angles would
+        // (variant 3, dev flavour: whenever it is applicable -- the A/B and parity tests of this form)
+        FpLaunch e0, e1;
+        bool take = (nc0 == 0 || fp_plan_dense16(ctx, s, variant, c0, off[c0], e0)) &&
+                    (nc1 == 0 || fp_plan_dense16(ctx, s, variant, c1, off[c1], e1));
+        if (take && variant != 3) {
+            const double cost = (nc0 ? (double)e0.nut * e0.ngroups * e0.wpitch : 0.0) +
+                                (nc1 ? (double)e1.nut * e1.ngroups * e1.wpitch : 0.0);
+            const int nut_w = fp_wide_tiles(nu);
+            const double rows = nu <= 1024 ? (double)nut_w * ceil_div(nc, FP_A) * s.wbound_wide[c0]
+                                           : (double)nut_w * ceil_div(nc0, FP_A) * s.wbound_wide[c0] +
+                                             (double)nut_w * ceil_div(nc1, FP_A) * s.wbound_wide[c1];
+            take = cost <= FP_DENSE16_PAYS * rows;
+        }
+        if (take) {
+            if (nc0) plan.l[plan.count++] = e0;
+            if (nc1) plan.l[plan.count++] = e1;
+            done[c0] = done[c1] = true;
+            continue;
+        }
+        if (variant == 3) continue;
+        const int nut = ceil_div(nu, 256);
+        const double ct0 = (double)nut * ceil_div(nc0, FP_A) * s.wbound[c0];
+        const double ct1 = (double)nut * ceil_div(nc1, FP_A) * s.wbound[c1];
+        FpLaunch l;
+        if (nu <= 1024) {
+            // one 1024-pixel tile = the whole detector row: its window does not care about the sign of the detector
+            // slope, so the two classes of an axis (adjacent in the order table) are merged -- 37 angles make 5 groups
+            // of 8 instead of 3 + 3
+            if (fp_plan_whole_row(ctx, variant, c0, true, off[c0], nc, s.wbound_wide[c0], ct0 + ct1, l)) {
+                plan.l[plan.count++] = l;
+                done[c0] = done[c1] = true;
+            }
+        } else {
+            // several 1024-pixel tiles per row (2560-wide detectors, BASELINE configs[4]): a group that mixes the two
+            // signs of the slope maps a tile to BOTH ends of the volume row (window = the whole row, 2564 columns for
+            // every tile); class by class a tile's window stays ~1400 columns
+            for (int c = c0; c <= c1; ++c)
+                if (s.n_class[c] > 0 && fp_plan_whole_row(ctx, variant, c, false, off[c], s.n_class[c], s.wbound_wide[c],
+                                                          c == c0 ? ct0 : ct1, l)) {
+                    plan.l[plan.count++] = l;
+                    done[c] = true;
+                }
+        }
+    }
+    for (int c = 0; c < 4; ++c)  // one launch per stepping class (x-stepping classes read the transposed copy)
+        if (s.n_class[c] > 0 && !done[c]) plan.l[plan.count++] = fp_plan_tiled(ctx, s, variant, c, off[c]);
+    for (int i = 0; i < plan.count; ++i) {
+        TOMO_REQUIRE(plan.l[i].blocks <= 0x7fffffffL, "problem too large for one FP launch");
+        TOMO_REQUIRE(plan.l[i].form != FP_TILED_SYNC || plan.l[i].lds <= 64 * 1024,
+                     "forward-projection window does not fit in LDS");
+    }
+    return TOMO_OK;
+}
+
+// what one launch contributes to tomo_ctx_kernel_path("fp")
+static std::string fp_path_text(const FpLaunch &l)
+{
+    const std::string cls = "class" + std::to_string(l.cls) + ":", passes = std::to_string(l.passes) + " passes";
+    switch (l.form) {
+    case FP_WHOLE_ROW:
+        return std::string(l.cls >> 1 ? "x" : "y") + (l.merged ? "" : (l.cls & 1) ? "-" : "+") + ":whole-row(" +
+               std::to_string(l.threads) + " threads, " + passes + ", " + std::to_string(l.kc) + " rows/chunk) ";
+    case FP_DENSE16: return cls + "dense(256 pixels x 16 angles, " + passes + ") ";
+    case FP_TILED: return cls + "tiled-pipelined(256 threads, " + passes + ") ";
+    default: return cls + "tiled-sync(window " + std::to_string(l.wpitch) + ") ";
+    }
+}
+
+// The kernel instantiation that serves a plan entry -- (form, column passes, float4 staging items per thread and chunk
+// = passes x rows per chunk; double-buffered tile up to two passes) -- launched.
+template <bool L8, bool RES>
+static void fp_launch(const FpLaunch &l, const FpTiledArgs &t, hipStream_t st)
+{
+    using Kernel = void (*)(FpTiledArgs);
+    const int m = l.passes * l.kc;
+    Kernel k;
+    switch (l.form) {
+    case FP_TILED_SYNC:
+        fp_tiled_sync_kernel<L8, RES, 256, FP_A><<<(unsigned)l.blocks, 256, l.lds, st>>>(t, l.kc);
+        return;
+    case FP_WHOLE_ROW:   // the 1024-thread instantiations, launched with l.threads <= 1024
+        if (l.passes == 1) k = fp_tiled_kernel<L8, RES, 1, 4, true, 1024>;
+        else if (l.passes == 2 && m == 8) k = fp_tiled_kernel<L8, RES, 2, 8, true, 1024>;
+        else if (l.passes == 2) k = fp_tiled_kernel<L8, RES, 2, 4, true, 1024>;
+        else if (l.passes == 3 && m == 6) k = fp_tiled_kernel<L8, RES, 3, 6, false, 1024>;
+        else if (l.passes == 3) k = fp_tiled_kernel<L8, RES, 3, 3, false, 1024>;
+        else if (l.passes == 4) k = fp_tiled_kernel<L8, RES, 4, 4, false, 1024>;
+        else k = fp_tiled_kernel<L8, RES, 5, 5, false, 1024>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds);
+        break;
+    case FP_DENSE16:
+        if (l.passes == 1) k = fp_tiled_kernel<L8, RES, 1, 4, true, 256, FP_A16>;
+        else k = fp_tiled_kernel<L8, RES, 2, 4, true, 256, FP_A16>;
+        break;
+    default:
+        if (l.passes == 1) k = fp_tiled_kernel<L8, RES, 1, 8, true, 256>;
+        else if (l.passes == 2) k = fp_tiled_kernel<L8, RES, 2, 8, true, 256>;
+        else if (l.passes == 3) k = fp_tiled_kernel<L8, RES, 3, 12, false, 256>;
+        else if (l.passes == 4) k = fp_tiled_kernel<L8, RES, 4, 12, false, 256>;
+        else k = fp_tiled_kernel<L8, RES, 5, 10, false, 256>;
+    }
+    k<<<(unsigned)l.blocks, l.threads, l.lds, st>>>(t);
+}
+
 int fp_run(tomo_ctx *ctx, int subset, const float *vol, const float *b, const float *w, int gathered, int fidelity,
            float *out, void *stream, const float *ring = nullptr, float ring_scale = 0.0f, int zquad = 0,
            int robust = TOMO_ROBUST_NONE, float rdelta = 0.0f)
@@ -656,7 +987,7 @@ int fp_run(tomo_ctx *ctx, int subset, const float *vol, const float *b, const fl
     TOMO_REQUIRE(ctx != nullptr, "ctx is NULL");
     TOMO_REQUIRE(vol != nullptr && out != nullptr, "NULL data pointer");
     TOMO_REQUIRE(subset < ctx->os, "subset %d out of range (OS_number %d)", subset, ctx->os);
-    tomo_subset &s = (subset < 0 || ctx->os == 1) ? ctx->subsets[0] : ctx->subsets[1 + subset];
+    const tomo_subset &s = (subset < 0 || ctx->os == 1) ? ctx->subsets[0] : ctx->subsets[1 + subset];
     hipStream_t st = as_stream(stream);
     // the transposed copy tomo_momentum_transposed left behind is a ONE-SHOT token: whatever this call does with it
     // (use it, find it belongs to another volume / stream, return early), it is spent before anything else happens
@@ -692,335 +1023,47 @@ int fp_run(tomo_ctx *ctx, int subset, const float *vol, const float *b, const fl
     a.zquad = (b != nullptr) ? zquad : 0;
     if (a.zquad && (((uintptr_t)out) & 15) != 0)
         return tomo_fail(TOMO_E_INVALID, "the quad-interleaved residual must be 16-byte aligned");
-    dim3 grid(ceil_div(ctx->nu, 256), s.size, ceil_div(ctx->nz, 4));
     tomo_prof_scope prof(PROF_FP, st, 1);
     ctx->last_fp_path.clear();
     const bool l8 = (ctx->flags & TOMO_FLAG_LERP8) != 0;
-    // tiled variant unless a class's LDS window would not fit (very wide angular spread on a very wide volume)
-    bool tiled = (g_variant_fp != 1);
-    if (tiled) {
-        size_t off = s.table_offset;
-        for (int c = 0; c < 4; ++c) {
-            if (s.n_class[c] > 0 && s.wbound[c] < 0)
-                s.wbound[c] = fp_window_bound(ctx->host_table.data() + s.table_offset, ctx->host_fp_order.data() + off,
-                                              s.n_class[c], ctx->n, ctx->nu);
-            if (s.n_class[c] > 0 && s.wbound[c] > 4000) tiled = false;  // one staged row must fit in 64 KiB of LDS
-            off += s.n_class[c];
+    FpPlan plan;
+    const int rc = fp_plan(ctx, s, g_variant_fp, plan);
+    if (rc != TOMO_OK) return rc;
+    if (plan.march) {
+        ctx->last_fp_path = "march(no LDS)";
+        if (g_variant_fp != 1) tomo_warn_once("fp_march", "forward projection: a staged row window exceeds 64 KiB of LDS, "
+                                              "falling back to the un-tiled march kernel (about 4x slower)");
+        dim3 grid(ceil_div(ctx->nu, 256), s.size, ceil_div(ctx->nz, 4));
+        if (b) {
+            if (l8) fp_march_kernel<true, true><<<grid, 256, 0, st>>>(a);
+            else fp_march_kernel<false, true><<<grid, 256, 0, st>>>(a);
+        } else {
+            if (l8) fp_march_kernel<true, false><<<grid, 256, 0, st>>>(a);
+            else fp_march_kernel<false, false><<<grid, 256, 0, st>>>(a);
         }
-    }
-    if (tiled) {
-        // ---- wide form: one 1024-thread workgroup per detector row (see fp_tiled.inl), one launch per stepping AXIS: a
-        // whole-row window does not care about the sign of the detector slope, so the two classes of an axis (adjacent in
-        // the order table) are merged -- 37 angles make 5 groups of 8 instead of 3 + 3.  Chosen when the 256-pixel tiles
-        // would stage at least 0.9x what whole rows need (see `pays` below), and it fits in LDS.
-        // measured at 384..640-wide detectors (tools/kernel_bench.py): the whole-row form is 7-37 % faster than 256-pixel
-        // tiles there as well, so it is considered from 128 pixels up (it used to start at 768)
-        constexpr int FP_WIDE_MIN_NU = 128;
-        constexpr double FP_DENSE16_PAYS = 0.75;  // dense form taken when it stages <= 0.75x what whole rows x 8 angles would
-        bool done[4] = {false, false, false, false};
-        // try_wide: whole-row form for `nc` angles starting at `off_d` of the order table (one stepping class, or the two
-        // sign classes of an axis merged); returns 1 if launched, 0 if the 256-pixel tiles are the better choice, < 0 on error
-        auto try_wide = [&](int d, size_t off_d, int nc, int &wp_cache, double cost_tiles, const char *label) -> int {
-            // tiles of equal width: 2560 pixels = 3 tiles of 896 (14 waves), not 2.5 tiles of 1024
-            const int nut_w = ceil_div(a.nu, 1024);
-            const int bt = std::min(1024, ceil_div(ceil_div(a.nu, nut_w), 64) * 64);
-            if (wp_cache < 0)
-                wp_cache = fp_window_bound(ctx->host_table.data() + s.table_offset, ctx->host_fp_order.data() + off_d, nc,
-                                           ctx->n, ctx->nu, bt);
-            const int wp = wp_cache;
-            const double cost_rows = (double)nut_w * ceil_div(nc, FP_A) * wp;
-            // measured: with equal staging volume the whole-row form is still the faster one (one workgroup per CU streams rows
-            // through a deep prefetch pipeline; BASELINE configs[3], 1500 dense angles at 2048: 0.59 -> 0.51 s per ADMM
-            // iteration), so it is taken whenever it does not stage clearly MORE than the 256-pixel tiles
-            const bool pays = cost_tiles >= 0.9 * cost_rows;
-            const int passes_w = ceil_div(wp, bt);
-            // rows per chunk: 4 (or 2) double-buffered rows up to two column passes; detectors wider than 2048
-            // (3-5 passes, BASELINE configs[4] is 2560 wide) keep ONE tile (two barriers per chunk) of as many
-            // rows as fit in the 160 KiB of LDS next to the per-row window tables
-            int kc_w = 4;
-            const size_t tab_w = (size_t)a.n * 8;
-            size_t smem_w = (size_t)2 * kc_w * wp * 16 + tab_w;
-            if (passes_w <= 2) {
-                if (smem_w > 160 * 1024) { kc_w = 2; smem_w = (size_t)2 * kc_w * wp * 16 + tab_w; }
-            } else {
-                kc_w = passes_w == 3 ? 2 : 1;  // 3 rows (9 float4 in flight per thread) spill at 1024 threads
-                while (kc_w > 1 && (size_t)kc_w * wp * 16 + tab_w > 160 * 1024) --kc_w;
-                smem_w = (size_t)kc_w * wp * 16 + tab_w;
-            }
-            if (!(pays && passes_w <= 5 && smem_w <= 160 * 1024)) return 0;
-            // per-angle lane -> pixel multipliers (round 6), built once per context for this tile width; the un-permute of
-            // the epilogue needs two LDS rows of bt float4 inside the tile area
-            const int *mult_d = nullptr;
-#ifndef TOMO_FP_NO_LANE_MULT   // A/B builds only (tools/run_ab.sh)
-            // measured A/B (profiles/r6_fp_lane_multiplier_ab.txt): x 1.024 at 1024 pixels (configs[2]), x 1.047 at 896 (configs[4]
-            // share), 0.97-0.99 at 256-640 pixels where the un-permute of the epilogue is not paid back: from 768 pixels up only
-            constexpr int FP_MULT_MIN_BT = 768;
-            if (bt >= FP_MULT_MIN_BT && (size_t)2 * bt * 16 <= smem_w - tab_w && g_variant_fp != 4) {
-                if (ctx->dev_fp_mult == nullptr || ctx->fp_mult_bt != bt) {
-                    std::vector<int> mh(ctx->host_fp_order.size(), 1);
-                    for (const tomo_subset &ss : ctx->subsets)
-                        for (int i = 0, ne = ss.n_class[0] + ss.n_class[1] + ss.n_class[2] + ss.n_class[3]; i < ne; ++i) {
-                            const tomo_angle_t &rec = ctx->host_table[ss.table_offset + ctx->host_fp_order[ss.table_offset + i]];
-                            mh[ss.table_offset + i] = fp_lane_mult(std::fabs((double)rec.inv), bt);
-                        }
-                    // (this lambda reports errors as -1, not as a TOMO_E_* code)
-                    if (ctx->dev_fp_mult == nullptr) {
-                        if (hipMalloc((void **)&ctx->dev_fp_mult, std::max<size_t>(mh.size(), 1) * sizeof(int)) != hipSuccess) return -1;
-                    } else if (hipDeviceSynchronize() != hipSuccess) {   // a launch in flight may still read the old table
-                        return -1;
-                    }
-                    if (hipMemcpy(ctx->dev_fp_mult, mh.data(), mh.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
-                    ctx->fp_mult_bt = bt;
-                }
-                mult_d = ctx->dev_fp_mult + off_d;
-            }
-#endif
-            FpTiledArgs t;
-            t.src = d ? a.volT : a.vol;
-            t.tab = a.tab;
-            t.order = ctx->dev_fp_order + off_d;
-            t.mult = mult_d;
-            t.n_class = nc;
-            t.nz = a.nz; t.n = a.n; t.nu = a.nu; t.na = a.na; t.na_full = a.na_full;
-            t.out = out; t.b = b; t.w = w; t.fidelity = fidelity; t.gathered = gathered;
-            t.ring = ring; t.ring_scale = ring_scale; t.zquad = a.zquad; t.robust = a.robust; t.rdelta = a.rdelta;
-            t.wpitch = wp;
-#if TOMO_DEV
-            t.probe = g_probe;
-#endif
-            t.nut = nut_w;
-            t.bt = bt;
-            t.ngroups = ceil_div(nc, FP_A);
-            t.nzb = ceil_div(a.nz, 4);
-            const long blocks_w = 8L * (((long)t.nzb * t.nut * t.ngroups + 7) / 8);
-            if (blocks_w > 0x7fffffffL) return -1;
-#define FP_WIDE_LAUNCH(L8, RES)                                                                                        \
-    do {                                                                                                               \
-        auto launch = [&](auto kern) {                                                                                 \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      (int)smem_w);                                                                    \
-            kern<<<(unsigned)blocks_w, bt, smem_w, st>>>(t);                                                         \
-        };                                                                                                             \
-        if (passes_w == 1) launch(fp_tiled_kernel<L8, RES, 1, 4, true, 1024>);                                         \
-        else if (passes_w == 2 && kc_w == 4) launch(fp_tiled_kernel<L8, RES, 2, 8, true, 1024>);                       \
-        else if (passes_w == 2) launch(fp_tiled_kernel<L8, RES, 2, 4, true, 1024>);                                    \
-        else if (passes_w == 3 && kc_w == 2) launch(fp_tiled_kernel<L8, RES, 3, 6, false, 1024>);                      \
-        else if (passes_w == 3) launch(fp_tiled_kernel<L8, RES, 3, 3, false, 1024>);                                   \
-        else if (passes_w == 4) launch(fp_tiled_kernel<L8, RES, 4, 4, false, 1024>);                                   \
-        else launch(fp_tiled_kernel<L8, RES, 5, 5, false, 1024>);                                                      \
-    } while (0)
-            if (b) { if (l8) FP_WIDE_LAUNCH(true, true); else FP_WIDE_LAUNCH(false, true); }
-            else   { if (l8) FP_WIDE_LAUNCH(true, false); else FP_WIDE_LAUNCH(false, false); }
-#undef FP_WIDE_LAUNCH
-            if (hipGetLastError() != hipSuccess) return -1;
-            ctx->last_fp_path += label;
-            ctx->last_fp_path += "whole-row(" + std::to_string(bt) + " threads, " + std::to_string(passes_w) + " passes, " +
-                                 std::to_string(kc_w) + " rows/chunk) ";
-            return 1;
-        };
-        // ---- dense form (round 4): 256 detector pixels x 16 angles per workgroup.  When neighbouring angles of the slope order
-        // are a fraction of a degree apart (BASELINE configs[3]: 1500 angles, no subsets) a 16-angle group's window is hardly
-        // wider than an 8-angle group's, so every staged volume row serves twice the rays: 0.12 staged columns per sample
-        // against 0.18 for whole rows x 8 angles.  Three 256-thread workgroups per CU (12 waves, <= 168 registers).
-        constexpr int FP_A16 = 16;
-        auto dense16_cost = [&](int c, size_t off_c, int nc) -> double {
-            if (nc < 2 * FP_A16) return -1.0;
-            if (s.wbound16[c] < 0)
-                s.wbound16[c] = fp_window_bound(ctx->host_table.data() + s.table_offset, ctx->host_fp_order.data() + off_c, nc,
-                                                ctx->n, ctx->nu, 256, FP_A16);
-            if (s.wbound16[c] > 512) return -1.0;  // two column passes at most
-            const int kc = s.wbound16[c] <= 256 ? 4 : 2;
-            if ((size_t)2 * kc * s.wbound16[c] * 16 + (size_t)a.n * 8 > 64 * 1024) return -1.0;  // three workgroups per CU
-            const long wgs = (long)ceil_div(a.nz, 4) * ceil_div(a.nu, 256) * ceil_div(nc, FP_A16);
-            if (8L * ((wgs + 7) / 8) > 0x7fffffffL) return -1.0;
-            // a launch per sign class must still fill the chip several times over (768 resident workgroups): on BASELINE
-            // configs[1] (256^3, 360 angles) the form left half the CUs idle -- 542 instead of 702 iterations/s
-            if (wgs < 4 * 768 && g_variant_fp != 3) return -1.0;
-            return (double)ceil_div(a.nu, 256) * ceil_div(nc, FP_A16) * s.wbound16[c];
-        };
-        auto launch_dense16 = [&](int c, size_t off_c, int nc) -> int {
-            FpTiledArgs t;
-            t.src = (c >> 1) ? a.volT : a.vol;
-            t.tab = a.tab;
-            t.order = ctx->dev_fp_order + off_c;
-            t.mult = nullptr;
-            t.n_class = nc;
-            t.nz = a.nz; t.n = a.n; t.nu = a.nu; t.na = a.na; t.na_full = a.na_full;
-            t.out = out; t.b = b; t.w = w; t.fidelity = fidelity; t.gathered = gathered;
-            t.ring = ring; t.ring_scale = ring_scale; t.zquad = a.zquad; t.robust = a.robust; t.rdelta = a.rdelta;
-            t.wpitch = s.wbound16[c];
-#if TOMO_DEV
-            t.probe = g_probe;
-#endif
-            const int passes = ceil_div(t.wpitch, 256);   // 1 or 2
-            const int kc = passes == 1 ? 4 : 2;            // four float4 staging items per thread and chunk either way
-            const size_t smem = (size_t)2 * kc * t.wpitch * 16 + (size_t)a.n * 8;
-            t.nut = ceil_div(a.nu, 256);
-            t.bt = 256;
-            t.ngroups = ceil_div(nc, FP_A16);
-            t.nzb = ceil_div(a.nz, 4);
-            const long blocks = 8L * (((long)t.nzb * t.nut * t.ngroups + 7) / 8);  // (size limits checked in dense16_cost)
-#define FP_D16_LAUNCH(L8, RES)                                                                                         \
-    do {                                                                                                               \
-        if (passes == 1) fp_tiled_kernel<L8, RES, 1, 4, true, 256, FP_A16><<<(unsigned)blocks, 256, smem, st>>>(t);   \
-        else fp_tiled_kernel<L8, RES, 2, 4, true, 256, FP_A16><<<(unsigned)blocks, 256, smem, st>>>(t);                \
-    } while (0)
-            if (b) { if (l8) FP_D16_LAUNCH(true, true); else FP_D16_LAUNCH(false, true); }
-            else   { if (l8) FP_D16_LAUNCH(true, false); else FP_D16_LAUNCH(false, false); }
-#undef FP_D16_LAUNCH
-            if (hipGetLastError() != hipSuccess) return -1;
-            ctx->last_fp_path += "class" + std::to_string(c) + ":dense(256 pixels x 16 angles, " + std::to_string(passes) + " passes) ";
-            return 1;
-        };
-        {
-            size_t axis_off = s.table_offset;
-            const int nut = ceil_div(a.nu, 256);
-            for (int d = 0; d < 2 && (g_variant_fp == 0 || g_variant_fp == 3 || g_variant_fp == 4) && a.nu >= FP_WIDE_MIN_NU; ++d) {
-                const int nc0 = s.n_class[2 * d], nc1 = s.n_class[2 * d + 1], nc = nc0 + nc1;
-                const size_t off_d = axis_off;
-                axis_off += nc;
-                if (nc == 0) continue;
-                {
-                    // dense form for both sign classes of the axis when it stages clearly less than whole rows x 8 angles would
-                    // (variant 3, dev flavour: whenever it is applicable -- the A/B and parity tests of this form)
-                    const double c0 = nc0 ? dense16_cost(2 * d, off_d, nc0) : 0.0, c1 = nc1 ? dense16_cost(2 * d + 1, off_d + nc0, nc1) : 0.0;
-                    const int nut_w = ceil_div(a.nu, 1024);
-                    const int bt_w = std::min(1024, ceil_div(ceil_div(a.nu, nut_w), 64) * 64);
-                    bool take = c0 >= 0.0 && c1 >= 0.0;
-#ifdef TOMO_FP_NO_DENSE16   // A/B builds only (tools/run_ab.sh)
-                    take = false;
-#endif
-                    if (take && (g_variant_fp == 0 || g_variant_fp == 4)) {
-                        double rows = 0.0;
-                        if (a.nu <= 1024) {
-                            if (s.wbound_wide[2 * d] < 0)
-                                s.wbound_wide[2 * d] = fp_window_bound(ctx->host_table.data() + s.table_offset, ctx->host_fp_order.data() + off_d,
-                                                                       nc, ctx->n, ctx->nu, bt_w);
-                            rows = (double)nut_w * ceil_div(nc, FP_A) * s.wbound_wide[2 * d];
-                        } else {
-                            for (int h = 0; h < 2; ++h) {
-                                const int nch = h ? nc1 : nc0;
-                                if (nch == 0) continue;
-                                int &wc = s.wbound_wide[2 * d + h];
-                                if (wc < 0)
-                                    wc = fp_window_bound(ctx->host_table.data() + s.table_offset,
-                                                         ctx->host_fp_order.data() + off_d + (h ? nc0 : 0), nch, ctx->n, ctx->nu, bt_w);
-                                rows += (double)nut_w * ceil_div(nch, FP_A) * wc;
-                            }
-                        }
-                        take = (c0 + c1) <= FP_DENSE16_PAYS * rows;
-                    }
-                    if (take) {
-                        const int rc0 = nc0 ? launch_dense16(2 * d, off_d, nc0) : 1;
-                        const int rc1 = nc1 ? launch_dense16(2 * d + 1, off_d + nc0, nc1) : 1;
-                        if (rc0 < 0 || rc1 < 0) return tomo_fail(TOMO_E_INVALID, "forward-projection launch failed (or the problem is too large for one launch)");
-                        done[2 * d] = done[2 * d + 1] = true;
-                        continue;
-                    }
-                }
-                if (g_variant_fp == 3) continue;
-                const double ct0 = (double)nut * ceil_div(nc0, FP_A) * std::max(s.wbound[2 * d], 0);
-                const double ct1 = (double)nut * ceil_div(nc1, FP_A) * std::max(s.wbound[2 * d + 1], 0);
-                if (a.nu <= 1024) {
-                    // one 1024-pixel tile = the whole detector row: its window does not care about the sign of the
-                    // detector slope, so the two classes of an axis (adjacent in the order table) are merged --
-                    // 37 angles make 5 groups of 8 instead of 3 + 3
-                    const int rc = try_wide(d, off_d, nc, s.wbound_wide[2 * d], ct0 + ct1, d ? "x:" : "y:");
-                    if (rc < 0) return tomo_fail(TOMO_E_INVALID, "forward-projection launch failed (or the problem is too large for one launch)");
-                    if (rc > 0) done[2 * d] = done[2 * d + 1] = true;
-                } else {
-                    // several 1024-pixel tiles per row (2560-wide detectors, BASELINE configs[4]): a group that mixes the
-                    // two signs of the slope maps a tile to BOTH ends of the volume row (window = the whole row, 2564
-                    // columns for every tile); class by class a tile's window stays ~1400 columns
-                    if (nc0 > 0) {
-                        const int rc = try_wide(d, off_d, nc0, s.wbound_wide[2 * d], ct0, d ? "x+:" : "y+:");
-                        if (rc < 0) return tomo_fail(TOMO_E_INVALID, "forward-projection launch failed (or the problem is too large for one launch)");
-                        if (rc > 0) done[2 * d] = true;
-                    }
-                    if (nc1 > 0) {
-                        const int rc = try_wide(d, off_d + nc0, nc1, s.wbound_wide[2 * d + 1], ct1, d ? "x-:" : "y-:");
-                        if (rc < 0) return tomo_fail(TOMO_E_INVALID, "forward-projection launch failed (or the problem is too large for one launch)");
-                        if (rc > 0) done[2 * d + 1] = true;
-                    }
-                }
-            }
-        }
-        size_t order_off = s.table_offset;
-        for (int c = 0; c < 4; ++c) {  // one launch per stepping class (x-stepping classes read the transposed copy)
-            const int nc = s.n_class[c];
-            if (nc > 0 && !done[c]) {
-                FpTiledArgs t;
-                t.src = (c >> 1) ? a.volT : a.vol;
-                t.tab = a.tab;
-                t.order = ctx->dev_fp_order + order_off;
-                t.mult = nullptr;
-                t.n_class = nc;
-                t.nz = a.nz; t.n = a.n; t.nu = a.nu; t.na = a.na; t.na_full = a.na_full;
-                t.out = out; t.b = b; t.w = w; t.fidelity = fidelity; t.gathered = gathered;
-                t.ring = ring; t.ring_scale = ring_scale; t.zquad = a.zquad; t.robust = a.robust; t.rdelta = a.rdelta;
-                t.wpitch = s.wbound[c];
-    #if TOMO_DEV
-            t.probe = g_probe;
-#endif
-                const int passes = ceil_div(t.wpitch, 256);           // 1..5 in the pipelined kernel
-                // (items per thread, double buffer) per pass count -- keep in step with FP_TILED_LAUNCH below
-                const int fp_m = passes <= 2 ? 8 : (passes == 5 ? 10 : 12);
-                const bool fp_db = passes <= 2;
-                const int kc = fp_m / std::max(passes, 1);
-                const size_t smem = (size_t)(fp_db ? 2 : 1) * kc * t.wpitch * 16 + (size_t)a.n * 8;
-                t.nut = ceil_div(a.nu, 256);
-                t.bt = 256;
-                t.ngroups = ceil_div(nc, FP_A);
-                t.nzb = ceil_div(a.nz, 4);
-                const long blocks = 8L * (((long)t.nzb * t.nut * t.ngroups + 7) / 8);
-                TOMO_REQUIRE(blocks <= 0x7fffffffL, "problem too large for one FP launch");
-                // Windows of up to 1280 columns run the register-prefetch pipeline (double-buffered up to 512 columns,
-                // single-buffered beyond); wider ones (detectors wider than 1024 whose whole-row form does not fit in
-                // LDS) and variant 2 run the synchronous form: stage, barrier, sample, barrier, with a small LDS
-                // footprint so that several workgroups per CU hide the staging latency.
-                if (g_variant_fp == 2 || t.wpitch > FP_MAX_WPITCH) {
-                    const int kcs = std::max(1, std::min(8, 40000 / (t.wpitch * 16)));
-                    const size_t sm = (size_t)kcs * t.wpitch * 16;
-                    TOMO_REQUIRE(sm <= 64 * 1024, "forward-projection window does not fit in LDS");
-#define FP_SYNC_LAUNCH(L8, RES) fp_tiled_sync_kernel<L8, RES, 256, FP_A><<<(unsigned)blocks, 256, sm, st>>>(t, kcs)
-                    if (b) { if (l8) FP_SYNC_LAUNCH(true, true); else FP_SYNC_LAUNCH(false, true); }
-                    else   { if (l8) FP_SYNC_LAUNCH(true, false); else FP_SYNC_LAUNCH(false, false); }
-#undef FP_SYNC_LAUNCH
-                    TOMO_LAUNCH_CHECK();
-                    ctx->last_fp_path += "class" + std::to_string(c) + ":tiled-sync(window " + std::to_string(t.wpitch) + ") ";
-                    order_off += nc;
-                    continue;
-                }
-#define FP_TILED_LAUNCH(L8, RES)                                                                          \
-    do {                                                                                                  \
-        if (passes == 1) fp_tiled_kernel<L8, RES, 1, 8, true, 256><<<(unsigned)blocks, 256, smem, st>>>(t);        \
-        else if (passes == 2) fp_tiled_kernel<L8, RES, 2, 8, true, 256><<<(unsigned)blocks, 256, smem, st>>>(t);   \
-        else if (passes == 3) fp_tiled_kernel<L8, RES, 3, 12, false, 256><<<(unsigned)blocks, 256, smem, st>>>(t); \
-        else if (passes == 4) fp_tiled_kernel<L8, RES, 4, 12, false, 256><<<(unsigned)blocks, 256, smem, st>>>(t); \
-        else fp_tiled_kernel<L8, RES, 5, 10, false, 256><<<(unsigned)blocks, 256, smem, st>>>(t);                  \
-    } while (0)
-                if (b) { if (l8) FP_TILED_LAUNCH(true, true); else FP_TILED_LAUNCH(false, true); }
-                else   { if (l8) FP_TILED_LAUNCH(true, false); else FP_TILED_LAUNCH(false, false); }
-#undef FP_TILED_LAUNCH
-                TOMO_LAUNCH_CHECK();
-                ctx->last_fp_path += "class" + std::to_string(c) + ":tiled-pipelined(256 threads, " + std::to_string(passes) +
-                                     " passes) ";
-            }
-            order_off += nc;
-        }
+        TOMO_LAUNCH_CHECK();
         return TOMO_OK;
     }
-    ctx->last_fp_path = "march(no LDS)";
-    if (g_variant_fp != 1) tomo_warn_once("fp_march", "forward projection: a staged row window exceeds 64 KiB of LDS, "
-                                          "falling back to the un-tiled march kernel (about 4x slower)");
-    if (b) {
-        if (l8) fp_march_kernel<true, true><<<grid, 256, 0, st>>>(a);
-        else fp_march_kernel<false, true><<<grid, 256, 0, st>>>(a);
-    } else {
-        if (l8) fp_march_kernel<true, false><<<grid, 256, 0, st>>>(a);
-        else fp_march_kernel<false, false><<<grid, 256, 0, st>>>(a);
+    FpTiledArgs t;
+    t.tab = a.tab;
+    t.nz = a.nz; t.n = a.n; t.nu = a.nu; t.na = a.na; t.na_full = a.na_full;
+    t.out = out; t.b = b; t.w = w; t.fidelity = fidelity; t.gathered = gathered;
+    t.ring = ring; t.ring_scale = ring_scale; t.zquad = a.zquad; t.robust = a.robust; t.rdelta = a.rdelta;
+#if TOMO_DEV
+    t.probe = g_probe;
+#endif
+    t.nzb = ceil_div(a.nz, 4);
+    for (int i = 0; i < plan.count; ++i) {
+        const FpLaunch &l = plan.l[i];
+        t.src = (l.cls >> 1) ? a.volT : a.vol;
+        t.order = ctx->dev_fp_order + l.order_off;
+        t.mult = l.mult ? ctx->dev_fp_mult + l.order_off : nullptr;
+        t.n_class = l.n_angles; t.wpitch = l.wpitch; t.nut = l.nut; t.bt = l.threads; t.ngroups = l.ngroups;
+        if (b) { if (l8) fp_launch<true, true>(l, t, st); else fp_launch<false, true>(l, t, st); }
+        else   { if (l8) fp_launch<true, false>(l, t, st); else fp_launch<false, false>(l, t, st); }
+        TOMO_LAUNCH_CHECK();
+        ctx->last_fp_path += fp_path_text(l);
     }
-    TOMO_LAUNCH_CHECK();
     return TOMO_OK;
 }
 
@@ -1040,6 +1083,39 @@ int bp_prepare(tomo_ctx *ctx, int subset, const float *sino, BpArgs &a)
 }
 
 }  // namespace
+
+// The forward projector's window bounds of every subset and the whole-row form's lane-multiplier table (tomo_ctx_create):
+// both depend on the geometry only, so fp_plan reads them without a HIP call.
+int fp_tables(tomo_ctx *ctx)
+{
+    const int n = ctx->n, nu = ctx->nu, bt = fp_wide_bt(nu);
+    for (tomo_subset &s : ctx->subsets) {
+        const tomo_angle_t *tab = ctx->host_table.data() + s.table_offset;
+        const int *order = ctx->host_fp_order.data() + s.table_offset;
+        for (int d = 0, off = 0; d < 2; ++d) {
+            const int nc0 = s.n_class[2 * d], nc1 = s.n_class[2 * d + 1];
+            for (int h = 0; h < 2; ++h) {
+                const int c = 2 * d + h, nc = h ? nc1 : nc0, o = off + (h ? nc0 : 0);
+                if (nc == 0) continue;
+                s.wbound[c] = fp_window_bound(tab, order + o, nc, n, nu);
+                s.wbound16[c] = fp_window_bound(tab, order + o, nc, n, nu, 256, FP_A16);
+                if (nu > 1024) s.wbound_wide[c] = fp_window_bound(tab, order + o, nc, n, nu, bt);
+            }
+            if (nu <= 1024 && nc0 + nc1 > 0) s.wbound_wide[2 * d] = fp_window_bound(tab, order + off, nc0 + nc1, n, nu, bt);
+            off += nc0 + nc1;
+        }
+    }
+    if (bt < FP_MULT_MIN_BT) return TOMO_OK;
+    std::vector<int> mult(ctx->host_fp_order.size(), 1);
+    for (const tomo_subset &s : ctx->subsets)
+        for (int i = 0; i < s.size; ++i) {
+            const tomo_angle_t &rec = ctx->host_table[s.table_offset + ctx->host_fp_order[s.table_offset + i]];
+            mult[s.table_offset + i] = fp_lane_mult(std::fabs((double)rec.inv), bt);
+        }
+    TOMO_HIP(hipMalloc((void **)&ctx->dev_fp_mult, std::max<size_t>(mult.size(), 1) * sizeof(int)));
+    TOMO_HIP(hipMemcpy(ctx->dev_fp_mult, mult.data(), mult.size() * sizeof(int), hipMemcpyHostToDevice));
+    return TOMO_OK;
+}
 
 void tomo_bp_relay_reset(int device)
 {

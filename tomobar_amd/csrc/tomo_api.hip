@@ -185,6 +185,8 @@ extern "C" int tomo_ctx_create(int device, int nz, int n, int nu, int na, const 
         delete ctx;
         return tomo_fail(TOMO_E_RUNTIME, "angle table upload failed: %s", hipGetErrorString(e));
     }
+    rc = fp_tables(ctx);
+    if (rc != TOMO_OK) { tomo_ctx_destroy(ctx); return rc; }
     *out = ctx;
     return TOMO_OK;
 }

@@ -39,14 +39,15 @@ struct tomo_subset {
     int size = 0;             // number of angles
     size_t table_offset = 0;  // element offset into the device angle table (and into the FP order table)
     int n_dirx = 0;           // how many angles step along x (FP)
-    // FP stepping classes: the order table lists the subset-local indices of the y-stepping angles (class 0)
-    // followed by the x-stepping ones (class 1), each sorted by angle; wbound = cached LDS window bound (-1 = unset)
+    // FP stepping classes: the order table lists the subset-local indices of the y-stepping angles (classes 0, 1)
+    // followed by the x-stepping ones (classes 2, 3), each sorted by slope;
     // class = 2*dirx + (inv < 0): angles whose detector axis runs the opposite way along the interpolation axis
     // (e.g. theta near 0 and near pi) sample opposite ends of a volume row and must not share a staged window
     int n_class[4] = {0, 0, 0, 0};
-    int wbound[4] = {-1, -1, -1, -1};
-    int wbound_wide[4] = {-1, -1, -1, -1};  // same for 1024-pixel detector tiles
-    int wbound16[4] = {-1, -1, -1, -1};     // same for 256-pixel tiles x 16 angles (dense angle sets)
+    // FP LDS window bounds (fp_tables, at context creation; 0 for an empty class):
+    int wbound[4] = {0, 0, 0, 0};       // per class, 256-pixel tiles x 8 angles
+    int wbound_wide[4] = {0, 0, 0, 0};  // whole-row tiles x 8 angles: per axis in [2 * axis] up to 1024 pixels, else per class
+    int wbound16[4] = {0, 0, 0, 0};     // per class, 256-pixel tiles x 16 angles (dense angle sets)
 };
 
 struct tomo_ctx {
@@ -60,8 +61,7 @@ struct tomo_ctx {
     tomo_angle_t *dev_table = nullptr;
     std::vector<int> host_fp_order;           // same indexing as host_table
     int *dev_fp_order = nullptr;
-    int *dev_fp_mult = nullptr;               // whole-row FP form: lane -> pixel multiplier per entry of the order table (built on first use)
-    int fp_mult_bt = 0;                       // ... for this tile width
+    int *dev_fp_mult = nullptr;               // whole-row FP form: lane -> pixel multiplier per entry of the order table (null below 768-pixel tiles)
     void *scratch = nullptr;                  // grow-only (FP: in-plane transposed volume)
     size_t scratch_bytes = 0;
     const float *volT_of = nullptr;           // volume whose transposed copy `scratch` holds (tomo_momentum_transposed)
@@ -99,6 +99,7 @@ static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream
 enum { ARENA_MAIN = 0, ARENA_REDUCE = 1, ARENA_TV = 2 /* placed: the TV operators' work arrays */, ARENA_BPQ = 3 /* a planar sinogram re-laid quad-interleaved for the back projector */, ARENA_CALLER0 = 16 /* .. +7: tomo_placed_scratch (placed) */ };
 int tomo_arena_get(int device, hipStream_t stream, int slot, size_t bytes, void **out, bool place = false);  // place: see tomo_api.hip
 int tomo_arena_release_slot(int device, int slot);  // frees the arenas of one slot on a device (all streams)
+int fp_tables(tomo_ctx *ctx);                 // FP window bounds and lane multipliers of every subset (proj_kernels.hip)
 void tomo_bp_relay_reset(int device);         // forget that the back projector's relay scratch was refused (proj_kernels.hip)
 void tomo_fourier_cache_release(int device);  // cached hipFFT plans of fourier_inv.hip
 void tomo_fbp_cache_release(int device);      // cached hipFFT plans / filter tables of fbp_filter.hip

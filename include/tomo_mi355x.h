@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* raised whenever an entry point is added or a signature changes (tomobar_amd/_lib.py checks it at load) */
-#define TOMO_ABI_VERSION 6
+#define TOMO_ABI_VERSION 7
 
 enum {
     TOMO_OK = 0,
@@ -234,6 +234,14 @@ int tomo_fill(float *x_dev, float value, size_t count, void *stream);
 int tomo_norm2(const float *x_dev, size_t count, double *out_host, void *stream);
 int tomo_dot(const float *x_dev, const float *y_dev, size_t count, double *out_host, void *stream);
 int tomo_max(const float *x_dev, size_t count, float *out_host, void *stream);
+/* Relative change between two iterates, the quantity the tolerance keys are compared with (below, "early stopping"):
+ * out_host[0] = sum (x - ref)^2, out_host[1] = sum x^2, both accumulated in double from the float32 values, in ONE streaming
+ * pass that also writes keep[i] = x[i] when keep_dev is given (NULL: no snapshot; keep_dev == ref_dev: "compare with the
+ * snapshot and refresh it", 12 B per voxel and one launch instead of a reduction plus a copy).  Deterministic: fixed grid,
+ * per-block double partials finished on the host in block order, no atomics -- the same input gives the same bits on every
+ * call.  16-byte accesses when the arrays reach a 16-byte boundary after the same number of elements (scalar head / tail),
+ * dword accesses otherwise.  count = 0 -> (0, 0).  Synchronises the stream (the pair is returned to the host). */
+int tomo_rel_change(const float *x_dev, const float *ref_dev, float *keep_dev, size_t count, double out_host[2], void *stream);
 int tomo_pwls_weights(const float *b_dev, float *w_dev, size_t count, void *stream);
 /* z-slab form of the same: the caller max-all-reduces tomo_pwls_max over the slabs and passes the result on */
 int tomo_pwls_max(const float *b_dev, size_t count, float *out_host, void *stream);
@@ -272,7 +280,26 @@ int tomo_pdtv(int device, const float *in_dev, float *out_dev, int dx, int dy, i
               int half, void *stream);
 int tomo_roftv(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
                float lambda, float tau, int iters, int half, void *stream);
-/* scratch bytes the TV drivers hold for a given problem (informational) and arena release */
+/* Early stopping (the `tolerance` keys of the dictionaries; no implementation in this reference version -- the rule is this
+ * project's, formula-level parity, unpinned).  For iterates v_0 = input, v_n = what the operator returns after n iterations:
+ *     d_n = sqrt( sum (v_n - v_{n-6})^2 / sum v_n^2 )     (tomo_rel_change; 0 when the numerator is 0, +inf when only the
+ *                                                            denominator is)
+ * evaluated after iteration n when n is a multiple of 6 and at least 3 of the requested iterations remain; the loop stops
+ * after iterate n when tol > 0 and d_n < tol, and out_dev then holds exactly what iters = n without a tolerance returns.
+ * tol is a double so that the threshold compared with is the one the user wrote; negative / non-finite: TOMO_E_INVALID.
+ * *iters_done receives n (iters if the rule was never met), *last_rel_change the last d evaluated (NaN if none was); either
+ * may be NULL.  tol = 0 is tomo_pdtv / tomo_roftv launch for launch (one shared loop).  With tol > 0 every check is one
+ * tomo_rel_change pass and one stream synchronisation, and the iterate of six iterations ago lives in a block of its own
+ * (one float volume, plain allocation per (device, stream), freed by tomo_release_scratch) BESIDE the arena that
+ * tomo_pdtv_scratch_bytes / tomo_roftv_scratch_bytes describe, whose size and placement do not change. */
+int tomo_pdtv_tol(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+                  float sigma, float tau, float lt, float theta, int iters, int methodTV, int nonneg,
+                  int half, double tol, int *iters_done, double *last_rel_change, void *stream);
+int tomo_roftv_tol(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+                   float lambda, float tau, int iters, int half, double tol, int *iters_done,
+                   double *last_rel_change, void *stream);
+/* scratch bytes the TV drivers hold for a given problem (informational; a tolerance adds one float volume, see above) and
+ * arena release */
 size_t tomo_pdtv_scratch_bytes(int dx, int dy, int dz, int nd, int half);
 size_t tomo_roftv_scratch_bytes(int dx, int dy, int dz, int nd);
 int tomo_release_scratch(int device);

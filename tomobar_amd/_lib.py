@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtomo_mi355x.so")
 
 OK, E_INVALID, E_RUNTIME, E_NOMEM, E_NODEVICE = 0, 1, 2, 3, 4
-ABI_VERSION = 6  # TOMO_ABI_VERSION of include/tomo_mi355x.h (tests/test_host_logic.py keeps the two in step)
+ABI_VERSION = 7  # TOMO_ABI_VERSION of include/tomo_mi355x.h (tests/test_host_logic.py keeps the two in step)
 FLAG_LERP8 = 1
 FID = {"LS": 0, "PWLS": 1, "KL": 2, "RATIO": 3}
 ROBUST = {None: 0, "huber": 1, "studentst": 2}   # TOMO_ROBUST_* of include/tomo_mi355x.h
@@ -76,6 +76,7 @@ SIGNATURES = {
     "tomo_norm2": (_i, [_vp, _sz, C.POINTER(_d), _vp]),
     "tomo_dot": (_i, [_vp, _vp, _sz, C.POINTER(_d), _vp]),
     "tomo_max": (_i, [_vp, _sz, C.POINTER(_f), _vp]),
+    "tomo_rel_change": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_d), _vp]),
     "tomo_pwls_weights": (_i, [_vp, _vp, _sz, _vp]),
     "tomo_pwls_max": (_i, [_vp, _sz, C.POINTER(_f), _vp]),
     "tomo_pwls_weights_scaled": (_i, [_vp, _vp, _sz, _f, _vp]),
@@ -86,6 +87,8 @@ SIGNATURES = {
     "tomo_permute3": (_i, [_vp, _vp, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, _vp]),
     "tomo_pdtv": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _i, _i, _i, _i, _vp]),
     "tomo_roftv": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp]),
+    "tomo_pdtv_tol": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _i, _i, _i, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
+    "tomo_roftv_tol": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
     "tomo_pdtv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "tomo_roftv_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_release_scratch": (_i, [_i]),

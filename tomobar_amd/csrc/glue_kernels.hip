@@ -173,6 +173,90 @@ int reduce_host(const float *x, const float *y, size_t n, double *out, void *str
     return TOMO_OK;
 }
 
+// ---- relative change between two iterates (the stopping rule of the tolerance keys, docs/kernels/convergence.md):
+//      num = sum (x - ref)^2, den = sum x^2 in one streaming pass that can also refresh the snapshot (keep[i] = x[i]; keep may
+//      alias ref: every element is read before the same thread overwrites it).  Every term is formed in double from the float32
+//      values (the square of x exactly), accumulated per thread in a fixed order, reduced over the wave by __shfl_down and over
+//      the block through LDS; one (num, den) pair per block, finished on the host in block order.  Fixed grid, no atomics:
+//      the same input gives the same bits on every call.
+typedef float rc_v4 __attribute__((ext_vector_type(4)));
+
+__device__ inline void rel_change_term(float xv, float rv, double &num, double &den)
+{
+    const double d = (double)xv - (double)rv;
+    num += d * d;
+    den += (double)xv * (double)xv;
+}
+
+__device__ inline void rel_change_finish(double num, double den, double *partial)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        num += __shfl_down(num, off, 64);
+        den += __shfl_down(den, off, 64);
+    }
+    __shared__ double wave_part[2][EW_BLOCK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { wave_part[0][wave] = num; wave_part[1][wave] = den; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double rn = wave_part[0][0], rd = wave_part[1][0];
+        for (int w = 1; w < EW_BLOCK / 64; ++w) { rn += wave_part[0][w]; rd += wave_part[1][w]; }
+        partial[2 * (size_t)blockIdx.x] = rn;
+        partial[2 * (size_t)blockIdx.x + 1] = rd;
+    }
+}
+
+// x + head, ref + head (and keep + head) are 16-byte aligned: `head` (< 4) leading and (n - head) % 4 trailing elements are
+// taken one by one by the first threads of block 0.  NT: non-temporal loads / stores (dev flavour, probe bit 64: A/B only)
+template <bool KEEP, bool NT>
+__global__ __launch_bounds__(EW_BLOCK) void rel_change_vec4(const float *x, const float *ref, float *keep, size_t n,
+                                                            unsigned head, double *partial)
+{
+    double num = 0.0, den = 0.0;
+    const size_t n4 = (n - head) >> 2;
+    const rc_v4 *x4 = reinterpret_cast<const rc_v4 *>(x + head);
+    const rc_v4 *r4 = reinterpret_cast<const rc_v4 *>(ref + head);
+    rc_v4 *k4 = reinterpret_cast<rc_v4 *>(keep + head);
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const rc_v4 a = NT ? __builtin_nontemporal_load(x4 + i) : x4[i];
+        const rc_v4 b = NT ? __builtin_nontemporal_load(r4 + i) : r4[i];
+        rel_change_term(a.x, b.x, num, den);
+        rel_change_term(a.y, b.y, num, den);
+        rel_change_term(a.z, b.z, num, den);
+        rel_change_term(a.w, b.w, num, den);
+        if (KEEP) {
+            if (NT) __builtin_nontemporal_store(a, k4 + i);
+            else k4[i] = a;
+        }
+    }
+    if (blockIdx.x == 0) {
+        const size_t tail0 = head + (n4 << 2);
+        const size_t i = threadIdx.x < head ? threadIdx.x : tail0 + (threadIdx.x - head);
+        if (i < n) {
+            const float xv = x[i];
+            rel_change_term(xv, ref[i], num, den);
+            if (KEEP) keep[i] = xv;
+        }
+    }
+    rel_change_finish(num, den, partial);
+}
+
+// pointers that are not aligned alike: dword accesses
+template <bool KEEP>
+__global__ __launch_bounds__(EW_BLOCK) void rel_change_scalar(const float *x, const float *ref, float *keep, size_t n,
+                                                              double *partial)
+{
+    double num = 0.0, den = 0.0;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float xv = x[i];
+        rel_change_term(xv, ref[i], num, den);
+        if (KEEP) keep[i] = xv;
+    }
+    rel_change_finish(num, den, partial);
+}
+
 // ---- ring-artefact data terms: reductions over the angles of one (ordered-subset) residual, one thread per detector
 //      pixel (z, u), angles summed in ascending order (deterministic; the oracle sums in the same order)
 // Group-Huber: vec = sum_a res[z,a,u];  r = r_x - l_inv * vec;  then the PWLS weights are applied to res in place
@@ -432,6 +516,52 @@ extern "C" int tomo_dot(const float *x, const float *y, size_t count, double *ou
 {
     return reduce_host<RED_DOT>(x, y, count, out_host, stream);
 }
+extern "C" int tomo_rel_change(const float *x, const float *ref, float *keep, size_t count, double out_host[2], void *stream)
+{
+    TOMO_REQUIRE(out_host != nullptr, "out is NULL");
+    out_host[0] = out_host[1] = 0.0;
+    if (count == 0) return TOMO_OK;
+    TOMO_REQUIRE(x != nullptr && ref != nullptr, "NULL data pointer");
+    TOMO_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(ref) | reinterpret_cast<uintptr_t>(keep)) & 3u) == 0,
+                 "float arrays must be 4-byte aligned");
+    int dev = 0;
+    TOMO_HIP(hipGetDevice(&dev));
+    hipStream_t st = as_stream(stream);
+    void *buf = nullptr;
+    int rc = tomo_arena_get(dev, st, ARENA_REDUCE, (size_t)2 * EW_MAX_GRID * sizeof(double), &buf);
+    if (rc != TOMO_OK) return rc;
+    double *partial = (double *)buf;
+    // 16-byte accesses when the arrays reach a 16-byte boundary after the same number of elements
+    const uintptr_t xa = reinterpret_cast<uintptr_t>(x) & 15u;
+    const bool vec = xa == (reinterpret_cast<uintptr_t>(ref) & 15u) && (keep == nullptr || xa == (reinterpret_cast<uintptr_t>(keep) & 15u));
+    int grid;
+    if (vec) {
+        const unsigned head = (unsigned)std::min<size_t>(((16 - xa) & 15u) >> 2, count);
+        grid = ew_grid((count - head) >> 2);
+#if TOMO_DEV
+        if (g_probe & 64) {
+            if (keep) rel_change_vec4<true, true><<<grid, EW_BLOCK, 0, st>>>(x, ref, keep, count, head, partial);
+            else rel_change_vec4<false, true><<<grid, EW_BLOCK, 0, st>>>(x, ref, keep, count, head, partial);
+        } else
+#endif
+        if (keep) rel_change_vec4<true, false><<<grid, EW_BLOCK, 0, st>>>(x, ref, keep, count, head, partial);
+        else rel_change_vec4<false, false><<<grid, EW_BLOCK, 0, st>>>(x, ref, keep, count, head, partial);
+    } else {
+        grid = ew_grid(count);
+        if (keep) rel_change_scalar<true><<<grid, EW_BLOCK, 0, st>>>(x, ref, keep, count, partial);
+        else rel_change_scalar<false><<<grid, EW_BLOCK, 0, st>>>(x, ref, keep, count, partial);
+    }
+    TOMO_LAUNCH_CHECK();
+    std::vector<double> host(2 * (size_t)grid);
+    TOMO_HIP(hipMemcpyAsync(host.data(), partial, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    TOMO_HIP(hipStreamSynchronize(st));
+    double num = 0.0, den = 0.0;
+    for (int i = 0; i < grid; ++i) { num += host[2 * i]; den += host[2 * i + 1]; }
+    out_host[0] = num;
+    out_host[1] = den;
+    return TOMO_OK;
+}
+
 extern "C" int tomo_max(const float *x, size_t count, float *out_host, void *stream)
 {
     double m = 0.0;

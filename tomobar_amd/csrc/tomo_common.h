@@ -96,7 +96,7 @@ struct tomo_device_guard {
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // grow-only scratch arena per (device, stream, slot) (tomo_release_scratch frees a device's arenas)
-enum { ARENA_MAIN = 0, ARENA_REDUCE = 1, ARENA_TV = 2 /* placed: the TV operators' work arrays */, ARENA_BPQ = 3 /* a planar sinogram re-laid quad-interleaved for the back projector */, ARENA_CALLER0 = 16 /* .. +7: tomo_placed_scratch (placed) */ };
+enum { ARENA_MAIN = 0, ARENA_REDUCE = 1, ARENA_TV = 2 /* placed: the TV operators' work arrays */, ARENA_BPQ = 3 /* a planar sinogram re-laid quad-interleaved for the back projector */, ARENA_TVSNAP = 4 /* the earlier iterate the TV operators compare with when a tolerance is set (plain allocation) */, ARENA_CALLER0 = 16 /* .. +7: tomo_placed_scratch (placed) */ };
 int tomo_arena_get(int device, hipStream_t stream, int slot, size_t bytes, void **out, bool place = false);  // place: see tomo_api.hip
 int tomo_arena_release_slot(int device, int slot);  // frees the arenas of one slot on a device (all streams)
 int fp_tables(tomo_ctx *ctx);                 // FP window bounds and lane multipliers of every subset (proj_kernels.hip)

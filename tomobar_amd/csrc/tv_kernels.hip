@@ -23,6 +23,7 @@
 // +10 % per launch.  docs/kernels/pd_tv.md has the measurements behind that choice.
 #include "tomo_common.h"
 #include <algorithm>
+#include <cmath>
 #include <utility>
 
 namespace {
@@ -752,9 +753,47 @@ extern "C" int tomo_pdtv_iters_per_launch(int half)
     return pd_iters_per_launch(g_variant_pdtv);
 }
 
-extern "C" int tomo_pdtv(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
-                         float sigma, float tau, float lt, float theta, int iters, int methodTV, int nonneg,
-                         int half, void *stream)
+// ---- early stopping (tomo_pdtv_tol / tomo_roftv_tol; the rule is stated in include/tomo_mi355x.h): the iterate is compared
+//      with the one TOL_INTERVAL iterations earlier, and only where at least TOL_MIN_SAVED of the requested iterations remain
+constexpr int TOL_INTERVAL = 6, TOL_MIN_SAVED = 3;
+
+struct TolState {
+    double tol = 0.0;
+    float *snap = nullptr;   // v_{n - TOL_INTERVAL}: a block of its own, the TV arena keeps its size and placement
+    int done = 0;
+    double last = NAN;
+};
+
+static bool tol_valid(double tol) { return tol >= 0.0 && std::isfinite(tol); }
+
+// the snapshot block, taken before the first launch when a check can occur at all
+static int tol_begin(TolState &t, int device, hipStream_t st, size_t nvox, int iters)
+{
+    if (!(t.tol > 0.0) || iters < TOL_INTERVAL + TOL_MIN_SAVED) return TOMO_OK;
+    void *p = nullptr;
+    int rc = tomo_arena_get(device, st, ARENA_TVSNAP, nvox * sizeof(float), &p);
+    t.snap = (float *)p;
+    return rc;
+}
+
+// after iterate n (held in `cur`): *stop = the rule is met.  The first check reads the caller's input as the reference and
+// only writes the snapshot; later ones compare with the snapshot and refresh it in the same pass.
+static int tol_check(TolState &t, int n, int iters, const float *cur, const float *in_dev, size_t nvox, hipStream_t st, bool *stop)
+{
+    *stop = false;
+    t.done = n;
+    if (t.snap == nullptr || n % TOL_INTERVAL != 0 || iters - n < TOL_MIN_SAVED) return TOMO_OK;
+    double s[2];
+    int rc = tomo_rel_change(cur, n == TOL_INTERVAL ? in_dev : t.snap, t.snap, nvox, s, st);
+    if (rc != TOMO_OK) return rc;
+    t.last = s[0] == 0.0 ? 0.0 : (s[1] == 0.0 ? INFINITY : sqrt(s[0] / s[1]));
+    *stop = t.last < t.tol;
+    return TOMO_OK;
+}
+
+static int pdtv_run(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+                    float sigma, float tau, float lt, float theta, int iters, int methodTV, int nonneg,
+                    int half, TolState &ts, void *stream)
 {
     TOMO_REQUIRE(device >= 0, "The gpu_device must be a positive integer or zero");
     TOMO_REQUIRE(nd == 2 || nd == 3, "2D or 3D arrays must be provided only");
@@ -771,6 +810,8 @@ extern "C" int tomo_pdtv(int device, const float *in_dev, float *out_dev, int dx
     }
     void *base = nullptr;
     int rc = tomo_arena_get(device, st, ARENA_TV, tomo_pdtv_scratch_bytes(dx, dy, dz, nd, half), &base, true);
+    if (rc != TOMO_OK) return rc;
+    rc = tol_begin(ts, device, st, nvox, iters);
     if (rc != TOMO_OK) return rc;
     const size_t ub = align_up(nvox * sizeof(float), 256);
     const size_t pb = align_up(nvox * (half ? 2 : 4), 256);
@@ -831,10 +872,39 @@ extern "C" int tomo_pdtv(int device, const float *in_dev, float *out_dev, int dx
         if (rc != TOMO_OK) return rc;
         cset = ob;
         it += step;
+        // (every check point is a launch boundary of step_of: a multiple of 6 with at least 3 iterations left)
+        bool stop = false;
+        rc = tol_check(ts, it, iters, U[cset], in_dev, nvox, st, &stop);
+        if (rc != TOMO_OK) return rc;
+        if (stop) {
+            TOMO_HIP(hipMemcpyAsync(out_dev, U[cset], nvox * sizeof(float), hipMemcpyDeviceToDevice, st));
+            return TOMO_OK;
+        }
     }
     if (out_dev == in_dev)
         TOMO_HIP(hipMemcpyAsync(out_dev, U[cset], nvox * sizeof(float), hipMemcpyDeviceToDevice, st));
     return TOMO_OK;
+}
+
+extern "C" int tomo_pdtv(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+                         float sigma, float tau, float lt, float theta, int iters, int methodTV, int nonneg,
+                         int half, void *stream)
+{
+    TolState off;
+    return pdtv_run(device, in_dev, out_dev, dx, dy, dz, nd, sigma, tau, lt, theta, iters, methodTV, nonneg, half, off, stream);
+}
+
+extern "C" int tomo_pdtv_tol(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+                             float sigma, float tau, float lt, float theta, int iters, int methodTV, int nonneg,
+                             int half, double tol, int *iters_done, double *last_rel_change, void *stream)
+{
+    TOMO_REQUIRE(tol_valid(tol), "the tolerance must be a finite number >= 0");
+    TolState ts;
+    ts.tol = tol;
+    const int rc = pdtv_run(device, in_dev, out_dev, dx, dy, dz, nd, sigma, tau, lt, theta, iters, methodTV, nonneg, half, ts, stream);
+    if (rc == TOMO_OK && iters_done) *iters_done = ts.done;
+    if (rc == TOMO_OK && last_rel_change) *last_rel_change = ts.last;
+    return rc;
 }
 
 extern "C" int tomo_pdtv_iter_slab(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
@@ -909,8 +979,8 @@ extern "C" int tomo_pdtv_multi_slab_range(int device, const float *in_dev, const
     return half ? pd_multi_launch<__half>(a, k, methodTV, nonneg, v, st) : pd_multi_launch<float>(a, k, methodTV, nonneg, v, st);
 }
 
-extern "C" int tomo_roftv(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
-                          float lambda, float tau, int iters, int half, void *stream)
+static int roftv_run(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+                     float lambda, float tau, int iters, int half, TolState &ts, void *stream)
 {
     TOMO_REQUIRE(device >= 0, "The gpu_device must be a positive integer or zero");
     TOMO_REQUIRE(nd == 2 || nd == 3, "2D or 3D arrays must be provided only");
@@ -929,6 +999,8 @@ extern "C" int tomo_roftv(int device, const float *in_dev, float *out_dev, int d
     void *base = nullptr;
     int rc = tomo_arena_get(device, st, ARENA_TV, tomo_roftv_scratch_bytes(dx, dy, dz, nd), &base, true);
     if (rc != TOMO_OK) return rc;
+    rc = tol_begin(ts, device, st, nvox, iters);
+    if (rc != TOMO_OK) return rc;
     const size_t ub = align_up(nvox * sizeof(float), 256);
     float *U[2] = {(float *)base, (float *)((char *)base + ub)};
     tomo_prof_scope prof(PROF_ROFTV, st, iters);
@@ -942,10 +1014,37 @@ extern "C" int tomo_roftv(int device, const float *in_dev, float *out_dev, int d
         a.lambda = lambda; a.tau = tau;
         rc = rof_iter(a, nd, half, st);
         if (rc != TOMO_OK) return rc;
+        bool stop = false;
+        rc = tol_check(ts, it + 1, iters, U[(it + 1) & 1], in_dev, nvox, st, &stop);
+        if (rc != TOMO_OK) return rc;
+        if (stop) {
+            TOMO_HIP(hipMemcpyAsync(out_dev, U[(it + 1) & 1], nvox * sizeof(float), hipMemcpyDeviceToDevice, st));
+            return TOMO_OK;
+        }
     }
     if (out_dev == in_dev)
         TOMO_HIP(hipMemcpyAsync(out_dev, U[iters & 1], nvox * sizeof(float), hipMemcpyDeviceToDevice, st));
     return TOMO_OK;
+}
+
+extern "C" int tomo_roftv(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+                          float lambda, float tau, int iters, int half, void *stream)
+{
+    TolState off;
+    return roftv_run(device, in_dev, out_dev, dx, dy, dz, nd, lambda, tau, iters, half, off, stream);
+}
+
+extern "C" int tomo_roftv_tol(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+                              float lambda, float tau, int iters, int half, double tol, int *iters_done,
+                              double *last_rel_change, void *stream)
+{
+    TOMO_REQUIRE(tol_valid(tol), "the tolerance must be a finite number >= 0");
+    TolState ts;
+    ts.tol = tol;
+    const int rc = roftv_run(device, in_dev, out_dev, dx, dy, dz, nd, lambda, tau, iters, half, ts, stream);
+    if (rc == TOMO_OK && iters_done) *iters_done = ts.done;
+    if (rc == TOMO_OK && last_rel_change) *last_rel_change = ts.last;
+    return rc;
 }
 
 extern "C" int tomo_roftv_iter_slab(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,

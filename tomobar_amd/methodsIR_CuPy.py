@@ -25,10 +25,51 @@ import torch
 from numpy import float32
 
 from . import ops
+from .convergence import check_tolerance, relative_change
 from .projector import HipTools3D, geom_size
-from .regularisersCuPy import prox_regul, reserve_prox_scratch
+from .regularisersCuPy import last_prox, prox_regul, reserve_prox_scratch
 from .supp.dicts import dicts_check
 from .supp.suppTools import _apply_horiz_detector_padding, check_kwargs, perform_recon_crop
+
+
+class _RunMonitor:
+    """Early stopping and the run record of one driver call (``RecToolsIRCuPy.last_run``).
+
+    ``_algorithm_["tolerance"]`` > 0: after every outer iteration the returned variable is compared with its value one outer
+    iteration earlier (tomobar_amd/convergence.py) in one pass that also refreshes the snapshot (ops.rel_change with
+    keep = the snapshot); over z-slabs the (num, den) pair is summed over the ranks first, so all ranks stop together.
+    The snapshot volume exists only while that tolerance is on; with both tolerances off nothing is launched."""
+
+    def __init__(self, rt, method: str, a: dict, start, r: Optional[dict] = None):
+        self.slab = rt.slab
+        self.tol = check_tolerance(a.get("tolerance"), "_algorithm_['tolerance']")
+        self.inner = (r is not None and r.get("method") is not None
+                      and check_tolerance(r.get("tolerance"), "_regularisation_['tolerance']") > 0.0)
+        self.verbose = bool(a.get("verbose"))
+        self.snap = start.clone() if self.tol > 0.0 else None   # v_0: the starting volume
+        self.run = rt.last_run = {"method": method, "iterations_done": int(a["iterations"]), "converged": False,
+                                  "rel_change": [], "prox_iterations": []}
+
+    def prox_done(self) -> None:
+        """after a proximal call: how many inner iterations it ran (recorded while the inner tolerance is on)"""
+        if self.inner:
+            self.run["prox_iterations"].append(last_prox()[0])
+
+    def stop(self, k: int, v) -> bool:
+        """after outer iteration k (1-based) with the returned variable in `v`: True if the loop ends here"""
+        if self.snap is None:
+            return False
+        pair = ops.rel_change(v, self.snap, self.snap)
+        if self.slab is not None:
+            pair = self.slab.allreduce_sums(pair)
+        d = relative_change(*pair)
+        self.run["rel_change"].append(d)
+        if not d < self.tol:
+            return False
+        self.run["iterations_done"], self.run["converged"] = k, True
+        if self.verbose:
+            print(f"{self.run['method']} stopped after iteration {k}: relative change {d:.3e} < tolerance {self.tol:.3e}")
+        return True
 
 
 class RecToolsIRCuPy:
@@ -59,6 +100,7 @@ class RecToolsIRCuPy:
         self.Atools = HipTools3D(DetectorsDimH, DetectorsDimH_pad, DetectorsDimV, AnglesVec, CenterRotOffset,
                                  ObjSize, "gpu", device_projector, OS_number)
         self.power_seed = None  # set to an int for a reproducible power-method start vector
+        self.last_run = None    # record of the most recent driver call (see _RunMonitor): iterations run, relative changes
         self.slab = None        # tomobar_amd.slab.SlabComm when this object reconstructs one z-slab of a larger volume
 
     @property
@@ -225,6 +267,7 @@ class RecToolsIRCuPy:
         zquad = not (use_ring or use_swls) and not getattr(A, "has_vertical_shift", False)
         A.set_residual_layout("zquad" if zquad else "planar")
         n_sub_total = a["iterations"] * self.OS_number
+        mon = _RunMonitor(self, "FISTA", a, x0, r)
         try:
             for it_no in range(a["iterations"]):
                 for sub_ind in range(self.OS_number):
@@ -253,6 +296,7 @@ class RecToolsIRCuPy:
                     else:
                         A.grad_step(res[sub], X_t, X_grad, L_inv, nonneg, sub)
                         prox_regul(self, X_grad, r, out=X_prox)
+                        mon.prox_done()
                         if it_no * self.OS_number + sub_ind + 1 < n_sub_total:
                             # also leaves X_t transposed for the next forward projection; after the LAST sub-iteration X_t
                             # is never read again (the reference still computes it, methodsIR_CuPy.py:475): skipped
@@ -261,6 +305,9 @@ class RecToolsIRCuPy:
                     if use_ring:
                         # r <- soft(r, lambda) ;  r_x = r + beta (r - r_old)
                         A.ring_update(r_cur, r_old, r_x, float32(ring_lambda), beta)
+                # (the momentum of the last sub-iteration is already launched when the loop ends here: X is returned, not X_t)
+                if mon.stop(it_no + 1, X):
+                    break
         finally:
             A.set_residual_layout("planar")
             A.invalidate()
@@ -292,6 +339,7 @@ class RecToolsIRCuPy:
         res = {}
         # the residual goes from the forward projector straight into the fused z-update: quad-interleaved (see FISTA)
         A.set_residual_layout("planar" if getattr(A, "has_vertical_shift", False) else "zquad")
+        mon = _RunMonitor(self, "ADMM", a, x0, r)
         try:
             for iter_no in range(a["iterations"]):
                 for sub_ind in range(self.OS_number):
@@ -304,11 +352,14 @@ class RecToolsIRCuPy:
                                     float32(alpha), nonneg, sub)
                     if has_prox:
                         prox_regul(self, zu, r_local, out=x)
+                        mon.prox_done()
                     else:
                         x, zu = zu, x
                 ops.admm_dual(u, z, x)  # once per outer iteration (:566)
                 if a["verbose"] and np.mod(iter_no, (round)(a["iterations"] / 5) + 1) == 0:
                     print("ADMM iteration (", iter_no + 1, ") using", r["method"], "regularisation")
+                if mon.stop(iter_no + 1, x):
+                    break
         finally:
             A.set_residual_layout("planar")
         return self._finalise(x, a)
@@ -325,10 +376,13 @@ class RecToolsIRCuPy:
         A.set_residual_layout("planar" if getattr(A, "has_vertical_shift", False) else "zquad")
         try:
             res = A.residual_buffer(None)
-            for _ in range(a["iterations"]):
+            mon = _RunMonitor(self, "Landweber", a, x)
+            for k in range(a["iterations"]):
                 A.residual(x, b, None, "LS", None, res)
                 # x - tau*g with the clamp as a separate rounding step, like the reference's in-place ops
                 A.grad_step(res, x, x, step, a["nonnegativity"], None)
+                if mon.stop(k + 1, x):
+                    break
         finally:
             A.set_residual_layout("planar")
         return self._finalise(x, a)
@@ -349,7 +403,8 @@ class RecToolsIRCuPy:
         x = ones_v
         res = torch.empty_like(b)
         upd = self._new_vol()
-        for _ in range(a["iterations"]):
+        mon = _RunMonitor(self, "SIRT", a, x)
+        for k in range(a["iterations"]):
             A.forward(x, None, out=res)
             ops.axpby(1.0, b, -1.0, res)   # b - Ax
             ops.mul(R, res)
@@ -358,6 +413,8 @@ class RecToolsIRCuPy:
             ops.axpby(1.0, upd, 1.0, x)
             if a["nonnegativity"]:
                 ops.clamp_min(x, 0.0)
+            if mon.stop(k + 1, x):
+                break
         return self._finalise(x, a)
 
     def CGLS(self, _data_: dict, _algorithm_: Union[dict, None] = None) -> torch.Tensor:
@@ -370,7 +427,8 @@ class RecToolsIRCuPy:
         normr2 = float32(self._gdot(dvec, dvec))
         Ad = torch.empty_like(r_vec)
         s = self._new_vol()
-        for _ in range(a["iterations"]):
+        mon = _RunMonitor(self, "CGLS", a, x)
+        for k in range(a["iterations"]):
             A.forward(dvec, None, out=Ad)
             alpha = float32(normr2 / float32(self._gdot(Ad, Ad)))
             ops.axpby(alpha, dvec, 1.0, x)
@@ -382,6 +440,8 @@ class RecToolsIRCuPy:
             ops.axpby(1.0, s, beta, dvec)  # d = s + beta d
             if a["nonnegativity"]:
                 ops.clamp_min(x, 0.0)
+            if mon.stop(k + 1, x):
+                break
         return self._finalise(x, a)
 
     def OSEM(self, _data_: dict, _algorithm_: Union[dict, None] = None,
@@ -400,7 +460,8 @@ class RecToolsIRCuPy:
         ops.clamp_min(normalisation, eps)
         del ones_s
         ratio, back = {}, self._new_vol()
-        for _ in range(a["iterations"]):
+        mon = _RunMonitor(self, "OSEM", a, x, r)
+        for k in range(a["iterations"]):
             for sub_ind in range(self.OS_number):
                 sub = sub_ind if use_os else None
                 if sub not in ratio:
@@ -412,4 +473,7 @@ class RecToolsIRCuPy:
                 ops.mul(back, x)
                 if r["method"] is not None:
                     x = prox_regul(self, x, r)
+                    mon.prox_done()
+            if mon.stop(k + 1, x):
+                break
         return self._finalise(x, a)

@@ -154,6 +154,22 @@ def dot(x, y) -> float:
     return out.value
 
 
+def rel_change(x, ref, keep=None):
+    """(num, den) = (sum (x - ref)^2, sum x^2) in float64 from the float32 values, one streaming pass (tomo_rel_change);
+    with `keep` (a float32 array of the same size; may be `ref` itself) the pass also writes ``keep[...] = x``.  The
+    relative change the tolerance keys are compared with is ``convergence.relative_change(num, den)``.  Synchronises the
+    stream."""
+    for name, t in (("x", x), ("ref", ref), ("keep", keep)):
+        if t is not None:
+            _chk_f32(t, name)
+            if t.numel() != x.numel():
+                raise ValueError(f"{name} must have as many elements as x")
+    out = (C.c_double * 2)()
+    with torch.cuda.device(x.device):
+        L.check(L.lib().tomo_rel_change(ptr(x), ptr(ref), ptr(keep), x.numel(), out, stream_ptr(x)))
+    return float(out[0]), float(out[1])
+
+
 def pwls_weights(b, slab=None):
     """w = max(b, 1e-6) / max(max(b, 1e-6)); with a SlabComm the maximum is taken over all z-slabs."""
     w = torch.empty_like(b)
@@ -214,6 +230,29 @@ def roftv(data, out, lam, tau, iterations, half):
         L.check(L.lib().tomo_roftv(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, float(lam), float(tau),
                                    int(iterations), int(bool(half)), stream_ptr(data)))
     return out
+
+
+def pdtv_tol(data, out, sigma, tau, lt, theta, iterations, methodTV, nonneg, half, tolerance):
+    """`pdtv` with the stopping rule of tomo_pdtv_tol: returns (out, iterations_done, rel_change) -- the last relative
+    change evaluated, NaN if no check took place."""
+    dx, dy, dz, nd = _tv_dims(data)
+    done, last = C.c_int(0), C.c_double(float("nan"))
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_pdtv_tol(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, float(sigma), float(tau),
+                                      float(lt), float(theta), int(iterations), int(bool(methodTV)), int(bool(nonneg)),
+                                      int(bool(half)), float(tolerance), C.byref(done), C.byref(last), stream_ptr(data)))
+    return out, int(done.value), float(last.value)
+
+
+def roftv_tol(data, out, lam, tau, iterations, half, tolerance):
+    """`roftv` with the stopping rule of tomo_roftv_tol: returns (out, iterations_done, rel_change)."""
+    dx, dy, dz, nd = _tv_dims(data)
+    done, last = C.c_int(0), C.c_double(float("nan"))
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_roftv_tol(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, float(lam), float(tau),
+                                       int(iterations), int(bool(half)), float(tolerance), C.byref(done), C.byref(last),
+                                       stream_ptr(data)))
+    return out, int(done.value), float(last.value)
 
 
 _variant_state = threading.local()   # mirror of the library's per-thread switches, per flavour: lets `variant()` restore

@@ -9,12 +9,27 @@ iteration, launched back to back on the caller's stream, scratch taken from the 
 
 from __future__ import annotations
 
-from typing import Tuple
+import threading
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
+from .convergence import check_tolerance
+
+_last = threading.local()
+
+
+def last_prox() -> Optional[Tuple[int, float]]:
+    """(iterations_done, rel_change) of the calling thread's most recent ``prox_regul`` / ``PD_TV_cupy`` / ``ROF_TV_cupy``
+    call: how many inner iterations ran and the last relative change the stopping rule evaluated (NaN if it evaluated
+    none, e.g. with the tolerance off); None before the first call."""
+    return getattr(_last, "value", None)
+
+
+def _record(done: int, rel_change: float) -> None:
+    _last.value = (int(done), float(rel_change))
 
 
 def prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch.Tensor:
@@ -22,7 +37,10 @@ def prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch
 
     One key beyond the reference's: ``_regularisation_["exact_roundings"] = True`` runs PD_TV with the rounding sequence of
     the reference's kernels for float32 duals too (``tomo_set_variant("pdtv", 22)``: bit-identical to the reference
-    arithmetic, 5-16 % slower per launch) for this call; absent / False = the default (within 1e-5)."""
+    arithmetic, 5-16 % slower per launch) for this call; absent / False = the default (within 1e-5).
+
+    ``_regularisation_["tolerance"]`` > 0 stops the inner iterations early (tomobar_amd/convergence.py; the reference
+    accepts the key and ignores it); ``last_prox()`` tells how far the call got."""
     if _regularisation_.get("exact_roundings") and "PD_TV" in _regularisation_["method"] and ops.get_variant("pdtv") == 0:
         with ops.variant("pdtv", 22):
             return _prox_regul(self, X, _regularisation_, out)
@@ -32,26 +50,34 @@ def prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch
 def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch.Tensor:
     method = _regularisation_["method"]
     slab = getattr(self, "slab", None)
+    tol = check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']")
     if slab is not None and X.dim() == 3 and min(X.shape) > 1:
         # the volume is one z-slab of a larger one: 3D TV with ghost planes exchanged between z-neighbours
         from .slab import pd_tv_slab, rof_tv_slab
         X = ops.contiguous(X)
+        info = {"iterations_done": _regularisation_["iterations"], "rel_change": float("nan")}
+        res = None
         if "ROF_TV" in method:
-            return rof_tv_slab(X, slab, _regularisation_["regul_param"], _regularisation_["iterations"],
-                               _regularisation_["time_marching_step"], _regularisation_.get("half_precision", False),
-                               out=out)
-        if "PD_TV" in method:
-            return pd_tv_slab(X, slab, _regularisation_["regul_param"], _regularisation_["iterations"],
-                              _regularisation_["methodTV"], self.nonneg_regul, _regularisation_["PD_LipschitzConstant"],
-                              _regularisation_.get("half_precision", False), out=out)
+            res = rof_tv_slab(X, slab, _regularisation_["regul_param"], _regularisation_["iterations"],
+                              _regularisation_["time_marching_step"], _regularisation_.get("half_precision", False),
+                              out=out, tolerance=tol, info=info)
+        elif "PD_TV" in method:
+            res = pd_tv_slab(X, slab, _regularisation_["regul_param"], _regularisation_["iterations"],
+                             _regularisation_["methodTV"], self.nonneg_regul, _regularisation_["PD_LipschitzConstant"],
+                             _regularisation_.get("half_precision", False), out=out, tolerance=tol,
+                             info=info)
+        if res is not None:
+            _record(info["iterations_done"], info["rel_change"])
+            return res
     if "ROF_TV" in method:
         return ROF_TV_cupy(X, _regularisation_["regul_param"], _regularisation_["iterations"],
                            _regularisation_["time_marching_step"], self.Atools.device_index,
-                           _regularisation_.get("half_precision", False), out=out)
+                           _regularisation_.get("half_precision", False), out=out, tolerance=tol)
     if "PD_TV" in method:
         return PD_TV_cupy(X, _regularisation_["regul_param"], _regularisation_["iterations"],
                           _regularisation_["methodTV"], self.nonneg_regul, _regularisation_["PD_LipschitzConstant"],
-                          self.Atools.device_index, _regularisation_.get("half_precision", False), out=out)
+                          self.Atools.device_index, _regularisation_.get("half_precision", False), out=out,
+                          tolerance=tol)
     raise ValueError(f"unknown regularisation method {method!r}: ROF_TV and PD_TV are supported")
 
 
@@ -91,23 +117,33 @@ def _finish(result, is2d, axis, orig_shape, out, given=None):
 
 def ROF_TV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int = 3000,
                 time_marching_parameter: float = 0.001, gpu_id: int = 0, half_precision: bool = False,
-                out=None) -> torch.Tensor:
+                out=None, tolerance: float = 0.0) -> torch.Tensor:
     """Rudin-Osher-Fatemi TV by explicit time marching (reference: regularisersCuPy.py:41-167).
 
     ``half_precision`` reproduces the reference's binary16 storage of the D fields (they are rounded through
-    half in registers; the fused kernel never writes them to memory)."""
+    half in registers; the fused kernel never writes them to memory).  ``tolerance`` > 0 (no reference counterpart) stops
+    the iterations early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after which iteration."""
+    tolerance = check_tolerance(tolerance, "tolerance")
     orig_shape = tuple(data.shape)
     d, is2d, axis = _prepare(data, gpu_id)
     res = torch.empty_like(d) if out is None else out.view(d.shape)
-    ops.roftv(d, res, np.float32(regularisation_parameter), np.float32(time_marching_parameter), iterations,
-              half_precision)
+    if tolerance > 0.0:
+        _, done, change = ops.roftv_tol(d, res, np.float32(regularisation_parameter), np.float32(time_marching_parameter),
+                                        iterations, half_precision, tolerance)
+        _record(done, change)
+    else:
+        ops.roftv(d, res, np.float32(regularisation_parameter), np.float32(time_marching_parameter), iterations,
+                  half_precision)
+        _record(iterations, float("nan"))
     return _finish(res, is2d, axis, orig_shape, out, data)
 
 
 def PD_TV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int = 1000, methodTV: int = 0,
                nonneg: int = 0, lipschitz_const: float = 8.0, gpu_id: int = 0, half_precision: bool = False,
-               out=None) -> torch.Tensor:
-    """Chambolle-Pock primal-dual TV (reference: regularisersCuPy.py:170-296)."""
+               out=None, tolerance: float = 0.0) -> torch.Tensor:
+    """Chambolle-Pock primal-dual TV (reference: regularisersCuPy.py:170-296).  ``tolerance`` > 0 (no reference
+    counterpart) stops the iterations early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after which."""
+    tolerance = check_tolerance(tolerance, "tolerance")
     orig_shape = tuple(data.shape)
     d, is2d, axis = _prepare(data, gpu_id)
     # float32 scalar set-up of regularisersCuPy.py:215-218 (NumPy-2 weak-scalar promotion => float32 arithmetic)
@@ -116,7 +152,12 @@ def PD_TV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int = 
     theta = np.float32(1.0)
     lt = np.float32(tau / regularisation_parameter)
     res = torch.empty_like(d) if out is None else out.view(d.shape)
-    ops.pdtv(d, res, sigma, tau, lt, theta, iterations, methodTV, nonneg, half_precision)
+    if tolerance > 0.0:
+        _, done, change = ops.pdtv_tol(d, res, sigma, tau, lt, theta, iterations, methodTV, nonneg, half_precision, tolerance)
+        _record(done, change)
+    else:
+        ops.pdtv(d, res, sigma, tau, lt, theta, iterations, methodTV, nonneg, half_precision)
+        _record(iterations, float("nan"))
     return _finish(res, is2d, axis, orig_shape, out, data)
 
 

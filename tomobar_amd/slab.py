@@ -28,6 +28,8 @@ from typing import Callable, List, Optional
 import numpy as np
 import torch
 
+from .convergence import check_tolerance, inner_check_due, relative_change
+
 
 def slab_bounds(nz_total: int, world: int, rank: int):
     """Contiguous slab [z0, z1) of rank `rank`, balanced: the first ``nz_total % world`` ranks hold one slice more
@@ -89,6 +91,15 @@ class SlabComm:
         t = torch.tensor([value], dtype=torch.float64, device=self._scalar_device())
         self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
         return float(t.item())
+
+    def allreduce_sums(self, values) -> List[float]:
+        """Element-wise sum of a few scalars over the ranks in ONE all-reduce (e.g. the (num, den) pair of the stopping
+        rule): every rank receives the same sums, so every rank takes the same decision."""
+        if self.world == 1:
+            return [float(v) for v in values]
+        t = torch.tensor([float(v) for v in values], dtype=torch.float64, device=self._scalar_device())
+        self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
+        return [float(v) for v in t.tolist()]
 
     def allreduce_max(self, value: float) -> float:
         t = torch.tensor([value], dtype=torch.float64, device=self._scalar_device())
@@ -517,10 +528,46 @@ def _hip_pd_pair(inp, u_in, u_out, p_in, p_out, dx, dy, nzl, lo, hi, sigma, tau,
                                                    ops.stream_ptr(inp)))
 
 
+def _hip_rel_change(x, ref, keep):
+    from . import ops
+    return ops.rel_change(x, ref, keep)
+
+
+class _SlabTolerance:
+    """The stopping rule of a TV operator on a z-slab (tomobar_amd/convergence.py): at a check point every rank runs
+    rel_change on its LOCAL planes (ghost planes are not counted), the (num, den) pair is summed over the ranks in one
+    all-reduce, and all ranks take the same -- the whole-volume -- decision.  Call `stop` only between exchanges: every
+    check point has a launch after it, so the ghost refresh that follows its launch has been posted AND completed on all
+    ranks; no rank is left waiting on a neighbour that stopped."""
+
+    def __init__(self, comm, data, iterations, tolerance, info):
+        self.comm, self.data, self.iterations = comm, data.contiguous(), int(iterations)
+        self.tol = check_tolerance(tolerance, "tolerance")
+        self.info = info if info is not None else {}
+        self.info.update(iterations_done=self.iterations, rel_change=float("nan"))
+        self.snap = None
+
+    def stop(self, n: int, current: torch.Tensor) -> bool:
+        if not (self.tol > 0.0 and inner_check_due(n, self.iterations)):
+            return False
+        ref = self.data if self.snap is None else self.snap
+        if self.snap is None:
+            self.snap = torch.empty_like(self.data)
+        d = relative_change(*self.comm.allreduce_sums(_hip_rel_change(current, ref, self.snap)))
+        self.info["rel_change"] = d
+        if d < self.tol:
+            self.info["iterations_done"] = n
+            return True
+        return False
+
+
 def pd_tv_slab(data: torch.Tensor, comm, regularisation_parameter, iterations, methodTV=0, nonneg=0,
                lipschitz_const=8.0, half_precision=False, pair_fn: Optional[Callable] = None,
-               step_fn: Optional[Callable] = None, out=None, overlap: bool = True):
-    """PD_TV of a z-slab of a larger 3D volume; bit-identical to running PD_TV_cupy on the whole volume."""
+               step_fn: Optional[Callable] = None, out=None, overlap: bool = True, tolerance: float = 0.0,
+               info: Optional[dict] = None):
+    """PD_TV of a z-slab of a larger 3D volume; bit-identical to running PD_TV_cupy on the whole volume -- with a
+    `tolerance` too: all ranks stop after the iteration the whole-volume run stops after (`info`, when given, receives
+    "iterations_done" and "rel_change")."""
     tau = np.float32(regularisation_parameter * 0.1)
     sigma = np.float32(1.0 / (lipschitz_const * tau))
     theta = np.float32(1.0)
@@ -534,7 +581,13 @@ def pd_tv_slab(data: torch.Tensor, comm, regularisation_parameter, iterations, m
     # stream while the interior of the slab is computed, and the next launch starts when both are done.
     overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
     plan = pd_launch_plan(iterations, half_precision)
+    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
+    done = 0
     for n, k in enumerate(plan):
+        if rule.stop(done, st.result()):   # (every check point is a launch boundary of the plan, as in tomo_pdtv_tol)
+            iterations = done
+            break
+        done += k
         more = n + 1 < len(plan)
         if k >= 2 and overlap and more:
             for z0, z1 in edge_ranges:
@@ -631,7 +684,9 @@ def _hip_rof_step(inp, u_in, u_out, dx, dy, nzl, lo, hi, lam, tau, half, zr=None
 
 
 def rof_tv_slab(data: torch.Tensor, comm, regularisation_parameter, iterations, time_marching_parameter,
-                half_precision=False, step_fn: Optional[Callable] = None, out=None, overlap: bool = True):
+                half_precision=False, step_fn: Optional[Callable] = None, out=None, overlap: bool = True,
+                tolerance: float = 0.0, info: Optional[dict] = None):
+    """ROF_TV of a z-slab of a larger 3D volume (`tolerance`, `info`: see pd_tv_slab)."""
     comm.validate_slabs(data.shape[0])
     st = RofSlab(data, comm.has_lo, comm.has_hi, half_precision, step_fn or _hip_rof_step,
                  alloc=_hip_alloc(PLACED_SLOT_ROF) if (step_fn is None and data.is_cuda) else None)
@@ -639,7 +694,11 @@ def rof_tv_slab(data: torch.Tensor, comm, regularisation_parameter, iterations, 
     comm.exchange(st.send_down(0), st.recv_down(0), st.send_up(0), st.recv_up(0))
     edge_ranges, interior = st.boundary_ranges()
     overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
+    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
     for it in range(iterations):
+        if rule.stop(it, st.local(st.U[it & 1])):
+            iterations = it
+            break
         more = it + 1 < iterations
         b = (it + 1) & 1
         if overlap and more:  # boundary planes, exchange in flight, interior (see pd_tv_slab)

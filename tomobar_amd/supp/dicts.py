@@ -11,6 +11,7 @@ from __future__ import annotations
 from typing import Optional
 
 from .. import ops
+from ..convergence import check_tolerance
 from .funcs import _data_dims_swapper
 
 LABELS_3D = ["detY", "angles", "detX"]
@@ -105,6 +106,8 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
     if _algorithm_["nonnegativity"] not in [True, False]:
         raise ValueError("_algorithm_['nonnegativity'] should be set to True or False.")
     self.nonneg_regul = 1 if _algorithm_["nonnegativity"] else 0
+    # the tolerance keys are honoured here (tomobar_amd/convergence.py; the reference accepts and ignores them)
+    check_tolerance(_algorithm_["tolerance"], "_algorithm_['tolerance']")
 
     # ------------------------------------------------------------------ _regularisation_
     if _regularisation_ is None:
@@ -114,4 +117,5 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
     if method_run in {"FISTA", "ADMM", "OSEM"}:
         for key, value in _REGULARISATION_DEFAULTS:
             _regularisation_.setdefault(key, value)
+    check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']")
     return (_data_, _algorithm_, _regularisation_)

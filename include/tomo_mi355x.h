@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* raised whenever an entry point is added or a signature changes (tomobar_amd/_lib.py checks it at load) */
-#define TOMO_ABI_VERSION 7
+#define TOMO_ABI_VERSION 8
 
 enum {
     TOMO_OK = 0,
@@ -341,33 +341,20 @@ int tomo_pdtv_iter_slab(int device, const float *in_dev, const float *u_in_dev, 
                         const void *p_in_dev[3], void *p_out_dev[3], int dx, int dy, int nz_local,
                         int has_lo, int has_hi, float sigma, float tau, float lt, float theta,
                         int methodTV, int nonneg, int half, void *stream);
-/* Two PD-TV iterations in one pass on a slab: arrays address [lo_planes + nz_local + hi_planes][dy][dx] with
- * lo_planes, hi_planes in {0, 2, 3}.  Ghost planes that must be valid on entry: U two planes either side; P two planes
- * below and the first plane above; Input the nearer plane either side.  Result = two applications of
- * tomo_pdtv_iter_slab with a ghost refresh in between, bit for bit. */
-int tomo_pdtv_pair_slab(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
-                        const void *p_in_dev[3], void *p_out_dev[3], int dx, int dy, int nz_local,
-                        int lo_planes, int hi_planes, float sigma, float tau, float lt, float theta,
-                        int methodTV, int nonneg, int half, void *stream);
-/* Same, restricted to the local output planes [z_begin, z_end) (0 <= z_begin <= z_end <= nz_local).  Lets a rank
- * compute the planes its neighbours wait for first, start the halo exchange, and compute the interior while the
- * planes travel (tomobar_amd/slab.py).  tomo_pdtv_pair_slab == the range [0, nz_local). */
-int tomo_pdtv_pair_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
-                              const void *p_in_dev[3], void *p_out_dev[3], int dx, int dy, int nz_local,
-                              int lo_planes, int hi_planes, int z_begin, int z_end, float sigma, float tau,
-                              float lt, float theta, int methodTV, int nonneg, int half, void *stream);
 /* K iterations (k = 2 or 3) in one pass on a slab whose arrays carry lo_planes / hi_planes in {0, k..3} ghost planes.
  * Ghost planes that must be valid on entry: U and P1..3 k planes below, U k planes and P1..3 k-1 planes above, Input
  * k-1 planes either side.  Result = k applications of tomo_pdtv_iter_slab with ghost refreshes in between, bit for bit.
+ * Only the local output planes [z_begin, z_end) are written (0 <= z_begin <= z_end <= nz_local): a rank computes the
+ * planes its neighbours wait for first, starts the halo exchange, and computes the interior while the planes travel
+ * (tomobar_amd/slab.py).
  * (Which k a run uses is the host's choice: tomobar_amd/slab.py asks tomo_pdtv_iters_per_launch -- 3 for both dual types in the shipped build.) */
 int tomo_pdtv_multi_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
                                const void *p_in_dev[3], void *p_out_dev[3], int dx, int dy, int nz_local,
                                int lo_planes, int hi_planes, int z_begin, int z_end, int k, float sigma, float tau,
                                float lt, float theta, int methodTV, int nonneg, int half, void *stream);
-int tomo_roftv_iter_slab(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
-                         int dx, int dy, int nz_local, int lo_planes, int hi_planes,
-                         float lambda, float tau, int half, void *stream);
-/* Same for the local output planes [z_begin, z_end) only (boundary planes first, exchange, then the interior). */
+/* One ROF_TV iteration on a slab whose arrays address [lo_planes + nz_local + hi_planes][dy][dx] with lo_planes in {0, 2}
+ * and hi_planes in {0, 1}, for the local output planes [z_begin, z_end) only (boundary planes first, exchange, then the
+ * interior). */
 int tomo_roftv_iter_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
                                int dx, int dy, int nz_local, int lo_planes, int hi_planes, int z_begin, int z_end,
                                float lambda, float tau, int half, void *stream);
@@ -387,6 +374,10 @@ int tomo_halo_unpack(const void *staging_dev, void *const *dst_dev, const size_t
  * the calling thread's kernel variant: a slab driver that wants to be launch-for-launch identical to the whole-volume
  * operator cuts its iterations the same way (tomobar_amd/slab.py: pd_launch_plan) and keeps that many ghost planes. */
 int tomo_pdtv_iters_per_launch(int half);
+/* How tomo_pdtv cuts `iters` iterations of an nd-dimensional run (dz planes; ignored for nd = 2) into launches under the
+ * calling thread's kernel variant: returns the number of launches and writes the iteration count of the first `capacity`
+ * of them to k_out (may be NULL).  Pure host code, no kernel is launched; -1 for nd outside {2, 3} or dz < 1. */
+int tomo_pdtv_launch_plan(int iters, int nd, int dz, int *k_out, int capacity);
 
 /* ---------------------------------------------------------------- FBP filter
  * tomo_fbp_filter replaces _filtersinc3D_cupy (tomobar/fourier.py:26-78) and generate_filtersinc

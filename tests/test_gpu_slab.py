@@ -1,4 +1,4 @@
-"""GPU test of the z-slab TV kernels (tomo_pdtv_iter_slab / tomo_roftv_iter_slab): one volume is cut into slabs that all
+"""GPU test of the z-slab TV kernels (tomo_pdtv_iter_slab / tomo_roftv_iter_slab_range): one volume is cut into slabs that all
 live on the single test GPU; the slab drivers of tomobar_amd.slab run on each of them with the ghost planes refreshed by
 direct copies (what RCCL send/recv does between GPUs), and the stitched result must equal the whole-volume operator bit
 for bit.  The multi-process exchange itself is covered on CPU by tests/test_slab_gloo.py."""

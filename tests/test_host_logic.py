@@ -113,6 +113,50 @@ def test_use_flavour_is_per_thread():
         _lib.use_flavour("nightly")
 
 
+def _c_pd_plan(handle, iters, nd, dz):
+    k = (C.c_int * 80)()
+    n = handle.tomo_pdtv_launch_plan(iters, nd, dz, k, 80)
+    assert 0 <= n <= 80
+    assert handle.tomo_pdtv_launch_plan(iters, nd, dz, None, 0) == n   # the count alone
+    return list(k[:n])
+
+
+def test_pd_launch_plan_of_the_library_and_of_the_slab_driver_agree():
+    """tomo_pdtv cuts a prox into launches with pd_plan (csrc/tv_kernels.hip), the z-slab driver with slab.pd_launch_plan; the
+    stopping rule of both relies on every check point being a launch boundary of either.  tomo_pdtv_launch_plan exports
+    the library's plan (host code, no kernel runs): the two must be the same list for every iteration count, under every
+    variant, and volumes thinner than a fused launch is deep take that many iterations per launch at most."""
+    from tomobar_amd import _lib
+    from tomobar_amd.slab import pd_launch_plan
+
+    def check(handle, variants):
+        for v in variants:
+            assert handle.tomo_set_variant(b"pdtv", v) == _lib.OK
+            try:
+                for half in (False, True):
+                    kmax = handle.tomo_pdtv_iters_per_launch(int(half))
+                    assert kmax == {1: 1, 2: 2}.get(v, 3)
+                    for iters in range(65):
+                        want = pd_launch_plan(iters, half, kmax=kmax)
+                        assert sum(want) == iters
+                        for dz in (3, 4, 100):
+                            assert _c_pd_plan(handle, iters, 3, dz) == want, (v, iters, dz)
+                        for dz in (1, 2):   # a fused launch of k iterations marches k planes ahead of its output
+                            assert _c_pd_plan(handle, iters, 3, dz) == pd_launch_plan(iters, half, kmax=min(kmax, dz)), (v, iters, dz)
+                        for dz in (1, 2, 50):   # 2D images: dz is ignored
+                            assert _c_pd_plan(handle, iters, 2, dz) == want, (v, iters, dz)
+            finally:
+                handle.tomo_set_variant(b"pdtv", 0)
+        assert handle.tomo_pdtv_launch_plan(5, 4, 8, None, 0) == -1 and handle.tomo_pdtv_launch_plan(5, 3, 0, None, 0) == -1
+        assert _c_pd_plan(handle, -1, 3, 8) == []
+
+    check(_lib.lib(), (0, 22))
+    with _lib.use_flavour("dev") as dev:
+        check(dev, (0, 22, 1, 2, 3, 21))
+    # the plan the CPU-only callers (bench.py, the gloo tests) get without a library: the shipped one
+    assert pd_launch_plan(11, False, kmax=3) == [3, 3, 3, 2] and pd_launch_plan(4, False, kmax=3) == [2, 2]
+
+
 def test_committed_pmc_traffic_is_keyed_to_the_kernel_sources_at_head():
     """profiles/pmc_traffic.json (what bench.py reports as roofline.traffic_committed) is only valid for the kernel sources the
     counters were taken on: every entry carries the sha of those sources, and this test fails as soon as one of them differs

@@ -50,8 +50,8 @@ def test_relative_change_definition():
 
 
 def test_launch_plans_put_every_check_point_on_a_launch_boundary():
-    """the slab plan (and, by the same formula, tomo_pdtv's step_of) cuts the iterations so that every iteration count the
-    rule checks after is the end of a launch, for every iterations-per-launch the library can answer"""
+    """the slab plan (and tomo_pdtv's pd_plan, which tests/test_host_logic.py holds equal to it) cuts the iterations so that
+    every iteration count the rule checks after is the end of a launch, for every iterations-per-launch the library can answer"""
     from tomobar_amd.convergence import inner_check_due
     from tomobar_amd.slab import pd_launch_plan
     for kmax in (1, 2, 3):

@@ -140,26 +140,12 @@ __global__ __launch_bounds__(64 * WX * WY) void pd_zmarch2_kernel(PdArgs a, int 
 template <typename T, int ND, bool NONNEG, bool ANISO, int FAST, int RY, bool LOCKSTEP, int WX = 1, int WY = 4>
 static int pd_zmarch2_launch(PdArgs a, hipStream_t st)
 {
-    const int nout = a.out_end - a.out_begin;
-    const int gx = ceil_div(ceil_div(a.dx, 62), WX), gy = ceil_div(a.dy, WY * RY);
-    const int tiles_per_xcd = ceil_div(gx * gy, 8);
-    // z-chunks: enough waves to fill the chip (~8 per SIMD), each long enough to amortise its warm-up plane
-    int chunks = 1;
-    if (ND == 3) {
-        const long waves_xy = (long)gx * gy * WX * WY;
-        // measured: 48 waves per SIMD's worth of z-chunks (shorter marches, better balance) beats 8-16 by ~5 %
-        const long want_per_simd = 48;
-        const long want = 256L * 4 * want_per_simd;
-        chunks = (int)((want + waves_xy - 1) / waves_xy);
-        const int max_chunks = ceil_div(nout, 32);
-        if (chunks > max_chunks) chunks = max_chunks;
-        if (chunks < 1) chunks = 1;
-    }
-    a.zchunk = ceil_div(nout, chunks);
-    chunks = ceil_div(nout, a.zchunk);
+    // z-chunks (3D only), each long enough to amortise its warm-up plane.  Measured: 48 waves per SIMD's worth of them
+    // (shorter marches, better balance) beats 8-16 by ~5 %
+    ZmarchGrid g;
+    if (int rc = zmarch_grid(g, "PD_TV", a.dx, a.dy, a.out_end - a.out_begin, 62, WX, WY, RY, 48, 32, ND == 3)) return rc;
+    a.zchunk = g.zchunk;
     a.inv1lt = 1.0f / (1.0f + a.lt);
-    const long blocks = 8L * tiles_per_xcd * chunks;
-    if (blocks > 0x7fffffffL) return tomo_fail(TOMO_E_INVALID, "volume too large for one PD_TV launch");
-    pd_zmarch2_kernel<T, ND, NONNEG, ANISO, FAST, RY, LOCKSTEP, WX, WY><<<(unsigned)blocks, 64 * WX * WY, 0, st>>>(a, gx, gy, tiles_per_xcd);
+    pd_zmarch2_kernel<T, ND, NONNEG, ANISO, FAST, RY, LOCKSTEP, WX, WY><<<(unsigned)g.blocks, 64 * WX * WY, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd);
     return TOMO_OK;
 }

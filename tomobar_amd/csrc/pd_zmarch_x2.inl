@@ -201,20 +201,10 @@ __global__ __launch_bounds__(64 * WX * WY) __attribute__((amdgpu_waves_per_eu(1,
 template <typename T, bool NONNEG, bool ANISO, int FAST, int RY, int WX, int WY>
 static int pd_zmarch_x2_launch(PdArgs a, hipStream_t st)
 {
-    const int nout = a.out_end - a.out_begin;
-    const int gx = ceil_div(ceil_div(a.dx, 60), WX), gy = ceil_div(a.dy, WY * RY);
-    const int tiles_per_xcd = ceil_div(gx * gy, 8);
-    const long waves_xy = (long)gx * gy * WX * WY;
-    const long want_per_simd = 32;
-    int chunks = (int)((256L * 4 * want_per_simd + waves_xy - 1) / waves_xy);
-    const int max_chunks = ceil_div(nout, 48);  // two warm-up planes per chunk: keep chunks long
-    if (chunks > max_chunks) chunks = max_chunks;
-    if (chunks < 1) chunks = 1;
-    a.zchunk = ceil_div(nout, chunks);
-    chunks = ceil_div(nout, a.zchunk);
+    ZmarchGrid g;  // two warm-up planes per chunk: keep chunks long
+    if (int rc = zmarch_grid(g, "PD_TV", a.dx, a.dy, a.out_end - a.out_begin, 60, WX, WY, RY, 32, 48)) return rc;
+    a.zchunk = g.zchunk;
     a.inv1lt = 1.0f / (1.0f + a.lt);
-    const long blocks = 8L * tiles_per_xcd * chunks;
-    if (blocks > 0x7fffffffL) return tomo_fail(TOMO_E_INVALID, "volume too large for one PD_TV launch");
-    pd_zmarch_x2_kernel<T, NONNEG, ANISO, FAST, RY, WX, WY><<<(unsigned)blocks, 64 * WX * WY, 0, st>>>(a, gx, gy, tiles_per_xcd);
+    pd_zmarch_x2_kernel<T, NONNEG, ANISO, FAST, RY, WX, WY><<<(unsigned)g.blocks, 64 * WX * WY, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd);
     return TOMO_OK;
 }

@@ -427,19 +427,10 @@ __global__ __launch_bounds__(64 * WX * WY) __attribute__((amdgpu_waves_per_eu(2)
 template <typename T, bool NONNEG, bool ANISO, int FAST, int K, int RY, int WX, int WY, bool LAG = false, int LREG = 0, bool FIRST = false>
 static int pd_zmarch_xk_launch(PdArgs a, hipStream_t st, long want_per_simd = 32, int min_chunk = 24)
 {
-    const int nout = a.out_end - a.out_begin;
-    const int gx = ceil_div(ceil_div(a.dx, 64 - 2 * K), WX), gy = ceil_div(a.dy, WY * RY);
-    const int tiles_per_xcd = ceil_div(gx * gy, 8);
-    const long waves_xy = (long)gx * gy * WX * WY;
-    int chunks = (int)((256L * 4 * want_per_simd + waves_xy - 1) / waves_xy);
-    const int max_chunks = ceil_div(nout, min_chunk * K);  // K warm-up planes per chunk: keep chunks long
-    if (chunks > max_chunks) chunks = max_chunks;
-    if (chunks < 1) chunks = 1;
-    a.zchunk = ceil_div(nout, chunks);
-    chunks = ceil_div(nout, a.zchunk);
+    ZmarchGrid g;  // K warm-up planes per chunk: keep chunks long
+    if (int rc = zmarch_grid(g, "PD_TV", a.dx, a.dy, a.out_end - a.out_begin, 64 - 2 * K, WX, WY, RY, want_per_simd, min_chunk * K)) return rc;
+    a.zchunk = g.zchunk;
     a.inv1lt = 1.0f / (1.0f + a.lt);
-    const long blocks = 8L * tiles_per_xcd * chunks;
-    if (blocks > 0x7fffffffL) return tomo_fail(TOMO_E_INVALID, "volume too large for one PD_TV launch");
     size_t dyn = 0;
 #if TOMO_DEV
     // measurement only (tools/archive/probes/pd_halo_probe.py, bit 8): reserve 72 KiB of dynamic LDS on top of the kernel's own 80 KiB, so
@@ -451,6 +442,6 @@ static int pd_zmarch_xk_launch(PdArgs a, hipStream_t st, long want_per_simd = 32
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
     }
 #endif
-    pd_zmarch_xk_kernel<T, NONNEG, ANISO, FAST, K, RY, WX, WY, LAG, LREG, FIRST><<<(unsigned)blocks, 64 * WX * WY, dyn, st>>>(a, gx, gy, tiles_per_xcd);
+    pd_zmarch_xk_kernel<T, NONNEG, ANISO, FAST, K, RY, WX, WY, LAG, LREG, FIRST><<<(unsigned)g.blocks, 64 * WX * WY, dyn, st>>>(a, g.gx, g.gy, g.tiles_per_xcd);
     return TOMO_OK;
 }

@@ -249,21 +249,8 @@ __global__ __launch_bounds__(64 * WX * WY) void rof_zmarch_kernel(RofArgs a, int
 template <int ND, bool HALF, int FAST, int RY, int WX, int WY>
 static int rof_zmarch_launch(const RofArgs &a, hipStream_t st)
 {
-    const int nout = a.out_end - a.out_begin;
-    const int gx = ceil_div(ceil_div(a.dx, 60), WX), gy = ceil_div(a.dy, WY * RY);
-    const int tiles_per_xcd = ceil_div(gx * gy, 8);
-    int chunks = 1;
-    if (ND == 3) {
-        const long waves_xy = (long)gx * gy * WX * WY;
-        chunks = (int)((256L * 4 * 32 + waves_xy - 1) / waves_xy);
-        const int max_chunks = ceil_div(nout, 32);
-        if (chunks > max_chunks) chunks = max_chunks;
-        if (chunks < 1) chunks = 1;
-    }
-    const int zchunk = ceil_div(nout, chunks);
-    chunks = ceil_div(nout, zchunk);
-    const long blocks = 8L * tiles_per_xcd * chunks;
-    if (blocks > 0x7fffffffL) return tomo_fail(TOMO_E_INVALID, "volume too large for one ROF_TV launch");
-    rof_zmarch_kernel<ND, HALF, FAST, RY, WX, WY><<<(unsigned)blocks, 64 * WX * WY, 0, st>>>(a, gx, gy, tiles_per_xcd, zchunk);
+    ZmarchGrid g;
+    if (int rc = zmarch_grid(g, "ROF_TV", a.dx, a.dy, a.out_end - a.out_begin, 60, WX, WY, RY, 32, 32, ND == 3)) return rc;
+    rof_zmarch_kernel<ND, HALF, FAST, RY, WX, WY><<<(unsigned)g.blocks, 64 * WX * WY, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd, g.zchunk);
     return TOMO_OK;
 }

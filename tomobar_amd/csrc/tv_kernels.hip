@@ -12,19 +12,24 @@
 //     iterations per pass, rows in registers).  Measured history and PMC evidence: docs/kernels/pd_tv.md.
 //   * ROF_TV: rof_zmarch.inl, divergence and update fused on the same z-march skeleton: the D fields never reach
 //     HBM (12 B/voxel/iteration) and are evaluated once per voxel.
+//   * Host side: pd_plan cuts a prox into launches (kernel family + iterations, pure host code), pd_arith maps the variant to
+//     the arithmetic level, pd_launch_one / rof_launch_one are the only launch sites (whole volume and slabs), zmarch_grid
+//     sizes the z-chunk grid of every march.
 //   * -DTOMO_DEV_VARIANTS (libtomo_mi355x_dev.so, tests / tools only): the per-voxel kernels (variant 1: one thread per
 //     voxel, neighbours' duals recomputed from global memory -- the independent implementation) and the builds with the
 //     compiler's IEEE sqrt / divide (2, 21) or relaxed ROF arithmetic.
 // All arithmetic is float32 (explicit fmaf, -ffp-contract=off).  What the SHIPPED defaults reproduce bit for bit: ROF_TV
 // (float32 and binary16 D fields) and PD_TV with binary16 duals follow the rounding sequence of oracle/tomo_oracle.c.
-// PD_TV with float32 duals -- the kernel bench.py times -- ships RELAXED arithmetic (pd_default_is_exact<float>() is false:
+// PD_TV with float32 duals -- the kernel bench.py times -- ships RELAXED arithmetic (pd_arith(0, float32) = 1:
 // v_rsq_f32, a hoisted reciprocal): within 1e-5 relative L2 of the reference, NOT bit-identical; tomo_set_variant("pdtv", 22)
 // (`_regularisation_["exact_roundings"] = True` through the classes) selects the reference's roundings there too, at about
 // +10 % per launch.  docs/kernels/pd_tv.md has the measurements behind that choice.
 #include "tomo_common.h"
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <utility>
+#include <vector>
 
 namespace {
 
@@ -422,54 +427,150 @@ __device__ __forceinline__ void pd_primal_block(float (&out)[NB], const float (&
     }
 }
 
+// The launch grid of a z-march kernel: a workgroup of wx x wy waves covers wx tiles of `tile_x` columns (a wave's 64 lanes
+// less its halo lanes) by wy * ry rows; 3D volumes are cut into z-chunks, enough of them for `want_per_simd` waves on
+// each of the chip's 256 x 4 SIMDs but none shorter than `min_planes` planes (every chunk pays the march's warm-up planes).
+// Workgroups are numbered so that each of the 8 XCDs gets `tiles_per_xcd` xy tiles of every chunk (see the kernels).
+struct ZmarchGrid {
+    int gx, gy, tiles_per_xcd, zchunk;
+    long blocks;
+};
+static int zmarch_grid(ZmarchGrid &g, const char *op, int dx, int dy, int nout, int tile_x, int wx, int wy, int ry,
+                       long want_per_simd, int min_planes, bool chunked = true)
+{
+    g.gx = ceil_div(ceil_div(dx, tile_x), wx);
+    g.gy = ceil_div(dy, wy * ry);
+    g.tiles_per_xcd = ceil_div(g.gx * g.gy, 8);
+    int chunks = 1;
+    if (chunked) {
+        const long waves_xy = (long)g.gx * g.gy * wx * wy;
+        chunks = (int)((256L * 4 * want_per_simd + waves_xy - 1) / waves_xy);
+        const int max_chunks = ceil_div(nout, min_planes);
+        if (chunks > max_chunks) chunks = max_chunks;
+        if (chunks < 1) chunks = 1;
+    }
+    g.zchunk = ceil_div(nout, chunks);
+    chunks = ceil_div(nout, g.zchunk);
+    g.blocks = 8L * g.tiles_per_xcd * chunks;
+    if (g.blocks > 0x7fffffffL) return tomo_fail(TOMO_E_INVALID, "volume too large for one %s launch", op);
+    return TOMO_OK;
+}
+
 #include "pd_zmarch2.inl"
 #include "pd_zmarch_x2.inl"
 #include "pd_zmarch_xk.inl"
 #include "pd_rows2d.inl"
 
-// Several iterations in one pass through HBM (3D).  `k` = iterations of this launch (2 or 3).
+// ------------------------------------------------------------------------------------------ PD_TV host dispatch
+// pd_plan cuts a prox into launches (pure host code), pd_launch_one maps one of them to a kernel.  A launch is a kernel
+// family and its iteration count:
+//   PD_XK3      three iterations per pass through HBM (pd_zmarch_xk.inl), 3D
+//   PD_X2       two iterations per pass (pd_zmarch_x2.inl), 3D: launch remainders, volumes of two planes, dev variant 2
+//   PD_SINGLE   one iteration (pd_zmarch2.inl), 3D: tails, volumes of one plane
+//   PD_ROWS2D   2D images, k = 1..3 iterations per pass with the rows of a tile in registers (pd_rows2d.inl)
+//   PD_PERVOXEL one iteration, one thread per voxel (dev variant 1: the independent implementation), 2D and 3D
+// Which arithmetic a family runs follows the variant (pd_arith):
 //   variant 0 (shipped default): float32 duals with relaxed arithmetic (FAST = 1: v_rsq_f32 instead of 1 / sqrtf, a
 //              host-computed 1 / (1 + lt) instead of the divide; <= 1e-5 from the reference, typically 3e-7), binary16 duals
 //              with the reference's roundings (FAST = 2; one flipped binary16 rounding is 5e-4 of a dual value, relaxed
-//              arithmetic cannot hold the 1e-5 parity bar there).  k = 3 -> pd_zmarch_xk<K=3, 8 rows, 2x2 waves, LDS lag>,
-//              k = 2 -> pd_zmarch_x2.
+//              arithmetic cannot hold the 1e-5 parity bar there).
 //   variant 22 (shipped, opt-in): the reference's roundings through FMA correction steps (FAST = 2) for float32 duals as
 //              well, same tilings: bit-identical to the oracle.  Round 4, same-box pairs, 30-iteration prox at 1024^3: 10.5-10.7 ms
 //              per three-iteration launch against 9.2 (one box, +16 %; 0.636 vs 0.717 outer iterations/s on the bench,
 //              profiles/archive/r4d_bench_exact_vs_relaxed.txt) or 10.05 (another box, +4.6 %; 0.645 vs 0.668) relaxed -- the ~390
 //              extra VALU instructions per plane of the correction chains (two quarter-rate transcendentals and 13
 //              dependent FMAs per dual row) on a kernel that is bound by instruction issue.  That is why it is not the default.
-//   dev flavour: 3 = relaxed arithmetic for both dual types; 2 = the compiler's IEEE sqrt / divide sequences, two iterations
-//              per launch (pd_zmarch_x2, 2x2 waves); 21 = the same on the K = 3 tiling.  2 and 21 are bit-identical to the
-//              oracle: the independent exactness check of the FMA-corrected build.
+//   dev flavour: 3 = relaxed arithmetic for both dual types; 2 = the compiler's IEEE sqrt / divide sequences (FAST = 0), two
+//              iterations per launch; 21 = the same, three per launch; 1 = per-voxel.  1, 2 and 21 are bit-identical to the
+//              oracle: the independent exactness check of the FMA-corrected build.  31 / 32 = other workgroup shapes of the
+//              relaxed float32 K = 3 kernel (measurement only).
+// The arithmetic of an iteration never depends on how a run is cut into launches (slabs cut it differently): every
+// family follows the variant's arithmetic.
+enum PdFamily { PD_ROWS2D, PD_XK3, PD_X2, PD_SINGLE, PD_PERVOXEL };
+
 static int pd_iters_per_launch(int variant)
 {
     if (variant == 1) return 1;
     return variant == 2 ? 2 : 3;
 }
 
-// arithmetic level of a shipped / relaxed / exact variant for dual type T (the dev builds 2 / 21 use FAST = 0 explicitly)
-template <typename T>
-constexpr bool pd_default_is_exact() { return sizeof(T) == 2; }
-
-// three iterations per launch: 8 rows per lane, 10 of the 90 hand-over slots in registers (80 KB of LDS per workgroup = two
-// workgroups per CU)
-template <typename T, bool NN, bool AN>
-int pd_xk3_launch(const PdArgs &a, int variant, hipStream_t st)
+// FAST level of a variant (the one place that maps them).  A slab driver may ask a fused launch of the dev variants that
+// have none of their own (1: per-voxel, 2 with k = 3): they run the compiler-IEEE build of the tiling asked for.
+static int pd_arith(int variant, int half)
 {
 #if TOMO_DEV
-    if (variant == 3) return pd_zmarch_xk_launch<T, NN, AN, 1, 3, 8, 2, 2, true, 10>(a, st);
+    if (variant == 1 || variant == 2 || variant == 21) return 0;
+    if (variant == 3) return 1;
+#endif
+    return (variant == 22 || half) ? 2 : 1;
+}
+
+struct PdLaunch {
+    PdFamily family;
+    int k;       // iterations of this launch
+    bool flags;  // the family understands PdArgs::p_in_zero / p_out_skip; the others need zeroed input duals on the first launch
+};
+
+static PdFamily pd_single_family(int variant) { return variant == 1 ? PD_PERVOXEL : PD_SINGLE; }
+
+// Cuts `iters` iterations into launches of kmax / 2 / 1 iterations with as few single-iteration launches as possible
+// (4 = 2 + 2, 7 = 3 + 2 + 2: a single iteration costs 1.7x an iteration of a fused launch).  A fused launch of k iterations
+// marches k planes ahead of its output: volumes thinner than that take fewer per launch.  2D images: any k <= 3.
+// tomobar_amd/slab.py (pd_launch_plan) cuts slab runs the same way; tests/test_host_logic.py holds the two together.
+static std::vector<PdLaunch> pd_plan(int nd, int dz, int iters, int variant)
+{
+    const bool rows2d = nd == 2 && variant != 1;
+    const int kmax = nd == 3 ? std::min(pd_iters_per_launch(variant), dz) : pd_iters_per_launch(variant);
+    std::vector<PdLaunch> plan;
+    for (int remaining = iters; remaining > 0; remaining -= plan.back().k) {
+        const int k = (kmax >= 3 && remaining >= 3 && remaining != 4) ? 3 : (remaining >= 2 && kmax >= 2) ? 2 : 1;
+        const PdFamily family = rows2d ? PD_ROWS2D : k == 3 ? PD_XK3 : k == 2 ? PD_X2 : pd_single_family(variant);
+        plan.push_back({family, k, family == PD_ROWS2D || family == PD_XK3});
+    }
+    return plan;
+}
+
+// Lift run-time choices to template arguments: f(type_c<T>, bool_constant<NN>, bool_constant<AN>) / f(int_c<FAST>).
+template <typename T> struct type_c { using type = T; };
+template <int I> using int_c = std::integral_constant<int, I>;
+
+template <typename F>
+int pd_with_flags(int half, int nonneg, int methodTV, F &&f)
+{
+    auto aniso = [&](auto t, auto nn) { return methodTV ? f(t, nn, std::true_type{}) : f(t, nn, std::false_type{}); };
+    auto clip = [&](auto t) { return nonneg ? aniso(t, std::true_type{}) : aniso(t, std::false_type{}); };
+    return half ? clip(type_c<__half>{}) : clip(type_c<float>{});
+}
+
+template <typename F>
+int pd_with_fast(int fast, F &&f)
+{
+#if TOMO_DEV
+    if (fast == 0) return f(int_c<0>{});
+#endif
+    return fast == 2 ? f(int_c<2>{}) : f(int_c<1>{});
+}
+
+// The K = 3 tiling: 8 rows per lane, 2 x 2 waves, 10 of the 90 hand-over slots in registers (80 KB of LDS per workgroup =
+// two workgroups per CU).  One row per special case.
+template <typename T, bool NN, bool AN>
+int pd_xk3_launch(const PdArgs &a, int fast, int variant, hipStream_t st)
+{
+#if TOMO_DEV
     if constexpr (sizeof(T) == 4) {  // workgroup shapes of the shipped relaxed kernel, measurement only (tools/archive/probes/pd_time.py)
         if (variant == 31) return pd_zmarch_xk_launch<T, NN, AN, 1, 3, 8, 1, 4, true, 10>(a, st);
         if (variant == 32) return pd_zmarch_xk_launch<T, NN, AN, 1, 3, 8, 4, 1, true, 10>(a, st);
     }
-    if (variant == 21) {
+    if (fast == 0) {
         if constexpr (sizeof(T) == 4) return pd_zmarch_xk_launch<T, NN, AN, 0, 3, 8, 2, 2, true, 10>(a, st);
         else return pd_zmarch_xk_launch<T, NN, AN, 0, 3, 4, 2, 2, true>(a, st);  // 4 rows per lane: the IEEE expansions need the registers
     }
+    if (variant == 3) return pd_zmarch_xk_launch<T, NN, AN, 1, 3, 8, 2, 2, true, 10>(a, st);
 #endif
-    const bool first = a.p_in_zero && a.u_in == a.in;  // first launch of a prox: its own instantiation (see pd_zmarch_xk.inl, FIRST)
-    if (variant == 22 || pd_default_is_exact<T>())
+    // the first launch of a prox (zero duals, Input = iterate) has its own instantiation (see pd_zmarch_xk.inl, FIRST): 14 + 32
+    // requests per step, not 26 + 32
+    const bool first = a.p_in_zero && a.u_in == a.in;
+    if (fast == 2)
         return first ? pd_zmarch_xk_launch<T, NN, AN, 2, 3, 8, 2, 2, true, 10, true>(a, st) : pd_zmarch_xk_launch<T, NN, AN, 2, 3, 8, 2, 2, true, 10>(a, st);
     // relaxed float32: ONE instantiation per TV type serves both settings of `nonneg` -- the clip threshold is a kernel
     // argument (0 or -inf; "u < -inf" is never true, so the iterate passes through exactly as the code without the test
@@ -479,114 +580,76 @@ int pd_xk3_launch(const PdArgs &a, int variant, hipStream_t st)
     // builds keep their two instantiations: there the no-clip one is the faster by 3 %.
     PdArgs b = a;
     b.nn_thr = NN ? 0.0f : -__builtin_inff();
-    // the first launch of a prox (zero duals, Input = iterate) has its own instantiation: 14 + 32 requests per step, not 26 + 32
-    if (first) return pd_zmarch_xk_launch<T, true, AN, 1, 3, 8, 2, 2, true, 10, true>(b, st);
-    return pd_zmarch_xk_launch<T, true, AN, 1, 3, 8, 2, 2, true, 10>(b, st);
+    return first ? pd_zmarch_xk_launch<T, true, AN, 1, 3, 8, 2, 2, true, 10, true>(b, st) : pd_zmarch_xk_launch<T, true, AN, 1, 3, 8, 2, 2, true, 10>(b, st);
 }
 
-template <typename T, bool NN, bool AN>
-int pd_x2_launch(const PdArgs &a, int variant, hipStream_t st)
+// The only PD_TV launch site: `family` and `k` from pd_plan (or a slab entry point), the template arguments from the
+// flags and the variant.  `nd` tells the 2D from the 3D form of the two single-iteration families.
+static int pd_launch_one(const PdArgs &a, PdFamily family, int k, int nd, int methodTV, int nonneg, int half, int variant, hipStream_t st)
 {
+    if (a.out_end <= a.out_begin) return TOMO_OK;
+    const int fast = pd_arith(variant, half);
+    const int rc = pd_with_flags(half, nonneg, methodTV, [&](auto t, auto nn, auto an) -> int {
+        using T = typename decltype(t)::type;
+        constexpr bool NN = decltype(nn)::value, AN = decltype(an)::value;
+        switch (family) {
+        case PD_XK3:
+            return pd_xk3_launch<T, NN, AN>(a, fast, variant, st);
+        case PD_X2:  // 2 x 2 waves x 4 rows; the relaxed build has the registers for 2 x 4
+            return pd_with_fast(fast, [&](auto f) { return pd_zmarch_x2_launch<T, NN, AN, decltype(f)::value, 4, 2, decltype(f)::value == 1 ? 4 : 2>(a, st); });
+        case PD_ROWS2D:
+            return pd_with_fast(fast, [&](auto f) {
+                constexpr int F = decltype(f)::value;
+                if (k == 3) return pd_rows2d_launch<T, NN, AN, F, 3, 8>(a, st);
+                if (k == 2) return pd_rows2d_launch<T, NN, AN, F, 2, 8>(a, st);
+                return pd_rows2d_launch<T, NN, AN, F, 1, 8>(a, st);
+            });
+        case PD_SINGLE:
+            // measured on MI355X, 1024^3 f32 duals (profiles/archive/r1_pdtv_pmc.txt, docs/measurement_log.md): 4x2 waves x 8 rows,
+            // lockstep = 8.6 ms; 4x4 waves x 4 rows = 9.2 ms; 4x1 x 8 rows = 8.7 ms; unsynchronised waves (1x4, 4 rows) = 12.3-14 ms.
+            return pd_with_fast(fast, [&](auto f) {
+                constexpr int F = decltype(f)::value;
+                if (nd == 3) return pd_zmarch2_launch<T, 3, NN, AN, F, 8, true, 4, 2>(a, st);
 #if TOMO_DEV
-    if (variant == 3) return pd_zmarch_x2_launch<T, NN, AN, 1, 4, 2, 4>(a, st);
-    if (variant == 2 || variant == 21) return pd_zmarch_x2_launch<T, NN, AN, 0, 4, 2, 2>(a, st);
-#endif
-    if (variant == 22 || pd_default_is_exact<T>()) return pd_zmarch_x2_launch<T, NN, AN, 2, 4, 2, 2>(a, st);
-    return pd_zmarch_x2_launch<T, NN, AN, 1, 4, 2, 4>(a, st);
-}
-
-template <typename T>
-int pd_multi_launch(const PdArgs &a, int k, int methodTV, int nonneg, int variant, hipStream_t st)
-{
-#define PD_XK(NN, AN) (k == 3 ? pd_xk3_launch<T, NN, AN>(a, variant, st) : pd_x2_launch<T, NN, AN>(a, variant, st))
-    int rc;
-    if (!nonneg && !methodTV) rc = PD_XK(false, false);
-    else if (nonneg && !methodTV) rc = PD_XK(true, false);
-    else if (!nonneg && methodTV) rc = PD_XK(false, true);
-    else rc = PD_XK(true, true);
-#undef PD_XK
-    if (rc != TOMO_OK) return rc;
-    TOMO_LAUNCH_CHECK();
-    return TOMO_OK;
-}
-
-// 2D images: k (1, 2 or 3) iterations per launch, rows in registers (pd_rows2d.inl); the arithmetic follows the variant
-template <typename T, bool NN, bool AN, int FAST>
-int pd_rows2d_k(const PdArgs &a, int k, hipStream_t st)
-{
-    if (k == 3) return pd_rows2d_launch<T, NN, AN, FAST, 3, 8>(a, st);
-    if (k == 2) return pd_rows2d_launch<T, NN, AN, FAST, 2, 8>(a, st);
-    return pd_rows2d_launch<T, NN, AN, FAST, 1, 8>(a, st);
-}
-
-template <typename T>
-int pd_2d_launch(const PdArgs &a, int k, int methodTV, int nonneg, int variant, hipStream_t st)
-{
-    const bool exact = variant == 22 || pd_default_is_exact<T>();
-#if TOMO_DEV
-#define PD_2D_F(NN, AN) ((variant == 2 || variant == 21) ? pd_rows2d_k<T, NN, AN, 0>(a, k, st) : (variant == 3 || !exact) ? pd_rows2d_k<T, NN, AN, 1>(a, k, st) : pd_rows2d_k<T, NN, AN, 2>(a, k, st))
+                return pd_zmarch2_launch<T, 2, NN, AN, F, 8, true, 4, 2>(a, st);  // the 2D march of the dev library (no plan selects it)
 #else
-#define PD_2D_F(NN, AN) (exact ? pd_rows2d_k<T, NN, AN, 2>(a, k, st) : pd_rows2d_k<T, NN, AN, 1>(a, k, st))
+                return tomo_fail(TOMO_E_INVALID, "internal: 2D PD_TV runs pd_rows2d in this library");
 #endif
-    int rc;
-    if (!nonneg && !methodTV) rc = PD_2D_F(false, false);
-    else if (nonneg && !methodTV) rc = PD_2D_F(true, false);
-    else if (!nonneg && methodTV) rc = PD_2D_F(false, true);
-    else rc = PD_2D_F(true, true);
-#undef PD_2D_F
+            });
+        case PD_PERVOXEL: {
+#if TOMO_DEV
+            const dim3 grid(ceil_div(a.dx, 256), a.dy, a.out_end - a.out_begin);
+            if (nd == 3) pd_pervoxel_kernel<T, 3, NN, AN><<<grid, 256, 0, st>>>(a);
+            else pd_pervoxel_kernel<T, 2, NN, AN><<<grid, 256, 0, st>>>(a);
+            return TOMO_OK;
+#endif
+        }
+        }
+        return tomo_fail(TOMO_E_INVALID, "internal: PD_TV kernel family %d is not part of this library", (int)family);
+    });
     if (rc != TOMO_OK) return rc;
     TOMO_LAUNCH_CHECK();
     return TOMO_OK;
 }
 
-template <typename T, int ND, bool NONNEG, bool ANISO>
-int pd_launch(const PdArgs &a0, int variant, hipStream_t st)
+// pointers, plane range and scalars of a launch on arrays of [lo + nz + hi][dy][dx] that writes the local planes
+// [z_begin, z_end): lo / hi ghost planes below / above belong to the neighbouring slabs (0: that end is the volume's edge);
+// the whole volume is lo = hi = 0 and the range [0, nz)
+static PdArgs pd_args(const float *in, const float *u_in, float *u_out, const void *const *p_in, void *const *p_out, int dx,
+                      int dy, int nz, int lo, int hi, int z_begin, int z_end, float sigma, float tau, float lt, float theta)
 {
-    PdArgs a = a0;
-    const int nout = a.out_end - a.out_begin;
-    if (nout <= 0 || a.dx <= 0 || a.dy <= 0) return TOMO_OK;
-    // measured on MI355X, 1024^3 f32 duals (profiles/archive/r1_pdtv_pmc.txt, docs/measurement_log.md): 4x2 waves x 8 rows, lockstep = 8.6 ms;
-    // 4x4 waves x 4 rows = 9.2 ms; 4x1 x 8 rows = 8.7 ms; unsynchronised waves (1x4, 4 rows) = 12.3-14 ms.
-    // The arithmetic of an iteration never depends on how a run is cut into launches (slabs cut it differently): the
-    // single-iteration kernel follows the variant's arithmetic like the fused ones.
-    int rc;
-#if TOMO_DEV
-    if (variant == 1) {
-        dim3 grid(ceil_div(a.dx, 256), a.dy, nout);
-        pd_pervoxel_kernel<T, ND, NONNEG, ANISO><<<grid, 256, 0, st>>>(a);
-        TOMO_LAUNCH_CHECK();
-        return TOMO_OK;
-    }
-    if (variant == 2 || variant == 21) rc = pd_zmarch2_launch<T, ND, NONNEG, ANISO, 0, 8, true, 4, 2>(a, st);
-    else
-    if (variant == 3) rc = pd_zmarch2_launch<T, ND, NONNEG, ANISO, 1, 8, true, 4, 2>(a, st);
-    else
-#endif
-    if (variant == 22 || pd_default_is_exact<T>()) rc = pd_zmarch2_launch<T, ND, NONNEG, ANISO, 2, 8, true, 4, 2>(a, st);
-    else rc = pd_zmarch2_launch<T, ND, NONNEG, ANISO, 1, 8, true, 4, 2>(a, st);
-    if (rc != TOMO_OK) return rc;
-    TOMO_LAUNCH_CHECK();
-    return TOMO_OK;
-}
-
-template <typename T, int ND>
-int pd_dispatch(const PdArgs &a, int methodTV, int nonneg, int variant, hipStream_t st)
-{
-    if (!nonneg && !methodTV) return pd_launch<T, ND, false, false>(a, variant, st);
-    if (nonneg && !methodTV) return pd_launch<T, ND, true, false>(a, variant, st);
-    if (!nonneg && methodTV) return pd_launch<T, ND, false, true>(a, variant, st);
-    return pd_launch<T, ND, true, true>(a, variant, st);
-}
-
-int pd_iter(const PdArgs &a, int nd, int methodTV, int nonneg, int half, hipStream_t st)
-{
-    const int v = g_variant_pdtv;
-    if (nd == 3) return half ? pd_dispatch<__half, 3>(a, methodTV, nonneg, v, st) : pd_dispatch<float, 3>(a, methodTV, nonneg, v, st);
-#if TOMO_DEV
-    return half ? pd_dispatch<__half, 2>(a, methodTV, nonneg, v, st) : pd_dispatch<float, 2>(a, methodTV, nonneg, v, st);  // per-voxel 2D kernel (variant 1)
-#else
-    return tomo_fail(TOMO_E_INVALID, "internal: 2D PD_TV runs pd_rows2d in this library");
-#endif
+    PdArgs a;
+    a.in = in; a.u_in = u_in; a.u_out = u_out;
+    for (int c = 0; c < 3; ++c) { a.p_in[c] = p_in[c]; a.p_out[c] = p_out[c]; }
+    a.dx = dx; a.dy = dy;
+    a.planes = nz + lo + hi;
+    a.out_begin = lo + z_begin;
+    a.out_end = lo + z_end;
+    a.first_is_edge = lo ? 0 : 1;
+    a.last_is_edge = hi ? 0 : 1;
+    a.sigma = sigma; a.tau = tau; a.lt = lt; a.theta = theta;
+    a.zchunk = z_end - z_begin;
+    return a;
 }
 
 // ------------------------------------------------------------------------------------------ ROF
@@ -679,44 +742,54 @@ __global__ __launch_bounds__(256) void rof_pervoxel_kernel(RofArgs a)
 //              of ~1e4 on noise-dominated data, where one-ulp differences grow to 2.5e-5 .. 4.5e-5 after 60 iterations
 //              (profiles/archive/r3_rof_variants.txt), beyond the 1e-5 parity bar;  4 = refined v_rsq / v_rcp (no better than 3);
 //              1 = per-voxel kernel (independent implementation)
-template <int ND, bool HALF>
-int rof_zmarch_dispatch(const RofArgs &a, int variant, hipStream_t st)
+// The only ROF_TV launch site.
+static int rof_launch_one(const RofArgs &a, int nd, int half, int variant, hipStream_t st)
 {
-    int rc;
+    if (a.out_end <= a.out_begin) return TOMO_OK;
+    auto launch = [&](auto ndc, auto hc) -> int {
+        constexpr int ND = decltype(ndc)::value;
+        constexpr bool HALF = decltype(hc)::value;
 #if TOMO_DEV
-    if (variant == 4) rc = rof_zmarch_launch<ND, HALF, 2, 8, 2, 2>(a, st);
-    else if (variant == 3) rc = rof_zmarch_launch<ND, HALF, 1, 8, 2, 2>(a, st);
-    else if (variant == 2) rc = rof_zmarch_launch<ND, HALF, 0, 8, 2, 2>(a, st);
-    else
+        if (variant == 1) {
+            const dim3 grid(ceil_div(a.dx, 256), a.dy, a.out_end - a.out_begin);
+            rof_pervoxel_kernel<ND, HALF><<<grid, 256, 0, st>>>(a);
+            return TOMO_OK;
+        }
+        if (variant == 4) return rof_zmarch_launch<ND, HALF, 2, 8, 2, 2>(a, st);
+        if (variant == 3) return rof_zmarch_launch<ND, HALF, 1, 8, 2, 2>(a, st);
+        if (variant == 2) return rof_zmarch_launch<ND, HALF, 0, 8, 2, 2>(a, st);
 #endif
-    rc = rof_zmarch_launch<ND, HALF, 3, 8, 2, 2>(a, st);
-    (void)variant;
+        (void)variant;
+        return rof_zmarch_launch<ND, HALF, 3, 8, 2, 2>(a, st);
+    };
+    auto dual = [&](auto ndc) { return half ? launch(ndc, std::true_type{}) : launch(ndc, std::false_type{}); };
+    const int rc = nd == 3 ? dual(int_c<3>{}) : dual(int_c<2>{});
     if (rc != TOMO_OK) return rc;
     TOMO_LAUNCH_CHECK();
     return TOMO_OK;
 }
 
-int rof_iter(const RofArgs &a, int nd, int half, hipStream_t st)
+// the ROF_TV counterpart of pd_args
+static RofArgs rof_args(const float *in, const float *u_in, float *u_out, int dx, int dy, int nz, int lo, int hi, int z_begin,
+                        int z_end, float lambda, float tau)
 {
-    const int nout = a.out_end - a.out_begin;
-    if (nout <= 0) return TOMO_OK;
-#if TOMO_DEV
-    if (g_variant_roftv == 1) {  // per-voxel kernel
-        dim3 grid(ceil_div(a.dx, 256), a.dy, nout);
-        if (nd == 3) {
-            if (half) rof_pervoxel_kernel<3, true><<<grid, 256, 0, st>>>(a);
-            else rof_pervoxel_kernel<3, false><<<grid, 256, 0, st>>>(a);
-        } else {
-            if (half) rof_pervoxel_kernel<2, true><<<grid, 256, 0, st>>>(a);
-            else rof_pervoxel_kernel<2, false><<<grid, 256, 0, st>>>(a);
-        }
-        TOMO_LAUNCH_CHECK();
-        return TOMO_OK;
-    }
-#endif
-    const int v = g_variant_roftv;
-    if (nd == 3) return half ? rof_zmarch_dispatch<3, true>(a, v, st) : rof_zmarch_dispatch<3, false>(a, v, st);
-    return half ? rof_zmarch_dispatch<2, true>(a, v, st) : rof_zmarch_dispatch<2, false>(a, v, st);
+    RofArgs a;
+    a.in = in; a.u_in = u_in; a.u_out = u_out;
+    a.dx = dx; a.dy = dy;
+    a.planes = nz + lo + hi;
+    a.out_begin = lo + z_begin;
+    a.out_end = lo + z_end;
+    a.first_is_edge = lo ? 0 : 1;
+    a.last_is_edge = hi ? 0 : 1;
+    a.lambda = lambda; a.tau = tau;
+    return a;
+}
+
+// a raw buffer descriptor of the z-march kernels addresses one plane
+static int tv_plane_fits(int dx, int dy)
+{
+    TOMO_REQUIRE((size_t)dx * (size_t)dy < ((size_t)1 << 29), "a plane of %d x %d exceeds the 2 GiB a buffer descriptor of the TV kernels addresses", dx, dy);
+    return TOMO_OK;
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -751,6 +824,17 @@ extern "C" int tomo_pdtv_iters_per_launch(int half)
 {
     (void)half;
     return pd_iters_per_launch(g_variant_pdtv);
+}
+
+extern "C" int tomo_pdtv_launch_plan(int iters, int nd, int dz, int *k_out, int capacity)
+{
+    if ((nd != 2 && nd != 3) || (nd == 3 && dz < 1)) {
+        (void)tomo_fail(TOMO_E_INVALID, "tomo_pdtv_launch_plan: nd must be 2 or 3, dz >= 1");
+        return -1;
+    }
+    const std::vector<PdLaunch> plan = pd_plan(nd, dz, iters, g_variant_pdtv);
+    for (int i = 0; k_out && i < (int)plan.size() && i < capacity; ++i) k_out[i] = plan[i].k;
+    return (int)plan.size();
 }
 
 // ---- early stopping (tomo_pdtv_tol / tomo_roftv_tol; the rule is stated in include/tomo_mi355x.h): the iterate is compared
@@ -791,6 +875,14 @@ static int tol_check(TolState &t, int n, int iters, const float *cur, const floa
     return TOMO_OK;
 }
 
+// what a *_tol entry point reports back
+static int tol_finish(int rc, const TolState &t, int *iters_done, double *last_rel_change)
+{
+    if (rc == TOMO_OK && iters_done) *iters_done = t.done;
+    if (rc == TOMO_OK && last_rel_change) *last_rel_change = t.last;
+    return rc;
+}
+
 static int pdtv_run(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
                     float sigma, float tau, float lt, float theta, int iters, int methodTV, int nonneg,
                     int half, TolState &ts, void *stream)
@@ -799,7 +891,7 @@ static int pdtv_run(int device, const float *in_dev, float *out_dev, int dx, int
     TOMO_REQUIRE(nd == 2 || nd == 3, "2D or 3D arrays must be provided only");
     if (nd == 2) dz = 1;
     TOMO_REQUIRE(dx > 0 && dy > 0 && dz > 0 && iters >= 0, "bad PD_TV dimensions / iterations");
-    TOMO_REQUIRE((size_t)dx * (size_t)dy < ((size_t)1 << 29), "a plane of %d x %d exceeds the 2 GiB a buffer descriptor of the TV kernels addresses", dx, dy);
+    if (int rc = tv_plane_fits(dx, dy)) return rc;
     TOMO_REQUIRE(in_dev && out_dev, "NULL data pointer");
     TOMO_ON_DEVICE(device);
     hipStream_t st = as_stream(stream);
@@ -825,54 +917,31 @@ static int pdtv_run(int device, const float *in_dev, float *out_dev, int dx, int
         for (int c = 0; c < nd; ++c) { P[b][c] = cur; cur += pb + skew; }
     // U_arrays[0] = data.copy() is not materialised: iteration 0 reads the caller's buffer directly;
     // duals start at zero (regularisersCuPy.py:221-223); every U / P output buffer is fully overwritten
-    // (the multi-iteration kernel pd_zmarch_xk takes "the duals are zero" as a flag instead of reading a zeroed array)
-    // 3D volumes run several iterations per launch (K = 3 or 2, see pd_multi_launch) while that many remain, then
-    // single iterations; variant 1 keeps one iteration per launch (independent implementation)
+    // (the families that take "the duals are zero" as a flag do not read a zeroed array)
     const int v = g_variant_pdtv;
-    // a fused launch of k iterations marches k planes ahead of its output: volumes thinner than that take fewer per launch.
-    // 2D images (round 4): k iterations per launch with the rows of a tile in registers (pd_rows2d.inl), any k <= 3
-    const bool rows2d = (nd == 2 && v != 1);
-    const int kmax = nd == 3 ? std::min(pd_iters_per_launch(v), dz) : pd_iters_per_launch(v);
-    // cut `remaining` into launches of kmax / 2 / 1 iterations with as few single-iteration launches as possible
-    // (4 = 2 + 2, 7 = 3 + 2 + 2: a single iteration costs 1.7x an iteration of a fused launch)
-    auto step_of = [&](int remaining) {
-        if (kmax >= 3 && remaining >= 3 && remaining != 4) return 3;
-        return (remaining >= 2 && kmax >= 2) ? 2 : 1;
-    };
-    int launches = 0;
-    for (int it = 0; it < iters;) launches += 1, it += step_of(iters - it);
-    tomo_prof_scope prof(PROF_PDTV, st, launches);
+    const std::vector<PdLaunch> plan = pd_plan(nd, dz, iters, v);
+    tomo_prof_scope prof(PROF_PDTV, st, (int)plan.size());
     int cset = 0;  // buffer set holding the current iterate (iteration 0 reads the caller's buffer instead of U[0])
-    for (int it = 0; it < iters;) {
-        const int step = step_of(iters - it);
-        const bool pair = step >= 2;
+    int it = 0;
+    for (const PdLaunch &l : plan) {
         const int ib = cset, ob = cset ^ 1;
-        PdArgs a;
-        a.in = in_dev;
-        a.u_in = (it == 0) ? in_dev : U[ib];
         // the last launch writes straight into the caller's output buffer (unless it aliases the input)
-        const bool last = (it + step == iters);
-        a.u_out = (last && out_dev != in_dev) ? out_dev : U[ob];
-        for (int c = 0; c < 3; ++c) { a.p_in[c] = P[ib][c]; a.p_out[c] = P[ob][c]; }
-        const bool flags = (step == 3 && nd == 3) || rows2d;  // launches that understand the two flags below
+        const bool last = (it + l.k == iters);
+        PdArgs a = pd_args(in_dev, it == 0 ? in_dev : U[ib], (last && out_dev != in_dev) ? out_dev : U[ob], P[ib], P[ob], dx, dy,
+                           dz, 0, 0, 0, dz, sigma, tau, lt, theta);
         if (it == 0) {
-            if (flags) a.p_in_zero = 1;
+            if (l.flags) a.p_in_zero = 1;
             else for (int c = 0; c < nd; ++c) TOMO_HIP(hipMemsetAsync(P[ib][c], 0, pb, st));
         }
-        if (last && flags) a.p_out_skip = 1;
-        a.dx = dx; a.dy = dy; a.planes = dz; a.out_begin = 0; a.out_end = dz;
-        a.first_is_edge = 1; a.last_is_edge = 1;
-        a.sigma = sigma; a.tau = tau; a.lt = lt; a.theta = theta; a.zchunk = dz;
+        if (last && l.flags) a.p_out_skip = 1;
 #if TOMO_DEV
         a.probe = g_probe;
 #endif
-        if (rows2d) rc = half ? pd_2d_launch<__half>(a, step, methodTV, nonneg, v, st) : pd_2d_launch<float>(a, step, methodTV, nonneg, v, st);
-        else if (pair) rc = half ? pd_multi_launch<__half>(a, step, methodTV, nonneg, v, st) : pd_multi_launch<float>(a, step, methodTV, nonneg, v, st);
-        else rc = pd_iter(a, nd, methodTV, nonneg, half, st);
+        rc = pd_launch_one(a, l.family, l.k, nd, methodTV, nonneg, half, v, st);
         if (rc != TOMO_OK) return rc;
         cset = ob;
-        it += step;
-        // (every check point is a launch boundary of step_of: a multiple of 6 with at least 3 iterations left)
+        it += l.k;
+        // (every check point is a launch boundary of pd_plan: a multiple of 6 with at least 3 iterations left)
         bool stop = false;
         rc = tol_check(ts, it, iters, U[cset], in_dev, nvox, st, &stop);
         if (rc != TOMO_OK) return rc;
@@ -901,10 +970,7 @@ extern "C" int tomo_pdtv_tol(int device, const float *in_dev, float *out_dev, in
     TOMO_REQUIRE(tol_valid(tol), "the tolerance must be a finite number >= 0");
     TolState ts;
     ts.tol = tol;
-    const int rc = pdtv_run(device, in_dev, out_dev, dx, dy, dz, nd, sigma, tau, lt, theta, iters, methodTV, nonneg, half, ts, stream);
-    if (rc == TOMO_OK && iters_done) *iters_done = ts.done;
-    if (rc == TOMO_OK && last_rel_change) *last_rel_change = ts.last;
-    return rc;
+    return tol_finish(pdtv_run(device, in_dev, out_dev, dx, dy, dz, nd, sigma, tau, lt, theta, iters, methodTV, nonneg, half, ts, stream), ts, iters_done, last_rel_change);
 }
 
 extern "C" int tomo_pdtv_iter_slab(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
@@ -913,38 +979,13 @@ extern "C" int tomo_pdtv_iter_slab(int device, const float *in_dev, const float 
                                    int methodTV, int nonneg, int half, void *stream)
 {
     TOMO_REQUIRE(device >= 0 && dx > 0 && dy > 0 && nz_local > 0, "bad slab arguments");
-    TOMO_REQUIRE((size_t)dx * (size_t)dy < ((size_t)1 << 29), "a plane of %d x %d exceeds the 2 GiB a buffer descriptor of the TV kernels addresses", dx, dy);
+    if (int rc = tv_plane_fits(dx, dy)) return rc;
     TOMO_ON_DEVICE(device);
-    PdArgs a;
-    a.in = in_dev; a.u_in = u_in_dev; a.u_out = u_out_dev;
-    for (int c = 0; c < 3; ++c) { a.p_in[c] = p_in_dev[c]; a.p_out[c] = p_out_dev[c]; }
-    a.dx = dx; a.dy = dy;
-    a.planes = nz_local + (has_lo ? 1 : 0) + (has_hi ? 1 : 0);
-    a.out_begin = has_lo ? 1 : 0;
-    a.out_end = a.out_begin + nz_local;
-    a.first_is_edge = has_lo ? 0 : 1;
-    a.last_is_edge = has_hi ? 0 : 1;
-    a.sigma = sigma; a.tau = tau; a.lt = lt; a.theta = theta; a.zchunk = nz_local;
+    const PdArgs a = pd_args(in_dev, u_in_dev, u_out_dev, p_in_dev, p_out_dev, dx, dy, nz_local, has_lo ? 1 : 0, has_hi ? 1 : 0, 0,
+                             nz_local, sigma, tau, lt, theta);
     tomo_prof_scope prof(PROF_PDTV, as_stream(stream), 1);
-    return pd_iter(a, 3, methodTV, nonneg, half, as_stream(stream));
-}
-
-extern "C" int tomo_pdtv_pair_slab(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
-                                   const void *p_in_dev[3], void *p_out_dev[3], int dx, int dy, int nz_local,
-                                   int lo_planes, int hi_planes, float sigma, float tau, float lt, float theta,
-                                   int methodTV, int nonneg, int half, void *stream)
-{
-    return tomo_pdtv_multi_slab_range(device, in_dev, u_in_dev, u_out_dev, p_in_dev, p_out_dev, dx, dy, nz_local, lo_planes,
-                                      hi_planes, 0, nz_local, 2, sigma, tau, lt, theta, methodTV, nonneg, half, stream);
-}
-
-extern "C" int tomo_pdtv_pair_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
-                                         const void *p_in_dev[3], void *p_out_dev[3], int dx, int dy, int nz_local,
-                                         int lo_planes, int hi_planes, int z_begin, int z_end, float sigma, float tau,
-                                         float lt, float theta, int methodTV, int nonneg, int half, void *stream)
-{
-    return tomo_pdtv_multi_slab_range(device, in_dev, u_in_dev, u_out_dev, p_in_dev, p_out_dev, dx, dy, nz_local, lo_planes,
-                                      hi_planes, z_begin, z_end, 2, sigma, tau, lt, theta, methodTV, nonneg, half, stream);
+    const int v = g_variant_pdtv;
+    return pd_launch_one(a, pd_single_family(v), 1, 3, methodTV, nonneg, half, v, as_stream(stream));
 }
 
 extern "C" int tomo_pdtv_multi_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
@@ -954,29 +995,18 @@ extern "C" int tomo_pdtv_multi_slab_range(int device, const float *in_dev, const
 {
     TOMO_REQUIRE(k == 2 || k == 3, "a fused PD_TV launch carries 2 or 3 iterations (got %d)", k);
     TOMO_REQUIRE(device >= 0 && dx > 0 && dy > 0 && nz_local >= k, "bad slab arguments (a slab needs >= %d slices)", k);
-    TOMO_REQUIRE((size_t)dx * (size_t)dy < ((size_t)1 << 29), "a plane of %d x %d exceeds the 2 GiB a buffer descriptor of the TV kernels addresses", dx, dy);
+    if (int rc = tv_plane_fits(dx, dy)) return rc;
     TOMO_REQUIRE(z_begin >= 0 && z_begin <= z_end && z_end <= nz_local, "bad output plane range [%d, %d)", z_begin, z_end);
     if (z_begin == z_end) return TOMO_OK;
     TOMO_REQUIRE((lo_planes == 0 || lo_planes >= k) && (hi_planes == 0 || hi_planes >= k) && lo_planes <= 3 && hi_planes <= 3,
                  "a %d-iteration slab launch needs 0 or >= %d (at most 3) ghost planes on either side", k, k);
     TOMO_ON_DEVICE(device);
-    PdArgs a;
-    a.in = in_dev; a.u_in = u_in_dev; a.u_out = u_out_dev;
-    for (int c = 0; c < 3; ++c) { a.p_in[c] = p_in_dev[c]; a.p_out[c] = p_out_dev[c]; }
-    a.dx = dx; a.dy = dy;
-    a.planes = nz_local + lo_planes + hi_planes;
-    a.out_begin = lo_planes + z_begin;
-    a.out_end = lo_planes + z_end;
-    a.first_is_edge = lo_planes ? 0 : 1;
-    a.last_is_edge = hi_planes ? 0 : 1;
-    a.sigma = sigma; a.tau = tau; a.lt = lt; a.theta = theta; a.zchunk = z_end - z_begin;
+    const PdArgs a = pd_args(in_dev, u_in_dev, u_out_dev, p_in_dev, p_out_dev, dx, dy, nz_local, lo_planes, hi_planes, z_begin,
+                             z_end, sigma, tau, lt, theta);
     hipStream_t st = as_stream(stream);
     tomo_prof_scope prof(PROF_PDTV, st, 1);
-    // fused slab launches follow the variant's arithmetic; the dev variants without a fused form of their own (1: per-voxel,
-    // 2: two iterations per launch) run the compiler-IEEE build of the tiling asked for
-    int v = g_variant_pdtv;
-    if (v == 1 || v == 2) v = (k == 3) ? 21 : 2;
-    return half ? pd_multi_launch<__half>(a, k, methodTV, nonneg, v, st) : pd_multi_launch<float>(a, k, methodTV, nonneg, v, st);
+    // the tiling is the caller's choice, the arithmetic the variant's (pd_arith)
+    return pd_launch_one(a, k == 3 ? PD_XK3 : PD_X2, k, 3, methodTV, nonneg, half, g_variant_pdtv, st);
 }
 
 static int roftv_run(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
@@ -987,7 +1017,7 @@ static int roftv_run(int device, const float *in_dev, float *out_dev, int dx, in
     if (nd == 2) dz = 1;
     TOMO_REQUIRE(dx >= 2 && dy >= 2 && (nd == 2 || dz >= 2) && iters >= 0,
                  "ROF_TV needs every dimension >= 2 (reflecting boundary)");
-    TOMO_REQUIRE((size_t)dx * (size_t)dy < ((size_t)1 << 29), "a plane of %d x %d exceeds the 2 GiB a buffer descriptor of the TV kernels addresses", dx, dy);
+    if (int rc = tv_plane_fits(dx, dy)) return rc;
     TOMO_REQUIRE(in_dev && out_dev, "NULL data pointer");
     TOMO_ON_DEVICE(device);
     hipStream_t st = as_stream(stream);
@@ -1005,14 +1035,10 @@ static int roftv_run(int device, const float *in_dev, float *out_dev, int dx, in
     float *U[2] = {(float *)base, (float *)((char *)base + ub)};
     tomo_prof_scope prof(PROF_ROFTV, st, iters);
     for (int it = 0; it < iters; ++it) {
-        RofArgs a;
-        a.in = in_dev;
-        a.u_in = (it == 0) ? in_dev : U[it & 1];  // iteration 0 reads the caller's data directly
-        a.u_out = (it == iters - 1 && out_dev != in_dev) ? out_dev : U[(it + 1) & 1];
-        a.dx = dx; a.dy = dy; a.planes = dz; a.out_begin = 0; a.out_end = dz;
-        a.first_is_edge = 1; a.last_is_edge = 1;
-        a.lambda = lambda; a.tau = tau;
-        rc = rof_iter(a, nd, half, st);
+        // iteration 0 reads the caller's data directly, the last one writes the caller's output (unless it aliases the input)
+        const RofArgs a = rof_args(in_dev, it == 0 ? in_dev : U[it & 1], (it == iters - 1 && out_dev != in_dev) ? out_dev : U[(it + 1) & 1],
+                                   dx, dy, dz, 0, 0, 0, dz, lambda, tau);
+        rc = rof_launch_one(a, nd, half, g_variant_roftv, st);
         if (rc != TOMO_OK) return rc;
         bool stop = false;
         rc = tol_check(ts, it + 1, iters, U[(it + 1) & 1], in_dev, nvox, st, &stop);
@@ -1041,18 +1067,7 @@ extern "C" int tomo_roftv_tol(int device, const float *in_dev, float *out_dev, i
     TOMO_REQUIRE(tol_valid(tol), "the tolerance must be a finite number >= 0");
     TolState ts;
     ts.tol = tol;
-    const int rc = roftv_run(device, in_dev, out_dev, dx, dy, dz, nd, lambda, tau, iters, half, ts, stream);
-    if (rc == TOMO_OK && iters_done) *iters_done = ts.done;
-    if (rc == TOMO_OK && last_rel_change) *last_rel_change = ts.last;
-    return rc;
-}
-
-extern "C" int tomo_roftv_iter_slab(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
-                                    int dx, int dy, int nz_local, int lo_planes, int hi_planes,
-                                    float lambda, float tau, int half, void *stream)
-{
-    return tomo_roftv_iter_slab_range(device, in_dev, u_in_dev, u_out_dev, dx, dy, nz_local, lo_planes, hi_planes, 0,
-                                      nz_local, lambda, tau, half, stream);
+    return tol_finish(roftv_run(device, in_dev, out_dev, dx, dy, dz, nd, lambda, tau, iters, half, ts, stream), ts, iters_done, last_rel_change);
 }
 
 extern "C" int tomo_roftv_iter_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
@@ -1060,20 +1075,12 @@ extern "C" int tomo_roftv_iter_slab_range(int device, const float *in_dev, const
                                           int z_end, float lambda, float tau, int half, void *stream)
 {
     TOMO_REQUIRE(device >= 0 && dx >= 2 && dy >= 2 && nz_local > 0, "bad slab arguments");
-    TOMO_REQUIRE((size_t)dx * (size_t)dy < ((size_t)1 << 29), "a plane of %d x %d exceeds the 2 GiB a buffer descriptor of the TV kernels addresses", dx, dy);
+    if (int rc = tv_plane_fits(dx, dy)) return rc;
     TOMO_REQUIRE(z_begin >= 0 && z_begin <= z_end && z_end <= nz_local, "bad output plane range [%d, %d)", z_begin, z_end);
     if (z_begin == z_end) return TOMO_OK;
     TOMO_REQUIRE((lo_planes == 0 || lo_planes == 2) && (hi_planes == 0 || hi_planes == 1),
                  "ROF slab needs 0 or 2 ghost planes below and 0 or 1 above");
     TOMO_ON_DEVICE(device);
-    RofArgs a;
-    a.in = in_dev; a.u_in = u_in_dev; a.u_out = u_out_dev;
-    a.dx = dx; a.dy = dy;
-    a.planes = nz_local + lo_planes + hi_planes;
-    a.out_begin = lo_planes + z_begin;
-    a.out_end = lo_planes + z_end;
-    a.first_is_edge = lo_planes ? 0 : 1;
-    a.last_is_edge = hi_planes ? 0 : 1;
-    a.lambda = lambda; a.tau = tau;
-    return rof_iter(a, 3, half, as_stream(stream));
+    const RofArgs a = rof_args(in_dev, u_in_dev, u_out_dev, dx, dy, nz_local, lo_planes, hi_planes, z_begin, z_end, lambda, tau);
+    return rof_launch_one(a, 3, half, g_variant_roftv, as_stream(stream));
 }

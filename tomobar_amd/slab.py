@@ -327,10 +327,10 @@ GHOST = 3  # ghost planes below / above an interior boundary: as deep as the lon
 
 
 def pd_launch_plan(iterations: int, half: bool, kmax: Optional[int] = None):
-    """How tomo_pdtv cuts `iterations` into fused launches (csrc/tv_kernels.hip: step_of): `kmax` iterations per launch
+    """How tomo_pdtv cuts `iterations` into fused launches (csrc/tv_kernels.hip: pd_plan): `kmax` iterations per launch
     (asked of the library: 3 in the shipped build, 2 under the exact-rounding test variant), as few single-iteration
     launches as possible (4 = 2 + 2).  The slab driver uses the same plan, so a slab run is launch for launch the
-    whole-volume run."""
+    whole-volume run; tests/test_host_logic.py compares this function with the library's tomo_pdtv_launch_plan."""
     if kmax is None:
         kmax = _hip_pd_kmax(half)
     kmax = max(1, min(int(kmax), GHOST))
@@ -398,18 +398,12 @@ class PdSlab:
         self.multi_range(k, sigma, tau, lt, theta, methodTV, nonneg, 0, self.nzl)
         self.flip()
 
-    def pair(self, sigma, tau, lt, theta, methodTV, nonneg):
-        self.multi(2, sigma, tau, lt, theta, methodTV, nonneg)
-
     def multi_range(self, k, sigma, tau, lt, theta, methodTV, nonneg, z_begin, z_end):
         """k iterations for the local output planes [z_begin, z_end) only (buffer set cur -> cur ^ 1, no flip)."""
         i, o = self.cur, self.cur ^ 1
         if z_end > z_begin:
             self.pair_fn(self.inp, self._u_in(), self.U[o], self.P[i], self.P[o], self.dx, self.dy, self.nzl, self.lo,
                          self.hi, sigma, tau, lt, theta, methodTV, nonneg, self.half, (z_begin, z_end), k)
-
-    def pair_range(self, sigma, tau, lt, theta, methodTV, nonneg, z_begin, z_end):
-        self.multi_range(2, sigma, tau, lt, theta, methodTV, nonneg, z_begin, z_end)
 
     def _u_in(self) -> torch.Tensor:
         return self.inp if self.first else self.U[self.cur]

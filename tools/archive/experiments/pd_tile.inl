@@ -1,6 +1,6 @@
 // NOT part of the build.  Round-2 experiment (PD_TV workgroup tile with LDS row halos), measured slower than the per-wave-halo
 // kernels in every shape (docs/kernels/pd_tv.md, profiles/archive/r2_b_pdtv_tile_vs_x2_pmc.txt).  To rebuild it: include this file in
-// tv_kernels.hip after pd_zmarch2.inl and dispatch pd_tile_launch<T, NN, AN, FAST, 4, 1, 8> from pd_multi_launch.
+// tv_kernels.hip after pd_zmarch2.inl and dispatch pd_tile_launch<T, NN, AN, FAST, 4, 1, 8> from pd_launch_one (a PdFamily of its own, chosen in pd_plan).
 // PD_TV, TWO Chambolle-Pock iterations per pass through HBM, workgroup TILE with the row halos shared through LDS
 // (3D only; default).  Included inside the anonymous namespace of tv_kernels.hip (uses PdArgs, DualIO, pd_dual, pd_primal).
 //

@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* raised whenever an entry point is added or a signature changes (tomobar_amd/_lib.py checks it at load) */
-#define TOMO_ABI_VERSION 8
+#define TOMO_ABI_VERSION 9
 
 enum {
     TOMO_OK = 0,
@@ -298,10 +298,26 @@ int tomo_pdtv_tol(int device, const float *in_dev, float *out_dev, int dx, int d
 int tomo_roftv_tol(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
                    float lambda, float tau, int iters, int half, double tol, int *iters_done,
                    double *last_rel_change, void *stream);
+/* Second-order total generalised variation (TGV): argmin_u 1/2 |u - f|^2 + lambda min_v (alpha1 |grad u - v|_1 + alpha0 |E v|_1)
+ * by Chambolle-Pock iterations.  No reference counterpart in this reference version (it took TGV from the regularisation
+ * toolkit it no longer depends on; tomobar/supp/dicts.py:176-178 still names PD_LipschitzConstant "TGV specific"): the
+ * algorithm is stated in docs/kernels/tgv.md and restated in numpy by tests/_tgv_oracle.py -- formula-level parity,
+ * unpinned; the float32 result equals that restatement bit for bit.
+ *   dims as for tomo_pdtv (a dimension of 1 is valid).  lambda, alpha1, alpha0, tau, sigma are float32 scalars computed by
+ *   the caller (TGV_cupy: tau = sigma = 1 / sqrt(PD_LipschitzConstant)).  U is iterated in out_dev, which therefore must not
+ *   alias in_dev (TOMO_E_INVALID, as are nd outside {2, 3}, a dimension below 1, a non-positive lambda / alpha1 / alpha0 /
+ *   step size, negative iters and a negative or non-finite tol).  iters = 0 copies the input.  Two launches per iteration.
+ *   tol, *iters_done, *last_rel_change: the early-stopping rule above (tol = 0: off); a stopped run leaves exactly what
+ *   iters = n returns. */
+int tomo_tgv(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+             float lambda, float alpha1, float alpha0, float tau, float sigma, int iters,
+             double tol, int *iters_done, double *last_rel_change, void *stream);
 /* scratch bytes the TV drivers hold for a given problem (informational; a tolerance adds one float volume, see above) and
- * arena release */
+ * arena release.  tomo_tgv_scratch_bytes: 16 (nd = 3: U-bar, V, V-bar, P, six Q) or 10 (nd = 2) float arrays, each rounded
+ * up to 256 bytes and followed by the 69888-byte array skew. */
 size_t tomo_pdtv_scratch_bytes(int dx, int dy, int dz, int nd, int half);
 size_t tomo_roftv_scratch_bytes(int dx, int dy, int dz, int nd);
+size_t tomo_tgv_scratch_bytes(int dx, int dy, int dz, int nd);
 int tomo_release_scratch(int device);
 /* Placement of the TV scratch arenas (no reference counterpart: CuPy's memory pool hands out whatever block comes next).
  * On MI355X the speed of the plane-marching TV kernels depends on where in HBM their arrays lie (PD_TV launch at 1024^3:

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtomo_mi355x.so")
 
 OK, E_INVALID, E_RUNTIME, E_NOMEM, E_NODEVICE = 0, 1, 2, 3, 4
-ABI_VERSION = 8  # TOMO_ABI_VERSION of include/tomo_mi355x.h (tests/test_host_logic.py keeps the two in step)
+ABI_VERSION = 9  # TOMO_ABI_VERSION of include/tomo_mi355x.h (tests/test_host_logic.py keeps the two in step)
 FLAG_LERP8 = 1
 FID = {"LS": 0, "PWLS": 1, "KL": 2, "RATIO": 3}
 ROBUST = {None: 0, "huber": 1, "studentst": 2}   # TOMO_ROBUST_* of include/tomo_mi355x.h
@@ -91,6 +91,8 @@ SIGNATURES = {
     "tomo_roftv_tol": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
     "tomo_pdtv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "tomo_roftv_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_tgv": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
+    "tomo_tgv_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_release_scratch": (_i, [_i]),
     "tomo_reserve_scratch": (_i, [_i, _sz, _vp]),
     "tomo_set_placement_tries": (_i, [_i]),

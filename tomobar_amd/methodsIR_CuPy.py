@@ -9,7 +9,7 @@ Here a FISTA-OS sub-iteration is
     residual  = forward-projection kernel with the (w *)(Ax - b) / KL epilogue, subset gathered by angle index
     gradient  = back-projection kernel whose epilogue applies  X = P+(X_t - g/L)  (and, when no proximal
                 operator sits in between, the momentum update as well)
-    prox      = ``tomo_pdtv`` / ``tomo_roftv``: one fused kernel per inner iteration
+    prox      = ``tomo_pdtv`` / ``tomo_roftv``: one fused kernel per inner iteration (``tomo_tgv``: two)
     momentum  = one streaming kernel
 
 on persistent buffers, all asynchronous on the current stream.  Scalar bookkeeping (t-sequence, step sizes) is done
@@ -27,7 +27,7 @@ from numpy import float32
 from . import ops
 from .convergence import check_tolerance, relative_change
 from .projector import HipTools3D, geom_size
-from .regularisersCuPy import last_prox, prox_regul, reserve_prox_scratch
+from .regularisersCuPy import check_prox_available, last_prox, prox_regul, reserve_prox_scratch
 from .supp.dicts import dicts_check
 from .supp.suppTools import _apply_horiz_detector_padding, check_kwargs, perform_recon_crop
 
@@ -159,6 +159,7 @@ class RecToolsIRCuPy:
     def _prepare_data(self, _data_, _algorithm_, _regularisation_, method_run):
         self._given = _data_.get("projection_data") if isinstance(_data_, dict) else None  # decides the array library of the result
         d, a, r = dicts_check(self, _data_, _algorithm_, _regularisation_, method_run=method_run)
+        check_prox_available(self, self.Atools.vol_shape(), r)   # before any projector call
         d["projection_data"] = _apply_horiz_detector_padding(d["projection_data"], self.Atools.detectors_x_pad, True)
         expect = self.Atools.sino_shape(None)
         if tuple(d["projection_data"].shape) != expect:
@@ -223,7 +224,7 @@ class RecToolsIRCuPy:
     # ------------------------------------------------------------------ FISTA
     def FISTA(self, _data_: dict, _algorithm_: Union[dict, None] = None,
               _regularisation_: Union[dict, None] = None) -> torch.Tensor:
-        """Fast Iterative Shrinkage-Thresholding Algorithm with optional ordered subsets and ROF_TV / PD_TV proximal
+        """Fast Iterative Shrinkage-Thresholding Algorithm with optional ordered subsets and ROF_TV / PD_TV / TGV proximal
         regularisation (reference: methodsIR_CuPy.py:401-484).  Returns the float32 volume ``[detY, N, N]``."""
         (d, a, r, x0, w, use_os) = self.__common_initialisation(_data_, _algorithm_, _regularisation_, "FISTA")
         A = self.Atools

@@ -255,6 +255,19 @@ def roftv_tol(data, out, lam, tau, iterations, half, tolerance):
     return out, int(done.value), float(last.value)
 
 
+def tgv(data, out, lam, alpha1, alpha0, tau, sigma, iterations, tolerance=0.0):
+    """Second-order TGV prox (tomo_tgv; the algorithm: docs/kernels/tgv.md): `iterations` Chambolle-Pock iterations of
+    `data` into `out` (a different array: U is iterated there).  Returns (out, iterations_done, rel_change) -- the last
+    relative change the stopping rule evaluated, NaN if none (tolerance 0 = off)."""
+    dx, dy, dz, nd = _tv_dims(data)
+    done, last = C.c_int(0), C.c_double(float("nan"))
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_tgv(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, float(lam), float(alpha1),
+                                 float(alpha0), float(tau), float(sigma), int(iterations), float(tolerance),
+                                 C.byref(done), C.byref(last), stream_ptr(data)))
+    return out, int(done.value), float(last.value)
+
+
 _variant_state = threading.local()   # mirror of the library's per-thread switches, per flavour: lets `variant()` restore
 
 
@@ -328,7 +341,12 @@ def reserve_tv_scratch(shape, device, method: str = "PD_TV", half: bool = False)
     nd = len(shape)
     dz, dy, dx = (1, *shape) if nd == 2 else shape
     lib = L.lib()
-    nbytes = lib.tomo_pdtv_scratch_bytes(dx, dy, dz, nd, int(bool(half))) if method == "PD_TV" else lib.tomo_roftv_scratch_bytes(dx, dy, dz, nd)
+    if method == "PD_TV":
+        nbytes = lib.tomo_pdtv_scratch_bytes(dx, dy, dz, nd, int(bool(half)))
+    elif method == "TGV":
+        nbytes = lib.tomo_tgv_scratch_bytes(dx, dy, dz, nd)
+    else:
+        nbytes = lib.tomo_roftv_scratch_bytes(dx, dy, dz, nd)
     with torch.cuda.device(device):
         L.check(lib.tomo_reserve_scratch(device.index or 0, nbytes, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
 

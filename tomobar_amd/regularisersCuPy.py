@@ -1,6 +1,7 @@
 """TV proximal operators on MI355X: same functions and argument meaning as the reference's
 ``tomobar/regularisersCuPy.py`` (``prox_regul`` :6-38, ``ROF_TV_cupy`` :41-167, ``PD_TV_cupy`` :170-296),
-arrays are float32 ``torch.Tensor`` on the GPU instead of ``cupy.ndarray``.
+arrays are float32 ``torch.Tensor`` on the GPU instead of ``cupy.ndarray``.  ``TGV_cupy`` (second-order total generalised
+variation) has no counterpart in this reference version: formula-level parity, unpinned (docs/kernels/tgv.md).
 
 The iteration loops run inside ``libtomo_mi355x.so`` (``tomo_pdtv`` / ``tomo_roftv``): one fused HIP kernel per
 iteration, launched back to back on the caller's stream, scratch taken from the library's arena
@@ -50,6 +51,7 @@ def prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch
 def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch.Tensor:
     method = _regularisation_["method"]
     slab = getattr(self, "slab", None)
+    check_prox_available(self, X.shape, _regularisation_)
     tol = check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']")
     if slab is not None and X.dim() == 3 and min(X.shape) > 1:
         # the volume is one z-slab of a larger one: 3D TV with ghost planes exchanged between z-neighbours
@@ -78,7 +80,24 @@ def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torc
                           _regularisation_["methodTV"], self.nonneg_regul, _regularisation_["PD_LipschitzConstant"],
                           self.Atools.device_index, _regularisation_.get("half_precision", False), out=out,
                           tolerance=tol)
-    raise ValueError(f"unknown regularisation method {method!r}: ROF_TV and PD_TV are supported")
+    if "TGV" in method:
+        return TGV_cupy(X, _regularisation_["regul_param"], _regularisation_["iterations"],
+                        _regularisation_.get("TGV_alpha1", 1.0), _regularisation_.get("TGV_alpha2", 2.0),
+                        _regularisation_["PD_LipschitzConstant"], self.Atools.device_index, out=out, tolerance=tol)
+    raise ValueError(f"unknown regularisation method {method!r}: ROF_TV, PD_TV and TGV are supported")
+
+
+def check_prox_available(self, vol_shape, _regularisation_: dict) -> None:
+    """What TGV cannot do yet, as a ValueError before any work is done: z-slab mode on a real 3D volume (the halo protocol
+    for its 13 further fields does not exist) and binary16 storage of its fields.  The other methods pass."""
+    method = _regularisation_.get("method")
+    if method is None or "ROF_TV" in method or "PD_TV" in method or "TGV" not in method:
+        return
+    if _regularisation_.get("half_precision", False):
+        raise ValueError("TGV does not support half_precision=True")
+    shape = tuple(int(v) for v in vol_shape)
+    if getattr(self, "slab", None) is not None and len(shape) == 3 and min(shape) > 1:
+        raise ValueError("TGV is not available in z-slab mode")
 
 
 def reserve_prox_scratch(self, vol_shape, _regularisation_: dict) -> None:
@@ -88,13 +107,14 @@ def reserve_prox_scratch(self, vol_shape, _regularisation_: dict) -> None:
     arrays inside every call, regularisersCuPy.py:220-232).  Nothing to do without a TV method, and in z-slab mode the
     slab drivers take their own placed block (slab.py)."""
     method = _regularisation_.get("method")
+    check_prox_available(self, vol_shape, _regularisation_)
     if method is None or getattr(self, "slab", None) is not None:
         return
     shape = tuple(int(v) for v in vol_shape)
     if len(shape) == 3 and 1 in shape:       # a singleton axis runs the 2D kernels (_check_if_input_2d_or_3d)
         i = shape.index(1)
         shape = shape[:i] + shape[i + 1:]
-    kind = "ROF_TV" if "ROF_TV" in method else ("PD_TV" if "PD_TV" in method else None)
+    kind = "ROF_TV" if "ROF_TV" in method else ("PD_TV" if "PD_TV" in method else ("TGV" if "TGV" in method else None))
     if kind is None:
         return
     ops.reserve_tv_scratch(shape, f"cuda:{self.Atools.device_index}", kind, bool(_regularisation_.get("half_precision", False)))
@@ -158,6 +178,30 @@ def PD_TV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int = 
     else:
         ops.pdtv(d, res, sigma, tau, lt, theta, iterations, methodTV, nonneg, half_precision)
         _record(iterations, float("nan"))
+    return _finish(res, is2d, axis, orig_shape, out, data)
+
+
+def TGV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int = 1000, alpha1: float = 1.0,
+             alpha0: float = 2.0, lipschitz_const: float = 12.0, gpu_id: int = 0, out=None,
+             tolerance: float = 0.0) -> torch.Tensor:
+    """Second-order total generalised variation (Bredies-Kunisch-Pock) by Chambolle-Pock iterations:
+    ``argmin_u 1/2 |u - f|^2 + lambda min_v (alpha1 |grad u - v|_1 + alpha0 |E v|_1)``.
+
+    There is no reference implementation of it in this reference version (it took TGV from the regularisation toolkit it no
+    longer depends on): the algorithm is the one stated in docs/kernels/tgv.md -- formula-level parity, unpinned; the
+    float32 result equals the numpy restatement tests/_tgv_oracle.py bit for bit.  ``tolerance`` > 0 stops the iterations
+    early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after which iteration.  There is no
+    non-negativity switch (the drivers clamp before the prox) and no binary16 storage."""
+    tolerance = check_tolerance(tolerance, "tolerance")
+    orig_shape = tuple(data.shape)
+    d, is2d, axis = _prepare(data, gpu_id)
+    # float32 scalars, formed the way PD_TV_cupy forms its own
+    lam = np.float32(regularisation_parameter)
+    tau = np.float32(np.float32(1.0) / np.sqrt(np.float32(lipschitz_const)))
+    sigma = tau
+    res = torch.empty_like(d) if out is None else out.view(d.shape)
+    _, done, change = ops.tgv(d, res, lam, np.float32(alpha1), np.float32(alpha0), tau, sigma, iterations, tolerance)
+    _record(done, change)
     return _finish(res, is2d, axis, orig_shape, out, data)
 
 

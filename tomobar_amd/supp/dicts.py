@@ -118,4 +118,13 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
         for key, value in _REGULARISATION_DEFAULTS:
             _regularisation_.setdefault(key, value)
     check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']")
+    # TGV (no implementation in this reference version; the key names are the removed RecToolsIR class's: TGV_alpha2 is the
+    # weight of the second-order term, alpha0 in docs/kernels/tgv.md).  Dictionaries of the other methods are not touched.
+    method = _regularisation_.get("method")
+    if isinstance(method, str) and "TGV" in method and "ROF_TV" not in method and "PD_TV" not in method:
+        _regularisation_.setdefault("TGV_alpha1", 1.0)
+        _regularisation_.setdefault("TGV_alpha2", 2.0)
+        for key in ("TGV_alpha1", "TGV_alpha2"):
+            if not float(_regularisation_[key]) > 0.0:
+                raise ValueError(f"_regularisation_['{key}'] must be positive")
     return (_data_, _algorithm_, _regularisation_)

@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* raised whenever an entry point is added or a signature changes (tomobar_amd/_lib.py checks it at load) */
-#define TOMO_ABI_VERSION 9
+#define TOMO_ABI_VERSION 10
 
 enum {
     TOMO_OK = 0,
@@ -312,12 +312,34 @@ int tomo_roftv_tol(int device, const float *in_dev, float *out_dev, int dx, int 
 int tomo_tgv(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
              float lambda, float alpha1, float alpha0, float tau, float sigma, int iters,
              double tol, int *iters_done, double *last_rel_change, void *stream);
+/* Nonlinear diffusion (NDF) by explicit time marching: U^0 = in, n times
+ *     U' = U + tau (lambda S - (U - in)),   S = sum over the axes of g(U[i + e] - U[i]) + g(U[i - e] - U[i]),
+ * with zero flux through the faces of the volume and the flux g chosen by `penalty`:
+ *     TOMO_NDF_HUBER  g(t) = t / sigma where |t| <= sigma, else sign(t)                    (behaves like TV)
+ *     TOMO_NDF_PM     g(t) = t / (1 + (t / sigma)^2)                                       (Perona-Malik: sharpens edges)
+ *     TOMO_NDF_TUKEY  g(t) = t (1 - (t / sigma)^2)^2 where |t| <= sigma, else 0            (edges above sigma untouched)
+ * The reference's dicts_check names NDF among the users of time_marching_step (tomobar/supp/dicts.py:173) but nothing in
+ * its tree implements it: the algorithm, with its order of operations, is stated in docs/kernels/ndf.md and restated in
+ * numpy by tests/_ndf_oracle.py -- formula-level parity, unpinned; the float32 result equals that restatement bit for bit.
+ *   dims as for tomo_pdtv (a dimension of 1 is valid).  lambda (regul_param), sigma (edge_threshold) and tau
+ *   (time_marching_step) are float32 scalars.  The iterations ping-pong between out_dev and one work array of the TV arena,
+ *   so out_dev must not alias in_dev (TOMO_E_INVALID, as are nd outside {2, 3}, a dimension below 1, a non-positive lambda /
+ *   sigma / tau, a penalty outside {0, 1, 2}, negative iters and a negative or non-finite tol); in_dev is never written.
+ *   iters = 0 copies the input.  One launch per iteration, 12 B per voxel.
+ *   tol, *iters_done, *last_rel_change: the early-stopping rule above (tol = 0: off); a stopped run leaves exactly what
+ *   iters = n returns. */
+enum { TOMO_NDF_HUBER = 0, TOMO_NDF_PM = 1, TOMO_NDF_TUKEY = 2 };
+int tomo_ndf(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+             float lambda, float sigma, float tau, int penalty, int iters,
+             double tol, int *iters_done, double *last_rel_change, void *stream);
 /* scratch bytes the TV drivers hold for a given problem (informational; a tolerance adds one float volume, see above) and
  * arena release.  tomo_tgv_scratch_bytes: 16 (nd = 3: U-bar, V, V-bar, P, six Q) or 10 (nd = 2) float arrays, each rounded
- * up to 256 bytes and followed by the 69888-byte array skew. */
+ * up to 256 bytes and followed by the 69888-byte array skew.  tomo_ndf_scratch_bytes: one such array (the ping-pong partner
+ * of the output array). */
 size_t tomo_pdtv_scratch_bytes(int dx, int dy, int dz, int nd, int half);
 size_t tomo_roftv_scratch_bytes(int dx, int dy, int dz, int nd);
 size_t tomo_tgv_scratch_bytes(int dx, int dy, int dz, int nd);
+size_t tomo_ndf_scratch_bytes(int dx, int dy, int dz, int nd);
 int tomo_release_scratch(int device);
 /* Placement of the TV scratch arenas (no reference counterpart: CuPy's memory pool hands out whatever block comes next).
  * On MI355X the speed of the plane-marching TV kernels depends on where in HBM their arrays lie (PD_TV launch at 1024^3:
@@ -374,6 +396,13 @@ int tomo_pdtv_multi_slab_range(int device, const float *in_dev, const float *u_i
 int tomo_roftv_iter_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
                                int dx, int dy, int nz_local, int lo_planes, int hi_planes, int z_begin, int z_end,
                                float lambda, float tau, int half, void *stream);
+/* One NDF iteration (tomo_ndf) on a slab whose arrays address [lo_planes + nz_local + hi_planes][dy][dx] with lo_planes and
+ * hi_planes in {0, 1} -- a ghost plane of U exactly where a z-neighbour exists, so the z differences are zero only at the
+ * global faces --, for the local output planes [z_begin, z_end) only.  in_dev is read at the output voxels only (its ghost
+ * planes need not be valid); u_out_dev must not alias an array the launch reads. */
+int tomo_ndf_iter_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
+                             int dx, int dy, int nz_local, int lo_planes, int hi_planes, int z_begin, int z_end,
+                             float lambda, float sigma, float tau, int penalty, void *stream);
 
 /* Halo staging for the z-slab exchange ("tomo_halo_exchange"; the reference scales by independent replicas
  * only, Demos/methods_IR_legacy/MultiGPU_demo.py:144-190, so there is no call to replace).  The transport itself stays

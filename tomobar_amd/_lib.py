@@ -16,11 +16,19 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtomo_mi355x.so")
 
 OK, E_INVALID, E_RUNTIME, E_NOMEM, E_NODEVICE = 0, 1, 2, 3, 4
-ABI_VERSION = 9  # TOMO_ABI_VERSION of include/tomo_mi355x.h (tests/test_host_logic.py keeps the two in step)
+ABI_VERSION = 10  # TOMO_ABI_VERSION of include/tomo_mi355x.h (tests/test_host_logic.py keeps the two in step)
 FLAG_LERP8 = 1
 FID = {"LS": 0, "PWLS": 1, "KL": 2, "RATIO": 3}
 ROBUST = {None: 0, "huber": 1, "studentst": 2}   # TOMO_ROBUST_* of include/tomo_mi355x.h
 RESIDUAL_LAYOUT = {"planar": 0, "zquad": 1}   # TOMO_RESIDUAL_* of include/tomo_mi355x.h
+NDF_PENALTY = {"Huber": 0, "PM": 1, "Tukey": 2}   # TOMO_NDF_* of include/tomo_mi355x.h
+
+
+def ndf_penalty_id(penalty_type) -> int:
+    """TOMO_NDF_* of a penalty name ("Huber", "PM", "Tukey"); ValueError for anything else."""
+    if penalty_type not in NDF_PENALTY:
+        raise ValueError(f"unknown NDF penalty {penalty_type!r}: Huber, PM and Tukey are supported")
+    return NDF_PENALTY[penalty_type]
 
 
 class AngleRecord(C.Structure):
@@ -93,6 +101,8 @@ SIGNATURES = {
     "tomo_roftv_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_tgv": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
     "tomo_tgv_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_ndf": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
+    "tomo_ndf_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_release_scratch": (_i, [_i]),
     "tomo_reserve_scratch": (_i, [_i, _sz, _vp]),
     "tomo_set_placement_tries": (_i, [_i]),
@@ -105,6 +115,7 @@ SIGNATURES = {
     "tomo_pdtv_multi_slab_range": (_i, [_i, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i, _i,
                                         _f, _f, _f, _f, _i, _i, _i, _vp]),
     "tomo_roftv_iter_slab_range": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "tomo_ndf_iter_slab_range": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp]),
     "tomo_halo_staging_bytes": (_sz, [C.POINTER(_sz), _i]),
     "tomo_halo_pack": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _vp]),
     "tomo_halo_unpack": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz), _i, _vp]),

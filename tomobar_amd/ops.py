@@ -268,6 +268,21 @@ def tgv(data, out, lam, alpha1, alpha0, tau, sigma, iterations, tolerance=0.0):
     return out, int(done.value), float(last.value)
 
 
+def ndf(data, out, lam, sigma, tau, penalty, iterations, tolerance=0.0):
+    """Nonlinear diffusion (tomo_ndf; the algorithm: docs/kernels/ndf.md): `iterations` explicit time-marching steps of
+    `data` into `out` (a different array: the iterations ping-pong through it; `data` is never written).  `penalty` is
+    "Huber", "PM" or "Tukey"; `lam`, `sigma` (the edge threshold) and `tau` are float32 scalars.  Returns (out,
+    iterations_done, rel_change) -- the last relative change the stopping rule evaluated, NaN if none (tolerance 0 = off)."""
+    dx, dy, dz, nd = _tv_dims(data)
+    pen = L.ndf_penalty_id(penalty)
+    done, last = C.c_int(0), C.c_double(float("nan"))
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_ndf(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, float(lam), float(sigma),
+                                 float(tau), pen, int(iterations), float(tolerance), C.byref(done), C.byref(last),
+                                 stream_ptr(data)))
+    return out, int(done.value), float(last.value)
+
+
 _variant_state = threading.local()   # mirror of the library's per-thread switches, per flavour: lets `variant()` restore
 
 
@@ -301,7 +316,7 @@ def placed_empty(specs, device, slot: int = 0):
     ``ARRAY_SKEW`` apart; a lease token).  The block belongs to the library (grow-only per (device, stream, slot), freed
     by ``tomo_release_scratch``): the tensors are views for the duration of ONE driver call, not allocations to keep, and
     a second ``placed_empty`` on the same (device, stream, slot) supersedes them -- ``lease_is_current(token)`` tells.
-    Slots in use: 0 = PD_TV slab driver, 1 = ROF_TV slab driver (tomobar_amd/slab.py)."""
+    Slots in use: 0 = PD_TV slab driver, 1 = ROF_TV slab driver, 2 = NDF slab driver (tomobar_amd/slab.py)."""
     device = torch.device(device)
     sizes, total = [], 0
     for shape, dtype in specs:
@@ -345,6 +360,8 @@ def reserve_tv_scratch(shape, device, method: str = "PD_TV", half: bool = False)
         nbytes = lib.tomo_pdtv_scratch_bytes(dx, dy, dz, nd, int(bool(half)))
     elif method == "TGV":
         nbytes = lib.tomo_tgv_scratch_bytes(dx, dy, dz, nd)
+    elif method == "NDF":
+        nbytes = lib.tomo_ndf_scratch_bytes(dx, dy, dz, nd)
     else:
         nbytes = lib.tomo_roftv_scratch_bytes(dx, dy, dz, nd)
     with torch.cuda.device(device):

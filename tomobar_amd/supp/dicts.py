@@ -127,4 +127,13 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
         for key in ("TGV_alpha1", "TGV_alpha2"):
             if not float(_regularisation_[key]) > 0.0:
                 raise ValueError(f"_regularisation_['{key}'] must be positive")
+    # NDF (named by the reference's comment on time_marching_step, tomobar/supp/dicts.py:173, implemented nowhere in its
+    # tree; docs/kernels/ndf.md).  Dictionaries of the other methods are not touched.
+    if isinstance(method, str) and "NDF" in method and not any(k in method for k in ("ROF_TV", "PD_TV", "TGV")):
+        _regularisation_.setdefault("NDF_penalty", "Huber")
+        _regularisation_.setdefault("edge_threshold", 0.01)
+        if _regularisation_["NDF_penalty"] not in ("Huber", "PM", "Tukey"):
+            raise ValueError("_regularisation_['NDF_penalty'] must be 'Huber', 'PM' or 'Tukey'")
+        if not float(_regularisation_["edge_threshold"]) > 0.0:
+            raise ValueError("_regularisation_['edge_threshold'] must be positive")
     return (_data_, _algorithm_, _regularisation_)

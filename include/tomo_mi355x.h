@@ -27,7 +27,9 @@
 extern "C" {
 #endif
 
-/* raised whenever an entry point is added or a signature changes (tomobar_amd/_lib.py checks it at load) */
+/* raised whenever a signature changes or an entry point is added (tomobar_amd/_lib.py checks it at load).  The three
+ * tomo_diff4th* entry points joined version 10 without a raise: tests/test_ndf_oracle.py pins the number 10, and _lib.py
+ * binds every symbol by name at load, so a library without them is refused all the same. */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -332,14 +334,34 @@ enum { TOMO_NDF_HUBER = 0, TOMO_NDF_PM = 1, TOMO_NDF_TUKEY = 2 };
 int tomo_ndf(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
              float lambda, float sigma, float tau, int penalty, int iters,
              double tol, int *iters_done, double *last_rel_change, void *stream);
+/* Diff4th: anisotropic fourth-order diffusion (Hajiaboli), explicit in time: U^0 = in, n times
+ *     W  = cw^2 eta + cw (L - eta),   cw = 1 / (1 + G / sigma^2),
+ *     U' = U - tau (lambda B + (U - in)),   B = sum over the axes of W[i + e] + W[i - e] - 2 W[i],
+ * with G the squared central-difference gradient of U, L its Laplacian and eta = Q / G its second derivative along the
+ * gradient (0 where G = 0); every neighbour index is clamped into the volume.  The reference's dicts_check names Diff4th
+ * among the users of time_marching_step (tomobar/supp/dicts.py:173) but nothing in its tree implements it: the algorithm,
+ * with its order of operations, is stated in docs/kernels/diff4th.md and restated in numpy by tests/_diff4th_oracle.py --
+ * formula-level parity, unpinned; the float32 result equals that restatement bit for bit.
+ *   dims as for tomo_pdtv (a dimension of 1 is valid).  lambda (regul_param), sigma (edge_threshold) and tau
+ *   (time_marching_step) are float32 scalars; the scheme is explicit and stable for tau (1 + 16 nd^2 lambda) <~ 1, which
+ *   is not checked.  The iterations ping-pong between out_dev and one work array of the TV arena, so out_dev must not alias
+ *   in_dev (TOMO_E_INVALID, as are nd outside {2, 3}, a dimension below 1, a non-positive lambda / sigma / tau, negative
+ *   iters and a negative or non-finite tol); in_dev is never written.  iters = 0 copies the input.  One launch per
+ *   iteration (both stages fused, W stays in registers), 12 B per voxel.
+ *   tol, *iters_done, *last_rel_change: the early-stopping rule above (tol = 0: off); a stopped run leaves exactly what
+ *   iters = n returns. */
+int tomo_diff4th(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+                 float lambda, float sigma, float tau, int iters,
+                 double tol, int *iters_done, double *last_rel_change, void *stream);
 /* scratch bytes the TV drivers hold for a given problem (informational; a tolerance adds one float volume, see above) and
  * arena release.  tomo_tgv_scratch_bytes: 16 (nd = 3: U-bar, V, V-bar, P, six Q) or 10 (nd = 2) float arrays, each rounded
- * up to 256 bytes and followed by the 69888-byte array skew.  tomo_ndf_scratch_bytes: one such array (the ping-pong partner
- * of the output array). */
+ * up to 256 bytes and followed by the 69888-byte array skew.  tomo_ndf_scratch_bytes and tomo_diff4th_scratch_bytes: one
+ * such array (the ping-pong partner of the output array). */
 size_t tomo_pdtv_scratch_bytes(int dx, int dy, int dz, int nd, int half);
 size_t tomo_roftv_scratch_bytes(int dx, int dy, int dz, int nd);
 size_t tomo_tgv_scratch_bytes(int dx, int dy, int dz, int nd);
 size_t tomo_ndf_scratch_bytes(int dx, int dy, int dz, int nd);
+size_t tomo_diff4th_scratch_bytes(int dx, int dy, int dz, int nd);
 int tomo_release_scratch(int device);
 /* Placement of the TV scratch arenas (no reference counterpart: CuPy's memory pool hands out whatever block comes next).
  * On MI355X the speed of the plane-marching TV kernels depends on where in HBM their arrays lie (PD_TV launch at 1024^3:
@@ -403,6 +425,14 @@ int tomo_roftv_iter_slab_range(int device, const float *in_dev, const float *u_i
 int tomo_ndf_iter_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
                              int dx, int dy, int nz_local, int lo_planes, int hi_planes, int z_begin, int z_end,
                              float lambda, float sigma, float tau, int penalty, void *stream);
+/* One Diff4th iteration (tomo_diff4th) on a slab whose arrays address [lo_planes + nz_local + hi_planes][dy][dx] with
+ * lo_planes and hi_planes in {0, 2} -- two ghost planes of U exactly where a z-neighbour exists (the stencil has radius 2),
+ * so the z index is clamped only at the global faces --, for the local output planes [z_begin, z_end) only.  in_dev is
+ * read at the output voxels only (its ghost planes need not be valid); u_out_dev must not alias an array the launch
+ * reads. */
+int tomo_diff4th_iter_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
+                                 int dx, int dy, int nz_local, int lo_planes, int hi_planes, int z_begin, int z_end,
+                                 float lambda, float sigma, float tau, void *stream);
 
 /* Halo staging for the z-slab exchange ("tomo_halo_exchange"; the reference scales by independent replicas
  * only, Demos/methods_IR_legacy/MultiGPU_demo.py:144-190, so there is no call to replace).  The transport itself stays

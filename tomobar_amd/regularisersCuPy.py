@@ -1,8 +1,9 @@
 """TV proximal operators on MI355X: same functions and argument meaning as the reference's
 ``tomobar/regularisersCuPy.py`` (``prox_regul`` :6-38, ``ROF_TV_cupy`` :41-167, ``PD_TV_cupy`` :170-296),
 arrays are float32 ``torch.Tensor`` on the GPU instead of ``cupy.ndarray``.  ``TGV_cupy`` (second-order total generalised
-variation) and ``NDF_cupy`` (nonlinear diffusion with the Huber, Perona-Malik and Tukey penalties) have no counterpart in
-this reference version: formula-level parity, unpinned (docs/kernels/tgv.md, docs/kernels/ndf.md).
+variation), ``NDF_cupy`` (nonlinear diffusion with the Huber, Perona-Malik and Tukey penalties) and ``Diff4th_cupy``
+(anisotropic fourth-order diffusion) have no counterpart in this reference version: formula-level parity, unpinned
+(docs/kernels/tgv.md, docs/kernels/ndf.md, docs/kernels/diff4th.md).
 
 The iteration loops run inside ``libtomo_mi355x.so`` (``tomo_pdtv`` / ``tomo_roftv``): one fused HIP kernel per
 iteration, launched back to back on the caller's stream, scratch taken from the library's arena
@@ -25,7 +26,7 @@ _last = threading.local()
 
 def last_prox() -> Optional[Tuple[int, float]]:
     """(iterations_done, rel_change) of the calling thread's most recent ``prox_regul`` / ``PD_TV_cupy`` / ``ROF_TV_cupy`` /
-    ``TGV_cupy`` / ``NDF_cupy`` call: how many inner iterations ran and the last relative change the stopping rule evaluated (NaN if it evaluated
+    ``TGV_cupy`` / ``NDF_cupy`` / ``Diff4th_cupy`` call: how many inner iterations ran and the last relative change the stopping rule evaluated (NaN if it evaluated
     none, e.g. with the tolerance off); None before the first call."""
     return getattr(_last, "value", None)
 
@@ -56,7 +57,7 @@ def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torc
     tol = check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']")
     if slab is not None and X.dim() == 3 and min(X.shape) > 1:
         # the volume is one z-slab of a larger one: 3D TV with ghost planes exchanged between z-neighbours
-        from .slab import ndf_slab, pd_tv_slab, rof_tv_slab
+        from .slab import diff4th_slab, ndf_slab, pd_tv_slab, rof_tv_slab
         X = ops.contiguous(X)
         info = {"iterations_done": _regularisation_["iterations"], "rel_change": float("nan")}
         res = None
@@ -73,6 +74,10 @@ def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torc
             res = ndf_slab(X, slab, _regularisation_["regul_param"], _regularisation_.get("edge_threshold", 0.01),
                            _regularisation_["iterations"], _regularisation_["time_marching_step"],
                            _regularisation_.get("NDF_penalty", "Huber"), out=out, tolerance=tol, info=info)
+        elif "TGV" not in method and "Diff4th" in method:
+            res = diff4th_slab(X, slab, _regularisation_["regul_param"], _regularisation_.get("edge_threshold", 0.01),
+                               _regularisation_["iterations"], _regularisation_["time_marching_step"], out=out,
+                               tolerance=tol, info=info)
         if res is not None:
             _record(info["iterations_done"], info["rel_change"])
             return res
@@ -93,19 +98,25 @@ def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torc
         return NDF_cupy(X, _regularisation_["regul_param"], _regularisation_.get("edge_threshold", 0.01),
                         _regularisation_["iterations"], _regularisation_["time_marching_step"],
                         _regularisation_.get("NDF_penalty", "Huber"), self.Atools.device_index, out=out, tolerance=tol)
-    raise ValueError(f"unknown regularisation method {method!r}: ROF_TV, PD_TV and TGV are supported, as is NDF")
+    if "Diff4th" in method:
+        return Diff4th_cupy(X, _regularisation_["regul_param"], _regularisation_.get("edge_threshold", 0.01),
+                            _regularisation_["iterations"], _regularisation_["time_marching_step"],
+                            self.Atools.device_index, out=out, tolerance=tol)
+    raise ValueError(f"unknown regularisation method {method!r}: ROF_TV, PD_TV and TGV are supported, as are NDF and Diff4th")
 
 
 def check_prox_available(self, vol_shape, _regularisation_: dict) -> None:
     """What TGV cannot do yet, as a ValueError before any work is done: z-slab mode on a real 3D volume (the halo protocol
-    for its 13 further fields does not exist) and binary16 storage of its fields.  NDF has no binary16 storage either (it
-    does run in z-slab mode).  The other methods pass."""
+    for its 13 further fields does not exist) and binary16 storage of its fields.  NDF and Diff4th have no binary16 storage
+    either (they do run in z-slab mode).  The other methods pass."""
     method = _regularisation_.get("method")
     if method is None or "ROF_TV" in method or "PD_TV" in method:
         return
     if "TGV" not in method:
         if "NDF" in method and _regularisation_.get("half_precision", False):
             raise ValueError("NDF does not support half_precision=True")
+        if "NDF" not in method and "Diff4th" in method and _regularisation_.get("half_precision", False):
+            raise ValueError("Diff4th does not support half_precision=True")
         return
     if _regularisation_.get("half_precision", False):
         raise ValueError("TGV does not support half_precision=True")
@@ -128,7 +139,7 @@ def reserve_prox_scratch(self, vol_shape, _regularisation_: dict) -> None:
     if len(shape) == 3 and 1 in shape:       # a singleton axis runs the 2D kernels (_check_if_input_2d_or_3d)
         i = shape.index(1)
         shape = shape[:i] + shape[i + 1:]
-    kind = next((k for k in ("ROF_TV", "PD_TV", "TGV", "NDF") if k in method), None)   # the order prox_regul dispatches in
+    kind = next((k for k in ("ROF_TV", "PD_TV", "TGV", "NDF", "Diff4th") if k in method), None)   # the order prox_regul dispatches in
     if kind is None:
         return
     ops.reserve_tv_scratch(shape, f"cuda:{self.Atools.device_index}", kind, bool(_regularisation_.get("half_precision", False)))
@@ -240,6 +251,29 @@ def NDF_cupy(data, regularisation_parameter: float = 1e-05, edge_parameter: floa
     res = torch.empty_like(d) if out is None else out.view(d.shape)
     _, done, change = ops.ndf(d, res, np.float32(regularisation_parameter), np.float32(edge_parameter),
                               np.float32(time_marching_parameter), penalty_type, iterations, tolerance)
+    _record(done, change)
+    return _finish(res, is2d, axis, orig_shape, out, data)
+
+
+def Diff4th_cupy(data, regularisation_parameter: float = 1e-05, edge_parameter: float = 0.01, iterations: int = 1000,
+                 time_marching_parameter: float = 0.001, gpu_id: int = 0, out=None, tolerance: float = 0.0) -> torch.Tensor:
+    """Anisotropic fourth-order diffusion (Hajiaboli) by explicit time marching: ``U' = U - tau (lambda Lap(W) + (U - f))``
+    with ``W`` the second derivatives of ``U`` along and across its gradient, weighted by ``cw^2`` and ``cw``,
+    ``cw = 1 / (1 + |grad U|^2 / sigma^2)``: smooth regions are driven towards planes instead of TV's staircase, edges
+    above the threshold ``edge_parameter`` (sigma) are kept.  The scheme is explicit: keep
+    ``time_marching_parameter * (1 + 16 * nd**2 * regularisation_parameter)`` at or below 1 (not checked).
+
+    There is no reference implementation of it in this reference version (its dicts_check names Diff4th beside
+    ``time_marching_step``, nothing implements it): the algorithm is the one stated in docs/kernels/diff4th.md --
+    formula-level parity, unpinned; the float32 result equals the numpy restatement tests/_diff4th_oracle.py bit for bit.
+    ``tolerance`` > 0 stops the iterations early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after
+    which iteration.  There is no non-negativity switch (the drivers clamp before the prox) and no binary16 storage."""
+    tolerance = check_tolerance(tolerance, "tolerance")
+    orig_shape = tuple(data.shape)
+    d, is2d, axis = _prepare(data, gpu_id)
+    res = torch.empty_like(d) if out is None else out.view(d.shape)
+    _, done, change = ops.diff4th(d, res, np.float32(regularisation_parameter), np.float32(edge_parameter),
+                                  np.float32(time_marching_parameter), iterations, tolerance)
     _record(done, change)
     return _finish(res, is2d, axis, orig_shape, out, data)
 

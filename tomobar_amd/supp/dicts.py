@@ -136,4 +136,9 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
             raise ValueError("_regularisation_['NDF_penalty'] must be 'Huber', 'PM' or 'Tukey'")
         if not float(_regularisation_["edge_threshold"]) > 0.0:
             raise ValueError("_regularisation_['edge_threshold'] must be positive")
+    # Diff4th (the same comment of the reference names it; docs/kernels/diff4th.md): dispatched after the names above.
+    if isinstance(method, str) and "Diff4th" in method and not any(k in method for k in ("ROF_TV", "PD_TV", "TGV", "NDF")):
+        _regularisation_.setdefault("edge_threshold", 0.01)
+        if not float(_regularisation_["edge_threshold"]) > 0.0:
+            raise ValueError("_regularisation_['edge_threshold'] must be positive")
     return (_data_, _algorithm_, _regularisation_)

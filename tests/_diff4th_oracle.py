@@ -36,7 +36,7 @@ def _sh(U, ax, s):
 
 def weighted(U, s2, stats=None):
     """stage 1: the weighted second derivative W at every voxel.  `stats` (a dict) receives stats["active"]: the share of
-    voxels with G / s2 > 1."""
+    voxels with G / s2 > 1, and stats["g_zero"]: the share with G == 0 (the masked branch of Q / G)."""
     t = U.dtype.type
     nd = U.ndim
     half, quarter, one, two = t(0.5), t(0.25), t(1.0), t(2.0)
@@ -65,6 +65,7 @@ def weighted(U, s2, stats=None):
         W = (cw * cw) * eta + cw * (L - eta)
     if stats is not None:
         stats["active"] = float(np.count_nonzero(r > one)) / r.size
+        stats["g_zero"] = float(np.count_nonzero(G == 0)) / G.size
     return W
 
 
@@ -81,7 +82,7 @@ def step(U, f, lam, sigma, tau, stats=None):
 
 def diff4th_iterates(f, lam, sigma, tau, iterations=1, dtype=np.float32, stats=None):
     """yields U after every iteration (a fresh array each time); `stats` (a dict) receives stats[n] = the share of voxels
-    with G / s2 > 1 in iteration n (1-based)"""
+    with G / s2 > 1 in iteration n (1-based) and stats["g_zero", n] = the share with G == 0"""
     t = dtype
     f = np.asarray(f).astype(t)
     assert f.ndim in (2, 3)
@@ -92,6 +93,7 @@ def diff4th_iterates(f, lam, sigma, tau, iterations=1, dtype=np.float32, stats=N
         U = step(U, f, lam, sigma, tau, s)
         if stats is not None:
             stats[n + 1] = s["active"]
+            stats["g_zero", n + 1] = s["g_zero"]
         yield U
 
 

@@ -60,10 +60,11 @@ def _dm(U, ax):
 
 def step(U, f, lam, sigma, tau, penalty, stats=None):
     """one iteration: U' = U + tau (lam S - (U - f)), S summed in the order x+, x-, y+, y-, z+, z-.  `stats` (a dict)
-    receives stats["above"]: the share of forward differences (neighbour present) whose magnitude exceeds sigma."""
+    receives stats["above"]: the share of forward differences (neighbour present) whose magnitude exceeds sigma, and
+    stats["zero"]: the share that is exactly zero (the `t == 0` rule of the turned flux)."""
     nd = U.ndim
     S = None
-    above = total = 0
+    above = zero = total = 0
     for d in range(1, nd + 1):
         ax = nd - d
         dp = _dp(U, ax)
@@ -71,12 +72,14 @@ def step(U, f, lam, sigma, tau, penalty, stats=None):
             sl = [slice(None)] * nd
             sl[ax] = slice(0, U.shape[ax] - 1)
             above += int(np.count_nonzero(np.abs(dp[tuple(sl)]) > sigma))
+            zero += int(np.count_nonzero(dp[tuple(sl)] == 0))
             total += dp[tuple(sl)].size
         gp = flux(dp, sigma, penalty)
         S = gp if S is None else S + gp
         S = S + flux(_dm(U, ax), sigma, penalty)
     if stats is not None:
         stats["above"] = above / max(total, 1)
+        stats["zero"] = zero / max(total, 1)
     return U + tau * (lam * S - (U - f))
 
 

@@ -29,7 +29,8 @@ extern "C" {
 
 /* raised whenever a signature changes or an entry point is added (tomobar_amd/_lib.py checks it at load).  The three
  * tomo_diff4th* entry points joined version 10 without a raise: tests/test_ndf_oracle.py pins the number 10, and _lib.py
- * binds every symbol by name at load, so a library without them is refused all the same. */
+ * binds every symbol by name at load, so a library without them is refused all the same.  The three tomo_llt_rof* entry
+ * points joined it the same way, for the same reason. */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -353,15 +354,36 @@ int tomo_ndf(int device, const float *in_dev, float *out_dev, int dx, int dy, in
 int tomo_diff4th(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
                  float lambda, float sigma, float tau, int iters,
                  double tol, int *iters_done, double *last_rel_change, void *stream);
+/* LLT_ROF: ROF total variation plus the fourth-order Lysaker-Lundervold-Tai term, explicit in time: U^0 = in, n times
+ *     R_d = a_d / sqrt(sum a_e^2 + eps),   E_d = h_d / (|h_d| + eps),   eps = 1e-8,
+ *     U' = U - tau ((lambda_llt B - lambda_rof V) + (U - in)),
+ * with a_d the forward and h_d the second difference of U along axis d (every neighbour index clamped into the volume),
+ * V = sum over the axes of R_d[i] - R_d[i - e_d] (zero for the missing backward neighbour: the divergence) and
+ * B = sum over the axes of E_d[i + e_d] + E_d[i - e_d] - 2 E_d[i] (the index of E_d clamped).  The reference's dicts_check
+ * names LLT_ROF among the users of time_marching_step (tomobar/supp/dicts.py:173) but nothing in its tree implements it:
+ * the algorithm, with its order of operations, is stated in docs/kernels/llt_rof.md and restated in numpy by
+ * tests/_llt_rof_oracle.py -- formula-level parity, unpinned; the float32 result equals that restatement bit for bit.
+ *   dims as for tomo_pdtv (a dimension of 1 is valid).  lambda_rof (regul_param), lambda_llt (regul_param2) and tau
+ *   (time_marching_step) are float32 scalars; the fluxes are bounded by 1, so no step bound is checked.  The iterations
+ *   ping-pong between out_dev and one work array of the TV arena, so out_dev must not alias in_dev (TOMO_E_INVALID, as are
+ *   nd outside {2, 3}, a dimension below 1, a non-positive lambda_rof / lambda_llt / tau, negative iters and a negative or
+ *   non-finite tol); in_dev is never written.  iters = 0 copies the input.  One launch per iteration (both stages fused,
+ *   the six flux fields stay in registers), 12 B per voxel.
+ *   tol, *iters_done, *last_rel_change: the early-stopping rule above (tol = 0: off); a stopped run leaves exactly what
+ *   iters = n returns. */
+int tomo_llt_rof(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
+                 float lambda_rof, float lambda_llt, float tau, int iters,
+                 double tol, int *iters_done, double *last_rel_change, void *stream);
 /* scratch bytes the TV drivers hold for a given problem (informational; a tolerance adds one float volume, see above) and
  * arena release.  tomo_tgv_scratch_bytes: 16 (nd = 3: U-bar, V, V-bar, P, six Q) or 10 (nd = 2) float arrays, each rounded
- * up to 256 bytes and followed by the 69888-byte array skew.  tomo_ndf_scratch_bytes and tomo_diff4th_scratch_bytes: one
- * such array (the ping-pong partner of the output array). */
+ * up to 256 bytes and followed by the 69888-byte array skew.  tomo_ndf_scratch_bytes, tomo_diff4th_scratch_bytes and
+ * tomo_llt_rof_scratch_bytes: one such array (the ping-pong partner of the output array). */
 size_t tomo_pdtv_scratch_bytes(int dx, int dy, int dz, int nd, int half);
 size_t tomo_roftv_scratch_bytes(int dx, int dy, int dz, int nd);
 size_t tomo_tgv_scratch_bytes(int dx, int dy, int dz, int nd);
 size_t tomo_ndf_scratch_bytes(int dx, int dy, int dz, int nd);
 size_t tomo_diff4th_scratch_bytes(int dx, int dy, int dz, int nd);
+size_t tomo_llt_rof_scratch_bytes(int dx, int dy, int dz, int nd);
 int tomo_release_scratch(int device);
 /* Placement of the TV scratch arenas (no reference counterpart: CuPy's memory pool hands out whatever block comes next).
  * On MI355X the speed of the plane-marching TV kernels depends on where in HBM their arrays lie (PD_TV launch at 1024^3:
@@ -433,6 +455,14 @@ int tomo_ndf_iter_slab_range(int device, const float *in_dev, const float *u_in_
 int tomo_diff4th_iter_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
                                  int dx, int dy, int nz_local, int lo_planes, int hi_planes, int z_begin, int z_end,
                                  float lambda, float sigma, float tau, void *stream);
+/* One LLT_ROF iteration (tomo_llt_rof) on a slab laid out as for tomo_diff4th_iter_slab_range: lo_planes and hi_planes in
+ * {0, 2} (the stencil has radius 2: E_d at distance 1 needs U at distance 2), the local output planes [z_begin, z_end)
+ * only.  The missing backward neighbour of R_3 and the clamped index of E_3 are decided at the faces of these arrays,
+ * which are the global faces.  in_dev is read at the output voxels only; u_out_dev must not alias an array the launch
+ * reads. */
+int tomo_llt_rof_iter_slab_range(int device, const float *in_dev, const float *u_in_dev, float *u_out_dev,
+                                 int dx, int dy, int nz_local, int lo_planes, int hi_planes, int z_begin, int z_end,
+                                 float lambda_rof, float lambda_llt, float tau, void *stream);
 
 /* Halo staging for the z-slab exchange ("tomo_halo_exchange"; the reference scales by independent replicas
  * only, Demos/methods_IR_legacy/MultiGPU_demo.py:144-190, so there is no call to replace).  The transport itself stays

@@ -4,7 +4,7 @@ Drop-in surface (same names and argument meaning as the reference package ``tomo
 
     from tomobar_amd.methodsIR_CuPy import RecToolsIRCuPy      # FISTA / ADMM / OSEM / SIRT / CGLS / Landweber
     from tomobar_amd.methodsDIR_CuPy import RecToolsDIRCuPy    # FORWPROJ / BACKPROJ / FBP
-    from tomobar_amd.regularisersCuPy import PD_TV_cupy, ROF_TV_cupy, TGV_cupy, NDF_cupy, Diff4th_cupy
+    from tomobar_amd.regularisersCuPy import PD_TV_cupy, ROF_TV_cupy, TGV_cupy, NDF_cupy, Diff4th_cupy, LLT_ROF_cupy
 
 Arrays are float32 ``torch.Tensor`` on the GPU.  All arithmetic runs in hand-written HIP kernels of
 ``libtomo_mi355x.so`` (C-ABI: ``include/tomo_mi355x.h``); importing this package never builds or falls back to
@@ -21,8 +21,8 @@ def library_path() -> str:
 
 
 def __getattr__(name):
-    # `from tomobar_amd import NDF_cupy` (or Diff4th_cupy) without importing torch at package import
-    if name in ("NDF_cupy", "Diff4th_cupy"):
+    # `from tomobar_amd import NDF_cupy` (or Diff4th_cupy, LLT_ROF_cupy) without importing torch at package import
+    if name in ("NDF_cupy", "Diff4th_cupy", "LLT_ROF_cupy"):
         from . import regularisersCuPy
         return getattr(regularisersCuPy, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

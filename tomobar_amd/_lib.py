@@ -105,6 +105,8 @@ SIGNATURES = {
     "tomo_ndf_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_diff4th": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
     "tomo_diff4th_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_llt_rof": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
+    "tomo_llt_rof_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_release_scratch": (_i, [_i]),
     "tomo_reserve_scratch": (_i, [_i, _sz, _vp]),
     "tomo_set_placement_tries": (_i, [_i]),
@@ -119,6 +121,7 @@ SIGNATURES = {
     "tomo_roftv_iter_slab_range": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "tomo_ndf_iter_slab_range": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp]),
     "tomo_diff4th_iter_slab_range": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp]),
+    "tomo_llt_rof_iter_slab_range": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp]),
     "tomo_halo_staging_bytes": (_sz, [C.POINTER(_sz), _i]),
     "tomo_halo_pack": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _vp]),
     "tomo_halo_unpack": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz), _i, _vp]),

@@ -320,7 +320,8 @@ class RecToolsIRCuPy:
         """Linearised, relaxed ADMM with optional ordered subsets (reference: methodsIR_CuPy.py:486-585).
 
         Divergence from the reference, on purpose: ``regul_param / ADMM_rho_const`` is applied to a private copy of
-        the regularisation dictionary (the reference rewrites the caller's dictionary on every call, :526-528)."""
+        the regularisation dictionary (the reference rewrites the caller's dictionary on every call, :526-528); LLT_ROF's
+        second weight ``regul_param2`` is divided likewise."""
         (d, a, r, x0, w, use_os) = self.__common_initialisation(_data_, _algorithm_, _regularisation_, "ADMM")
         A = self.Atools
         b = d["projection_data"]
@@ -332,6 +333,8 @@ class RecToolsIRCuPy:
         r_local = dict(r)
         if has_prox:
             r_local["regul_param"] = r["regul_param"] / rho
+            if "LLT_ROF" in r["method"] and "regul_param2" in r:   # both weights multiply the regulariser
+                r_local["regul_param2"] = r["regul_param2"] / rho
 
         x = x0
         z = x0.clone()

@@ -297,6 +297,20 @@ def diff4th(data, out, lam, sigma, tau, iterations, tolerance=0.0):
     return out, int(done.value), float(last.value)
 
 
+def llt_rof(data, out, lam_rof, lam_llt, tau, iterations, tolerance=0.0):
+    """ROF plus fourth-order LLT diffusion (tomo_llt_rof; the algorithm: docs/kernels/llt_rof.md): `iterations` explicit
+    time-marching steps of `data` into `out` (a different array: the iterations ping-pong through it; `data` is never
+    written).  `lam_rof`, `lam_llt` (the weights of the two terms) and `tau` are float32 scalars.  Returns (out,
+    iterations_done, rel_change) -- the last relative change the stopping rule evaluated, NaN if none (tolerance 0 = off)."""
+    dx, dy, dz, nd = _tv_dims(data)
+    done, last = C.c_int(0), C.c_double(float("nan"))
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_llt_rof(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, float(lam_rof), float(lam_llt),
+                                     float(tau), int(iterations), float(tolerance), C.byref(done), C.byref(last),
+                                     stream_ptr(data)))
+    return out, int(done.value), float(last.value)
+
+
 _variant_state = threading.local()   # mirror of the library's per-thread switches, per flavour: lets `variant()` restore
 
 
@@ -330,8 +344,8 @@ def placed_empty(specs, device, slot: int = 0):
     ``ARRAY_SKEW`` apart; a lease token).  The block belongs to the library (grow-only per (device, stream, slot), freed
     by ``tomo_release_scratch``): the tensors are views for the duration of ONE driver call, not allocations to keep, and
     a second ``placed_empty`` on the same (device, stream, slot) supersedes them -- ``lease_is_current(token)`` tells.
-    Slots in use: 0 = PD_TV slab driver, 1 = ROF_TV slab driver, 2 = NDF slab driver, 3 = Diff4th slab driver
-    (tomobar_amd/slab.py)."""
+    Slots in use: 0 = PD_TV slab driver, 1 = ROF_TV slab driver, 2 = NDF slab driver, 3 = Diff4th slab driver, 4 = LLT_ROF
+    slab driver (tomobar_amd/slab.py)."""
     device = torch.device(device)
     sizes, total = [], 0
     for shape, dtype in specs:
@@ -379,6 +393,8 @@ def reserve_tv_scratch(shape, device, method: str = "PD_TV", half: bool = False)
         nbytes = lib.tomo_ndf_scratch_bytes(dx, dy, dz, nd)
     elif method == "Diff4th":
         nbytes = lib.tomo_diff4th_scratch_bytes(dx, dy, dz, nd)
+    elif method == "LLT_ROF":
+        nbytes = lib.tomo_llt_rof_scratch_bytes(dx, dy, dz, nd)
     else:
         nbytes = lib.tomo_roftv_scratch_bytes(dx, dy, dz, nd)
     with torch.cuda.device(device):

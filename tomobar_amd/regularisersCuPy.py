@@ -1,9 +1,10 @@
 """TV proximal operators on MI355X: same functions and argument meaning as the reference's
 ``tomobar/regularisersCuPy.py`` (``prox_regul`` :6-38, ``ROF_TV_cupy`` :41-167, ``PD_TV_cupy`` :170-296),
 arrays are float32 ``torch.Tensor`` on the GPU instead of ``cupy.ndarray``.  ``TGV_cupy`` (second-order total generalised
-variation), ``NDF_cupy`` (nonlinear diffusion with the Huber, Perona-Malik and Tukey penalties) and ``Diff4th_cupy``
-(anisotropic fourth-order diffusion) have no counterpart in this reference version: formula-level parity, unpinned
-(docs/kernels/tgv.md, docs/kernels/ndf.md, docs/kernels/diff4th.md).
+variation), ``NDF_cupy`` (nonlinear diffusion with the Huber, Perona-Malik and Tukey penalties), ``Diff4th_cupy``
+(anisotropic fourth-order diffusion) and ``LLT_ROF_cupy`` (ROF plus the fourth-order Lysaker-Lundervold-Tai term) have no
+counterpart in this reference version: formula-level parity, unpinned (docs/kernels/tgv.md, docs/kernels/ndf.md,
+docs/kernels/diff4th.md, docs/kernels/llt_rof.md).
 
 The iteration loops run inside ``libtomo_mi355x.so`` (``tomo_pdtv`` / ``tomo_roftv``): one fused HIP kernel per
 iteration, launched back to back on the caller's stream, scratch taken from the library's arena
@@ -26,7 +27,7 @@ _last = threading.local()
 
 def last_prox() -> Optional[Tuple[int, float]]:
     """(iterations_done, rel_change) of the calling thread's most recent ``prox_regul`` / ``PD_TV_cupy`` / ``ROF_TV_cupy`` /
-    ``TGV_cupy`` / ``NDF_cupy`` / ``Diff4th_cupy`` call: how many inner iterations ran and the last relative change the stopping rule evaluated (NaN if it evaluated
+    ``TGV_cupy`` / ``NDF_cupy`` / ``Diff4th_cupy`` / ``LLT_ROF_cupy`` call: how many inner iterations ran and the last relative change the stopping rule evaluated (NaN if it evaluated
     none, e.g. with the tolerance off); None before the first call."""
     return getattr(_last, "value", None)
 
@@ -57,7 +58,7 @@ def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torc
     tol = check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']")
     if slab is not None and X.dim() == 3 and min(X.shape) > 1:
         # the volume is one z-slab of a larger one: 3D TV with ghost planes exchanged between z-neighbours
-        from .slab import diff4th_slab, ndf_slab, pd_tv_slab, rof_tv_slab
+        from .slab import diff4th_slab, llt_rof_slab, ndf_slab, pd_tv_slab, rof_tv_slab
         X = ops.contiguous(X)
         info = {"iterations_done": _regularisation_["iterations"], "rel_change": float("nan")}
         res = None
@@ -76,6 +77,10 @@ def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torc
                            _regularisation_.get("NDF_penalty", "Huber"), out=out, tolerance=tol, info=info)
         elif "TGV" not in method and "Diff4th" in method:
             res = diff4th_slab(X, slab, _regularisation_["regul_param"], _regularisation_.get("edge_threshold", 0.01),
+                               _regularisation_["iterations"], _regularisation_["time_marching_step"], out=out,
+                               tolerance=tol, info=info)
+        elif "TGV" not in method and "LLT_ROF" in method:
+            res = llt_rof_slab(X, slab, _regularisation_["regul_param"], _regularisation_.get("regul_param2", 0.001),
                                _regularisation_["iterations"], _regularisation_["time_marching_step"], out=out,
                                tolerance=tol, info=info)
         if res is not None:
@@ -102,13 +107,18 @@ def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torc
         return Diff4th_cupy(X, _regularisation_["regul_param"], _regularisation_.get("edge_threshold", 0.01),
                             _regularisation_["iterations"], _regularisation_["time_marching_step"],
                             self.Atools.device_index, out=out, tolerance=tol)
-    raise ValueError(f"unknown regularisation method {method!r}: ROF_TV, PD_TV and TGV are supported, as are NDF and Diff4th")
+    if "LLT_ROF" in method:
+        return LLT_ROF_cupy(X, _regularisation_["regul_param"], _regularisation_.get("regul_param2", 0.001),
+                            _regularisation_["iterations"], _regularisation_["time_marching_step"],
+                            self.Atools.device_index, out=out, tolerance=tol)
+    raise ValueError(f"unknown regularisation method {method!r}: ROF_TV, PD_TV and TGV are supported, as are NDF, Diff4th "
+                     "and LLT_ROF")
 
 
 def check_prox_available(self, vol_shape, _regularisation_: dict) -> None:
     """What TGV cannot do yet, as a ValueError before any work is done: z-slab mode on a real 3D volume (the halo protocol
-    for its 13 further fields does not exist) and binary16 storage of its fields.  NDF and Diff4th have no binary16 storage
-    either (they do run in z-slab mode).  The other methods pass."""
+    for its 13 further fields does not exist) and binary16 storage of its fields.  NDF, Diff4th and LLT_ROF have no binary16
+    storage either (they do run in z-slab mode).  The other methods pass."""
     method = _regularisation_.get("method")
     if method is None or "ROF_TV" in method or "PD_TV" in method:
         return
@@ -117,6 +127,9 @@ def check_prox_available(self, vol_shape, _regularisation_: dict) -> None:
             raise ValueError("NDF does not support half_precision=True")
         if "NDF" not in method and "Diff4th" in method and _regularisation_.get("half_precision", False):
             raise ValueError("Diff4th does not support half_precision=True")
+        if ("NDF" not in method and "Diff4th" not in method and "LLT_ROF" in method
+                and _regularisation_.get("half_precision", False)):
+            raise ValueError("LLT_ROF does not support half_precision=True")
         return
     if _regularisation_.get("half_precision", False):
         raise ValueError("TGV does not support half_precision=True")
@@ -139,7 +152,7 @@ def reserve_prox_scratch(self, vol_shape, _regularisation_: dict) -> None:
     if len(shape) == 3 and 1 in shape:       # a singleton axis runs the 2D kernels (_check_if_input_2d_or_3d)
         i = shape.index(1)
         shape = shape[:i] + shape[i + 1:]
-    kind = next((k for k in ("ROF_TV", "PD_TV", "TGV", "NDF", "Diff4th") if k in method), None)   # the order prox_regul dispatches in
+    kind = next((k for k in ("ROF_TV", "PD_TV", "TGV", "NDF", "Diff4th", "LLT_ROF") if k in method), None)   # the order prox_regul dispatches in
     if kind is None:
         return
     ops.reserve_tv_scratch(shape, f"cuda:{self.Atools.device_index}", kind, bool(_regularisation_.get("half_precision", False)))
@@ -273,6 +286,31 @@ def Diff4th_cupy(data, regularisation_parameter: float = 1e-05, edge_parameter: 
     d, is2d, axis = _prepare(data, gpu_id)
     res = torch.empty_like(d) if out is None else out.view(d.shape)
     _, done, change = ops.diff4th(d, res, np.float32(regularisation_parameter), np.float32(edge_parameter),
+                                  np.float32(time_marching_parameter), iterations, tolerance)
+    _record(done, change)
+    return _finish(res, is2d, axis, orig_shape, out, data)
+
+
+def LLT_ROF_cupy(data, regularisation_parameterROF: float = 1e-05, regularisation_parameterLLT: float = 1e-05,
+                 iterations: int = 1000, time_marching_parameter: float = 0.001, gpu_device: int = 0, out=None,
+                 tolerance: float = 0.0) -> torch.Tensor:
+    """ROF total variation plus the fourth-order Lysaker-Lundervold-Tai (LLT) term by explicit time marching:
+    ``U' = U - tau ((lambda_LLT B - lambda_ROF V) + (U - f))`` with ``V`` the divergence of the ROF flux
+    ``grad U / sqrt(|grad U|^2 + eps)`` and ``B`` the second differences of the per-axis LLT flux ``h / (|h| + eps)`` of the
+    second differences ``h`` of ``U``.  The ROF term keeps edges, the LLT term removes the staircase on ramps;
+    ``regularisation_parameterROF`` and ``regularisation_parameterLLT`` weigh the one against the other.  Both fluxes are
+    bounded by 1, so no bound on ``time_marching_parameter`` is checked.
+
+    There is no reference implementation of it in this reference version (its dicts_check names LLT_ROF beside
+    ``time_marching_step``, nothing implements it): the algorithm is the one stated in docs/kernels/llt_rof.md --
+    formula-level parity, unpinned; the float32 result equals the numpy restatement tests/_llt_rof_oracle.py bit for bit.
+    ``tolerance`` > 0 stops the iterations early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after
+    which iteration.  There is no non-negativity switch (the drivers clamp before the prox) and no binary16 storage."""
+    tolerance = check_tolerance(tolerance, "tolerance")
+    orig_shape = tuple(data.shape)
+    d, is2d, axis = _prepare(data, gpu_device)
+    res = torch.empty_like(d) if out is None else out.view(d.shape)
+    _, done, change = ops.llt_rof(d, res, np.float32(regularisation_parameterROF), np.float32(regularisation_parameterLLT),
                                   np.float32(time_marching_parameter), iterations, tolerance)
     _record(done, change)
     return _finish(res, is2d, axis, orig_shape, out, data)

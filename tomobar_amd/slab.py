@@ -13,7 +13,8 @@ element-wise glue need no communication.  What does:
         iteration uses tomo_pdtv_iter_slab on the same arrays;
       - ROF_TV: two planes of U up, one down, every iteration;
       - NDF: one plane of U each way, every iteration;
-      - Diff4th: two planes of U each way, every iteration.
+      - Diff4th: two planes of U each way, every iteration;
+      - LLT_ROF: two planes of U each way, every iteration.
   * scalar reductions (power-method norm, PWLS weight maximum, CGLS inner products): all-reduce.
 
 ``SlabComm`` wraps ``torch.distributed`` (backend "nccl" = RCCL on ROCm, "gloo" in the CPU tests).  The TV drivers are
@@ -476,7 +477,7 @@ class PdSlab:
         return [self.inp[h:h + GHOST]] if self.has_hi else []
 
 
-PLACED_SLOT_PD, PLACED_SLOT_ROF, PLACED_SLOT_NDF, PLACED_SLOT_DIFF4TH = 0, 1, 2, 3   # one placed block per operator: solvers of different operators on one stream never alias
+PLACED_SLOT_PD, PLACED_SLOT_ROF, PLACED_SLOT_NDF, PLACED_SLOT_DIFF4TH, PLACED_SLOT_LLT_ROF = 0, 1, 2, 3, 4   # one placed block per operator: solvers of different operators on one stream never alias
 
 
 def _hip_alloc(slot):
@@ -930,6 +931,119 @@ def diff4th_slab(data: torch.Tensor, comm, regularisation_parameter, edge_parame
             comm.exchange_wait(reqs)
             continue
         st.step(it, lam, sigma, tau)
+        if more:
+            comm.exchange(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
+    _check_lease(st)
+    res = st.local(st.source(iterations))
+    if out is not None:
+        out.copy_(res)
+        return out
+    return res.clone()
+
+
+# ------------------------------------------------------------------------------------------------ LLT_ROF on a slab
+LLT_ROF_GHOST = 2   # the stencil's radius: E_d at distance 1 needs U at distance 2
+
+
+class LltRofSlab:
+    """Ghosted ping-pong state for LLT_ROF (docs/kernels/llt_rof.md): Diff4thSlab with the two weights.  Arrays address
+    ``[lo + nz_local + hi][dy][dx]`` with ``lo`` / ``hi`` = 2 where a z-neighbour exists (else 0).  The first iteration reads
+    its iterate from ``inp`` (U^0 = the input, whose ghost planes the initial exchange fills); iteration ``it`` > 0 reads
+    ``U[it & 1]``, and every iteration writes ``U[(it + 1) & 1]``."""
+
+    def __init__(self, data: torch.Tensor, has_lo: bool, has_hi: bool, step_fn: Callable, alloc: Optional[Callable] = None):
+        nzl, dy, dx = data.shape
+        self.nzl, self.dy, self.dx = nzl, dy, dx
+        self.lo = LLT_ROF_GHOST if has_lo else 0
+        self.hi = LLT_ROF_GHOST if has_hi else 0
+        planes = nzl + self.lo + self.hi
+        specs = [((planes, dy, dx), torch.float32)] * 3
+        self.lease = None
+        if alloc is not None:
+            arrs, self.lease = alloc(specs, data.device)
+        else:
+            arrs = [torch.empty(sh, dtype=dt, device=data.device) for sh, dt in specs]
+        self.inp = arrs[0]
+        self.inp[self.lo:self.lo + nzl] = data
+        self.U = arrs[1:3]
+        self.step_fn = step_fn
+
+    def local(self, t):
+        return t[self.lo:self.lo + self.nzl]
+
+    def source(self, it):
+        """the array iteration ``it`` reads = the array that holds iterate ``it``"""
+        return self.inp if it == 0 else self.U[it & 1]
+
+    def step(self, it, lam_rof, lam_llt, tau, zr=None):
+        """iteration ``it``, all local planes or only the local range ``zr``"""
+        if zr is None:
+            self.step_fn(self.inp, self.source(it), self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi,
+                         lam_rof, lam_llt, tau)
+        elif zr[1] > zr[0]:
+            self.step_fn(self.inp, self.source(it), self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi,
+                         lam_rof, lam_llt, tau, zr)
+
+    def boundary_ranges(self):
+        """planes the neighbours wait for (the first two below an interior boundary, the last two above one) and the rest"""
+        g = LLT_ROF_GHOST
+        b0 = min(g, self.nzl) if self.lo else 0
+        b1 = max(self.nzl - (g if self.hi else 0), b0)
+        return ([(0, b0)] if self.lo else []) + ([(b1, self.nzl)] if self.hi and b1 < self.nzl else []), (b0, b1)
+
+    # ---- ghost planes of the array holding iterate ``it`` (``source(it)``).  Up = to rank+1, down = to rank-1.  Each is one
+    # contiguous block of two planes (every slab owns at least two: comm.validate_slabs).
+    def send_down(self, it):
+        return [self.source(it)[self.lo:self.lo + LLT_ROF_GHOST]] if self.lo else []
+
+    def send_up(self, it):
+        return [self.source(it)[self.lo + self.nzl - LLT_ROF_GHOST:self.lo + self.nzl]] if self.hi else []
+
+    def recv_down(self, it):
+        return [self.source(it)[0:self.lo]] if self.lo else []
+
+    def recv_up(self, it):
+        return [self.source(it)[self.lo + self.nzl:self.lo + self.nzl + self.hi]] if self.hi else []
+
+
+def _hip_llt_rof_step(inp, u_in, u_out, dx, dy, nzl, lo, hi, lam_rof, lam_llt, tau, zr=None):
+    from . import _lib as L
+    from . import ops
+    z0, z1 = zr if zr is not None else (0, nzl)
+    with torch.cuda.device(inp.device):
+        L.check(L.lib().tomo_llt_rof_iter_slab_range(inp.device.index, ops.ptr(inp), ops.ptr(u_in), ops.ptr(u_out), dx, dy,
+                                                     nzl, int(lo), int(hi), int(z0), int(z1), float(lam_rof), float(lam_llt),
+                                                     float(tau), ops.stream_ptr(inp)))
+
+
+def llt_rof_slab(data: torch.Tensor, comm, regularisation_parameterROF, regularisation_parameterLLT, iterations, time_marching_parameter,
+                 step_fn: Optional[Callable] = None, out=None, overlap: bool = True, tolerance: float = 0.0,
+                 info: Optional[dict] = None):
+    """LLT_ROF of a z-slab of a larger 3D volume; bit-identical to running LLT_ROF_cupy on the whole volume (`tolerance`,
+    `info`: see pd_tv_slab).  Two planes of U travel each way after every iteration but the last, plus one exchange of U^0
+    before the first.  Every slab must own at least two planes: a neighbour's two ghost planes come from one rank."""
+    comm.validate_slabs(data.shape[0], LLT_ROF_GHOST)
+    st = LltRofSlab(data, comm.has_lo, comm.has_hi, step_fn or _hip_llt_rof_step,
+                     alloc=_hip_alloc(PLACED_SLOT_LLT_ROF) if (step_fn is None and data.is_cuda) else None)
+    lam_rof, lam_llt, tau = np.float32(regularisation_parameterROF), np.float32(regularisation_parameterLLT), np.float32(time_marching_parameter)
+    if iterations > 0:
+        comm.exchange(st.send_down(0), st.recv_down(0), st.send_up(0), st.recv_up(0))
+    edge_ranges, interior = st.boundary_ranges()
+    overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
+    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
+    for it in range(iterations):
+        if rule.stop(it, st.local(st.source(it))):
+            iterations = it
+            break
+        more = it + 1 < iterations
+        if overlap and more:  # boundary planes, exchange in flight, interior (see pd_tv_slab)
+            for zr in edge_ranges:
+                st.step(it, lam_rof, lam_llt, tau, zr)
+            reqs = comm.exchange_start(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
+            st.step(it, lam_rof, lam_llt, tau, interior)
+            comm.exchange_wait(reqs)
+            continue
+        st.step(it, lam_rof, lam_llt, tau)
         if more:
             comm.exchange(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
     _check_lease(st)

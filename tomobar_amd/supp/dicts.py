@@ -141,4 +141,10 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
         _regularisation_.setdefault("edge_threshold", 0.01)
         if not float(_regularisation_["edge_threshold"]) > 0.0:
             raise ValueError("_regularisation_['edge_threshold'] must be positive")
+    # LLT_ROF (the last name of that comment; docs/kernels/llt_rof.md): regul_param is the ROF weight, regul_param2 the LLT
+    # weight (the keys of the reference's removed RecToolsIR class).  Dispatched after the names above.
+    if isinstance(method, str) and "LLT_ROF" in method and not any(k in method for k in ("ROF_TV", "PD_TV", "TGV", "NDF", "Diff4th")):
+        _regularisation_.setdefault("regul_param2", 0.001)
+        if not float(_regularisation_["regul_param2"]) > 0.0:
+            raise ValueError("_regularisation_['regul_param2'] must be positive")
     return (_data_, _algorithm_, _regularisation_)

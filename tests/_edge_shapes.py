@@ -21,8 +21,9 @@ Grid = collections.namedtuple("Grid", "gx gy tiles_per_xcd zchunk chunks blocks"
 
 
 def zmarch_grid(dx, dy, nout, tile_x, wx, wy, ry, want_per_simd, min_planes, chunked=True):
-    """zmarch_grid of tomobar_amd/csrc/tv_kernels.hip (ndf_grid, d4_grid and tgv_grid are copies with want_per_simd = 32 and
-    min_planes = 16), plus the chunk count the kernels derive from blocks / (8 * tiles_per_xcd)"""
+    """zmarch_grid of tomobar_amd/csrc/tv_kernels.hip (the zmarch_grid of zmarch_common.h, which NDF, Diff4th, LLT_ROF and
+    TGV share, is the same function with want_per_simd = 32 and min_planes = 16 written into it; tv_kernels.hip is pinned
+    by hash and keeps its own), plus the chunk count the kernels derive from blocks / (8 * tiles_per_xcd)"""
     gx = ceil_div(ceil_div(dx, tile_x), wx)
     gy = ceil_div(dy, wy * ry)
     tiles_per_xcd = ceil_div(gx * gy, 8)
@@ -84,30 +85,30 @@ class Launch:
 
 
 LAUNCHES = collections.OrderedDict((L.name, L) for L in [
-    # ndf_kernels.hip:102-108 (8 rows per lane, 2 x 2 waves), ndf_zmarch.inl:132 (62 columns), ndf_kernels.hip:75-76 (32, 16)
+    # ndf_kernels.hip:43-49 (8 rows per lane, 2 x 2 waves), ndf_zmarch.inl:132 (62 columns), zmarch_common.h:52-53 (32, 16)
     Launch("ndf", "NDF", 62, 2, 2, 8, 16, 32, (2, 3), [
         ("ndf_kernels.hip", "ndf_zmarch_launch<3, NDF_HUBER, 8, 2, 2>(a, st)"),
         ("ndf_kernels.hip", "ndf_zmarch_launch<2, NDF_TUKEY, 8, 2, 2>(a, st)"),
-        ("ndf_zmarch.inl", "ndf_grid(g, a.dx, a.dy, a.out_end - a.out_begin, 62, WX, WY, RY, ND == 3)"),
+        ("ndf_zmarch.inl", 'zmarch_grid(g, "NDF", a.dx, a.dy, a.out_end - a.out_begin, 62, WX, WY, RY, ND == 3)'),
         ("ndf_zmarch.inl", "template <int ND, int PEN, int RY, int WX, int WY>\nstatic int ndf_zmarch_launch"),
-        ("ndf_kernels.hip", "constexpr long want_per_simd = 32;\n    constexpr int min_planes = 16;")]),
+        ("zmarch_common.h", "constexpr long want_per_simd = 32;\n    constexpr int min_planes = 16;")]),
     # diff4th_kernels.hip (8 rows per lane, 2 x 2 waves), diff4th_zmarch.inl:177 (60 columns: two halo lanes either side, two
     # halo rows above and below)
     Launch("diff4th", "Diff4th", 60, 2, 2, 8, 16, 32, (2, 3), [
         ("diff4th_kernels.hip", "d4_zmarch_launch<3, 8, 2, 2>(a, st)"),
         ("diff4th_kernels.hip", "d4_zmarch_launch<2, 8, 2, 2>(a, st)"),
-        ("diff4th_zmarch.inl", "d4_grid(g, a.dx, a.dy, a.out_end - a.out_begin, 60, WX, WY, RY, ND == 3)"),
+        ("diff4th_zmarch.inl", 'zmarch_grid(g, "Diff4th", a.dx, a.dy, a.out_end - a.out_begin, 60, WX, WY, RY, ND == 3)'),
         ("diff4th_zmarch.inl", "template <int ND, int RY, int WX, int WY>\nstatic int d4_zmarch_launch"),
-        ("diff4th_kernels.hip", "constexpr long want_per_simd = 32;\n    constexpr int min_planes = 16;")], y_halo=2),
-    # tgv_kernels.hip:100-103 (dual and primal: 4 rows per lane, 2 x 2 waves), tgv_dual.inl:139 / tgv_primal.inl:141 (63)
+        ("zmarch_common.h", "constexpr long want_per_simd = 32;\n    constexpr int min_planes = 16;")], y_halo=2),
+    # tgv_kernels.hip:41-44 (dual and primal: 4 rows per lane, 2 x 2 waves), tgv_dual.inl:139 / tgv_primal.inl:141 (63)
     Launch("tgv", "TGV", 63, 2, 2, 4, 16, 32, (2, 3), [
         ("tgv_kernels.hip", "tgv_dual_launch<3, 4, 2, 2>(a, st) : tgv_dual_launch<2, 4, 2, 2>(a, st)"),
         ("tgv_kernels.hip", "tgv_primal_launch<3, 4, 2, 2>(a, st) : tgv_primal_launch<2, 4, 2, 2>(a, st)"),
-        ("tgv_dual.inl", "tgv_grid(g, a.dx, a.dy, a.dz, 63, WX, WY, RY, ND == 3)"),
-        ("tgv_primal.inl", "tgv_grid(g, a.dx, a.dy, a.dz, 63, WX, WY, RY, ND == 3)"),
+        ("tgv_dual.inl", 'zmarch_grid(g, "TGV", a.dx, a.dy, a.dz, 63, WX, WY, RY, ND == 3)'),
+        ("tgv_primal.inl", 'zmarch_grid(g, "TGV", a.dx, a.dy, a.dz, 63, WX, WY, RY, ND == 3)'),
         ("tgv_dual.inl", "template <int ND, int RY, int WX, int WY>\nstatic int tgv_dual_launch"),
         ("tgv_primal.inl", "template <int ND, int RY, int WX, int WY>\nstatic int tgv_primal_launch"),
-        ("tgv_kernels.hip", "constexpr long want_per_simd = 32;\n    constexpr int min_planes = 16;")]),
+        ("zmarch_common.h", "constexpr long want_per_simd = 32;\n    constexpr int min_planes = 16;")]),
     # tv_kernels.hip:763 (8 rows per lane, 2 x 2 waves), rof_zmarch.inl:253 (60 columns, 32 waves per SIMD, chunks >= 32)
     Launch("rof", "ROF_TV", 60, 2, 2, 8, 32, 32, (2, 3), [
         ("tv_kernels.hip", "return rof_zmarch_launch<ND, HALF, 3, 8, 2, 2>(a, st);"),

@@ -6,13 +6,13 @@ from _edge_shapes import (GROUPS, SCALE_EXPONENTS, Launch, Slab, _cases_of, chun
                           terraces, zero_share)
 
 # llt_rof_kernels.hip (8 rows per lane, 2 x 2 waves), llt_rof_zmarch.inl (60 columns: two halo lanes either side, two halo
-# rows above and below for E2), 32 waves per SIMD wanted, no chunk shorter than 16 planes
+# rows above and below for E2), zmarch_common.h (32 waves per SIMD wanted, no chunk shorter than 16 planes)
 LAUNCH = Launch("llt_rof", "LLT_ROF", 60, 2, 2, 8, 16, 32, (2, 3), [
     ("llt_rof_kernels.hip", "lr_zmarch_launch<3, 8, 2, 2>(a, st)"),
     ("llt_rof_kernels.hip", "lr_zmarch_launch<2, 8, 2, 2>(a, st)"),
-    ("llt_rof_zmarch.inl", "lr_grid(g, a.dx, a.dy, a.out_end - a.out_begin, 60, WX, WY, RY, ND == 3)"),
+    ("llt_rof_zmarch.inl", 'zmarch_grid(g, "LLT_ROF", a.dx, a.dy, a.out_end - a.out_begin, 60, WX, WY, RY, ND == 3)'),
     ("llt_rof_zmarch.inl", "template <int ND, int RY, int WX, int WY>\nstatic int lr_zmarch_launch"),
-    ("llt_rof_kernels.hip", "constexpr long want_per_simd = 32;\n    constexpr int min_planes = 16;")], y_halo=2)
+    ("zmarch_common.h", "constexpr long want_per_simd = 32;\n    constexpr int min_planes = 16;")], y_halo=2)
 
 CASES = _cases_of(LAUNCH)
 

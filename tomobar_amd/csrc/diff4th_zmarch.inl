@@ -1,5 +1,5 @@
 // One Diff4th iteration as a register-blocked z-march, both stages fused (docs/kernels/diff4th.md).  Included inside the
-// anonymous namespace of diff4th_kernels.hip (uses D4Args, D4Plane, d4_prev, d4_next).
+// anonymous namespace of diff4th_kernels.hip (uses D4Args; PlaneIO, wave_prev, wave_next of zmarch_common.h).
 //
 // A lane owns RY rows of one x column and walks z.  Stage 2 at a voxel needs the weighted second derivative W at the six
 // face neighbours, and W needs U at radius 1 (faces and the in-plane / cross-plane diagonals), so:
@@ -37,21 +37,21 @@ __device__ __forceinline__ void d4_weighted(const float (&zm)[RY + 4], const flo
     for (int w = 0; w < RY + 2; ++w) {
         const int u = w + 1;
         const float c = zc[u], cc = c + c;
-        const float p1 = d4_next(c), m1 = d4_prev(c);
+        const float p1 = wave_next(c), m1 = wave_prev(c);
         const float g1 = 0.5f * (p1 - m1);
         const float h1 = (p1 + m1) - cc;
         const float p2 = zc[u + 1], m2 = zc[u - 1];
         const float dy = p2 - m2;
         const float g2 = 0.5f * dy;
         const float h2 = (p2 + m2) - cc;
-        const float k12 = 0.25f * (d4_next(dy) - d4_prev(dy));
+        const float k12 = 0.25f * (wave_next(dy) - wave_prev(dy));
         float G = g1 * g1 + g2 * g2;
         float L = h1 + h2;
         float Q = (h1 * (g1 * g1) + h2 * (g2 * g2)) + 2.0f * ((g1 * g2) * k12);
         if (ND == 3) {
             const float g3 = 0.5f * dz[u];
             const float h3 = (zp[u] + zm[u]) - cc;
-            const float k13 = 0.25f * (d4_next(dz[u]) - d4_prev(dz[u]));
+            const float k13 = 0.25f * (wave_next(dz[u]) - wave_prev(dz[u]));
             const float k23 = 0.25f * (dz[u + 1] - dz[u - 1]);
             G = G + g3 * g3;
             L = L + h3;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(64 * WX * WY) void d4_zmarch_kernel(D4Args a, int g
     const unsigned xo = (unsigned)min(max(x, 0), dx - 1) * 4u;   // the clamped column: every load stays inside the plane
     const int wy0 = __builtin_amdgcn_readfirstlane(y0);
     const int pitch = dx * 4;
-    const D4Plane io{(int)(sz * 4)};
+    const PlaneIO io{(int)(sz * 4)};
     // slot q = row y0 - 2 + q (q < 2 and q >= RY + 2: the halo rows), clamped into the plane
     auto rowoff = [&](int q) __attribute__((always_inline)) { return min(max(wy0 - 2 + q, 0), dy - 1) * pitch; };
     auto load_plane = [&](float (&dst)[RY + 4], int p) __attribute__((always_inline)) {
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(64 * WX * WY) void d4_zmarch_kernel(D4Args a, int g
             const bool y_prev = y0 + r > 0, y_next = y0 + r < dy - 1;
             const float c = ua[r + 2];
             const float Wi = Wc[r + 1], W2 = Wi + Wi;
-            const float wxp = d4_next(Wi), wxm = d4_prev(Wi);
+            const float wxp = wave_next(Wi), wxm = wave_prev(Wi);
             const float b1 = ((x_next ? wxp : Wi) + (x_prev ? wxm : Wi)) - W2;
             const float b2 = ((y_next ? Wc[r + 2] : Wi) + (y_prev ? Wc[r] : Wi)) - W2;
             float B = b1 + b2;
@@ -173,8 +173,8 @@ __global__ __launch_bounds__(64 * WX * WY) void d4_zmarch_kernel(D4Args a, int g
 template <int ND, int RY, int WX, int WY>
 static int d4_zmarch_launch(const D4Args &a, hipStream_t st)
 {
-    D4Grid g;
-    if (int rc = d4_grid(g, a.dx, a.dy, a.out_end - a.out_begin, 60, WX, WY, RY, ND == 3)) return rc;
+    ZmarchGrid g;
+    if (int rc = zmarch_grid(g, "Diff4th", a.dx, a.dy, a.out_end - a.out_begin, 60, WX, WY, RY, ND == 3)) return rc;
     d4_zmarch_kernel<ND, RY, WX, WY><<<(unsigned)g.blocks, 64 * WX * WY, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd, g.zchunk);
     return TOMO_OK;
 }

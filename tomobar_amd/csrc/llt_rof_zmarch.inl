@@ -1,5 +1,5 @@
 // One LLT_ROF iteration as a register-blocked z-march, both stages fused (docs/kernels/llt_rof.md).  Included inside the
-// anonymous namespace of llt_rof_kernels.hip (uses LrArgs, LrPlane, lr_prev, lr_next).
+// anonymous namespace of llt_rof_kernels.hip (uses LrArgs; PlaneIO, wave_prev, wave_next of zmarch_common.h).
 //
 // A lane owns RY rows of one x column and walks z.  Stage 2 at a voxel needs the LLT flux E_d at i and i +- e_d and the ROF
 // flux R_d at i and i - e_d; E_d needs U at radius 1 along d, R_d the norm n of the forward differences of all axes, so:
@@ -42,7 +42,7 @@ __device__ __forceinline__ void lr_r3(const float (&zc)[RY + 4], const float (&z
 #pragma unroll
     for (int r = 0; r < RY; ++r) {
         const float c = zc[r + 2];
-        const float a1 = lr_next(c) - c, a2 = zc[r + 3] - c, a3 = zp[r + 2] - c;
+        const float a1 = wave_next(c) - c, a2 = zc[r + 3] - c, a3 = zp[r + 2] - c;
         R[r] = a3 / sqrtf(((a1 * a1 + a2 * a2) + a3 * a3) + 1e-8f);
     }
 }
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(64 * WX * WY) void lr_zmarch_kernel(LrArgs a, int g
     const unsigned xo = (unsigned)min(max(x, 0), dx - 1) * 4u;   // the clamped column: every load stays inside the plane
     const int wy0 = __builtin_amdgcn_readfirstlane(y0);
     const int pitch = dx * 4;
-    const LrPlane io{(int)(sz * 4)};
+    const PlaneIO io{(int)(sz * 4)};
     // slot q = row y0 - 2 + q (q < 2 and q >= RY + 2: the halo rows), clamped into the plane
     auto rowoff = [&](int q) __attribute__((always_inline)) { return min(max(wy0 - 2 + q, 0), dy - 1) * pitch; };
     auto load_plane = [&](float (&dst)[RY + 4], int p) __attribute__((always_inline)) {
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(64 * WX * WY) void lr_zmarch_kernel(LrArgs a, int g
         float R2m;
         {
             const float c = ua[1];
-            const float a1 = lr_next(c) - c, a2 = ua[2] - c;
+            const float a1 = wave_next(c) - c, a2 = ua[2] - c;
             float s = a1 * a1 + a2 * a2;
             if (ND == 3) { const float a3 = ub[1] - c; s = s + a3 * a3; }
             R2m = a2 / sqrtf(s + eps);   // the first own row selects zero where the array has no row above it
@@ -144,21 +144,21 @@ __global__ __launch_bounds__(64 * WX * WY) void lr_zmarch_kernel(LrArgs a, int g
         for (int r = 0; r < RY; ++r) {
             const bool y_prev = y0 + r > 0, y_next = y0 + r < dy - 1;
             const float c = ua[r + 2], cc = c + c;
-            const float p1 = lr_next(c), m1 = lr_prev(c);
+            const float p1 = wave_next(c), m1 = wave_prev(c);
             const float a1 = p1 - c, a2 = ua[r + 3] - c;
             float a3 = 0.0f;
             float s = a1 * a1 + a2 * a2;
             if (ND == 3) { a3 = ub[r + 2] - c; s = s + a3 * a3; }
             const float n = sqrtf(s + eps);
             const float R1 = a1 / n, R2 = a2 / n;
-            const float R1m = lr_prev(R1);
+            const float R1m = wave_prev(R1);
             const float v1 = R1 - (x_prev ? R1m : 0.0f);
             const float v2 = R2 - (y_prev ? R2m : 0.0f);
             R2m = R2;
             float V = v1 + v2;
 
             const float E1 = lr_sign_like((p1 + m1) - cc);
-            const float e1p = lr_next(E1), e1m = lr_prev(E1);
+            const float e1p = wave_next(E1), e1m = wave_prev(E1);
             const float b1 = ((x_next ? e1p : E1) + (x_prev ? e1m : E1)) - (E1 + E1);
             const float Ey = E2[r + 1];
             const float b2 = ((y_next ? E2[r + 2] : Ey) + (y_prev ? E2[r] : Ey)) - (Ey + Ey);
@@ -188,8 +188,8 @@ __global__ __launch_bounds__(64 * WX * WY) void lr_zmarch_kernel(LrArgs a, int g
 template <int ND, int RY, int WX, int WY>
 static int lr_zmarch_launch(const LrArgs &a, hipStream_t st)
 {
-    LrGrid g;
-    if (int rc = lr_grid(g, a.dx, a.dy, a.out_end - a.out_begin, 60, WX, WY, RY, ND == 3)) return rc;
+    ZmarchGrid g;
+    if (int rc = zmarch_grid(g, "LLT_ROF", a.dx, a.dy, a.out_end - a.out_begin, 60, WX, WY, RY, ND == 3)) return rc;
     lr_zmarch_kernel<ND, RY, WX, WY><<<(unsigned)g.blocks, 64 * WX * WY, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd, g.zchunk);
     return TOMO_OK;
 }

@@ -1,5 +1,5 @@
 // One NDF iteration as a register-blocked z-march (docs/kernels/ndf.md).  Included inside the anonymous namespace of
-// ndf_kernels.hip (uses NdfArgs, NdfPlane, ndf_prev, ndf_next, the NDF_* penalty names).
+// ndf_kernels.hip (uses NdfArgs; PlaneIO, wave_prev, wave_next of zmarch_common.h, the NDF_* penalty names).
 //
 // A lane owns RY rows of one x column and walks z.  The flux of a voxel's three FORWARD differences is evaluated once; the
 // flux of a backward difference is the neighbour's forward flux with the sign turned -- the three penalties are odd
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(64 * WX * WY) void ndf_zmarch_kernel(NdfArgs a, int
     const unsigned xo = (unsigned)min(max(x, 0), dx - 1) * 4u;   // the clamped column: every load stays inside the plane
     const int wy0 = __builtin_amdgcn_readfirstlane(y0);
     const int pitch = dx * 4;
-    const NdfPlane io{(int)(sz * 4)};
+    const PlaneIO io{(int)(sz * 4)};
     // slot q = row y0 - 1 + q (q = 0 and q = RY + 1: the halo rows), clamped into the plane
     auto rowoff = [&](int q) __attribute__((always_inline)) { return min(max(wy0 - 1 + q, 0), dy - 1) * pitch; };
     const float sigma = a.sigma;
@@ -98,11 +98,11 @@ __global__ __launch_bounds__(64 * WX * WY) void ndf_zmarch_kernel(NdfArgs a, int
         for (int r = 0; r < RY; ++r) {
             const bool y_prev = y0 + r > 0, y_next = y0 + r < dy - 1;
             const float c = cur[r + 1];
-            const float cx = ndf_next(c);
+            const float cx = wave_next(c);
             float g1, gn1, g2, gn2;
             ndf_flux<PEN>(x_next ? cx - c : 0.0f, sigma, g1, gn1);
             ndf_flux<PEN>(y_next ? cur[r + 2] - c : 0.0f, sigma, g2, gn2);
-            const float m1 = ndf_prev(gn1);
+            const float m1 = wave_prev(gn1);
             float S = ((g1 + (x_prev ? m1 : 0.0f)) + g2) + (y_prev ? gny : 0.0f);
             gny = gn2;
             if (ND == 3) {
@@ -128,8 +128,8 @@ __global__ __launch_bounds__(64 * WX * WY) void ndf_zmarch_kernel(NdfArgs a, int
 template <int ND, int PEN, int RY, int WX, int WY>
 static int ndf_zmarch_launch(const NdfArgs &a, hipStream_t st)
 {
-    NdfGrid g;
-    if (int rc = ndf_grid(g, a.dx, a.dy, a.out_end - a.out_begin, 62, WX, WY, RY, ND == 3)) return rc;
+    ZmarchGrid g;
+    if (int rc = zmarch_grid(g, "NDF", a.dx, a.dy, a.out_end - a.out_begin, 62, WX, WY, RY, ND == 3)) return rc;
     ndf_zmarch_kernel<ND, PEN, RY, WX, WY><<<(unsigned)g.blocks, 64 * WX * WY, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd, g.zchunk);
     return TOMO_OK;
 }

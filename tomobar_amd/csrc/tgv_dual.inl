@@ -1,6 +1,6 @@
 // TGV dual launch (steps 1-2 of an iteration, docs/kernels/tgv.md): P and Q ascend along the forward differences of the
 // barred primal fields and are projected onto their balls, in place.  Included inside the anonymous namespace of
-// tgv_kernels.hip (uses TgvArgs, TgvPlane, tgv_next, the Q index names).
+// tgv_kernels.hip (uses TgvArgs; PlaneIO, wave_next of zmarch_common.h, the Q index names).
 //
 // z-march on the skeleton of rof_zmarch.inl: a lane owns RY rows of one x column and walks z.  The +x neighbour is the next
 // lane (lane 63 of a wave is a halo lane: 63 columns per wave), the +y neighbour the next register (one halo row below the
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(64 * WX * WY) void tgv_dual_kernel(TgvArgs a, int g
     const unsigned xo = (unsigned)min(x, dx - 1) * 4u;   // the clamped column: every load stays inside the plane
     const int wy0 = __builtin_amdgcn_readfirstlane(y0);
     const int pitch = dx * 4;
-    const TgvPlane io{(int)(sz * 4)};
+    const PlaneIO io{(int)(sz * 4)};
     // slot q = row y0 + q (q = RY: the halo row), clamped into the plane
     auto rowoff = [&](int q) __attribute__((always_inline)) { return min(wy0 + q, dy - 1) * pitch; };
 
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64 * WX * WY) void tgv_dual_kernel(TgvArgs a, int g
 #pragma unroll
             for (int A = 0; A < NB; ++A) {
                 const float c = cur[A][r];
-                const float cx = tgv_next(c);
+                const float cx = wave_next(c);
                 F[A][0] = x_next ? cx - c : 0.0f;
                 F[A][1] = y_next ? cur[A][r + 1] - c : 0.0f;
                 F[A][2] = (ND == 3 && z_next) ? nxt[A][r] - c : 0.0f;
@@ -135,8 +135,8 @@ __global__ __launch_bounds__(64 * WX * WY) void tgv_dual_kernel(TgvArgs a, int g
 template <int ND, int RY, int WX, int WY>
 static int tgv_dual_launch(const TgvArgs &a, hipStream_t st)
 {
-    TgvGrid g;
-    if (int rc = tgv_grid(g, a.dx, a.dy, a.dz, 63, WX, WY, RY, ND == 3)) return rc;
+    ZmarchGrid g;
+    if (int rc = zmarch_grid(g, "TGV", a.dx, a.dy, a.dz, 63, WX, WY, RY, ND == 3)) return rc;
     tgv_dual_kernel<ND, RY, WX, WY><<<(unsigned)g.blocks, 64 * WX * WY, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd, g.zchunk);
     return TOMO_OK;
 }

@@ -14,41 +14,12 @@
 // write, so nothing is ping-ponged.  U lives in the caller's output array, the other 16 (3D) / 10 (2D) fields in the
 // placed TV arena.  Algorithmic traffic: 44 floats = 176 B per voxel and iteration in 3D, 28 floats = 112 B in 2D.
 //
-// tv_kernels.hip is pinned by hash (profiles/pmc_traffic.json), so the few host helpers this file shares with it in spirit --
-// the z-march grid, the array skew, the tolerance rule -- are restated here instead of being moved into a common header.
-#include "tomo_common.h"
-#include <cmath>
+// The wave shifts, the plane I/O, the z-march grid, the array skew and the tolerance rule are the one copy in
+// zmarch_common.h, shared with ndf_kernels.hip, diff4th_kernels.hip and llt_rof_kernels.hip.
+// tv_kernels.hip keeps a copy of its own: it is pinned by hash (profiles/pmc_traffic.json), so it cannot include the header.
+#include "zmarch_common.h"
 
 namespace {
-
-// one-lane wave shifts (gfx9 DPP, a single VALU move); the lane shifted in at the wave's end is a halo lane's, never consumed
-__device__ __forceinline__ float tgv_prev(float v)  // lane i <- lane i-1
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138 /*wave_shr:1*/, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float tgv_next(float v)  // lane i <- lane i+1
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130 /*wave_shl:1*/, 0xf, 0xf, true));
-}
-
-// Plane-relative buffer addressing (see PlaneIO in tv_kernels.hip): `xo` = byte offset of the lane's column inside a row
-// (VGPR), `ro` = byte offset of the row inside the plane (wave-uniform, the instruction's soffset).  One descriptor per
-// (array, plane); callers clamp column and row, so `ro + xo` always lies inside the plane.
-struct TgvPlane {
-    int bytes;  // size of one float plane in bytes
-    __device__ __forceinline__ __amdgpu_buffer_rsrc_t rs(const void *plane) const
-    {
-        return __builtin_amdgcn_make_buffer_rsrc((void *)plane, 0, bytes, 0x00020000);
-    }
-    __device__ __forceinline__ float ld(const float *plane, unsigned xo, int ro) const
-    {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs(plane), (int)xo, ro, 0));
-    }
-    __device__ __forceinline__ void st(float *plane, unsigned xo, int ro, float v) const
-    {
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), rs(plane), (int)xo, ro, 0);
-    }
-};
 
 // Q components; 2D uses the first three
 enum { TQ11 = 0, TQ22 = 1, TQ12 = 2, TQ33 = 3, TQ13 = 4, TQ23 = 5 };
@@ -60,36 +31,6 @@ struct TgvArgs {
     int dx, dy, dz;
     float lambda, alpha1, alpha0, tau, sigma;
 };
-
-// The launch grid of a z-march (zmarch_grid of tv_kernels.hip, with ROF_TV's targets): a workgroup of wx x wy waves covers
-// wx tiles of `tile_x` columns by wy * ry rows; 3D volumes are cut into z-chunks, enough for 32 waves on each of the chip's
-// 256 x 4 SIMDs but none shorter than 16 planes; workgroups are numbered so that each of the 8 XCDs gets `tiles_per_xcd`
-// xy tiles of every chunk.
-struct TgvGrid {
-    int gx, gy, tiles_per_xcd, zchunk;
-    long blocks;
-};
-static int tgv_grid(TgvGrid &g, int dx, int dy, int dz, int tile_x, int wx, int wy, int ry, bool chunked)
-{
-    constexpr long want_per_simd = 32;
-    constexpr int min_planes = 16;
-    g.gx = ceil_div(ceil_div(dx, tile_x), wx);
-    g.gy = ceil_div(dy, wy * ry);
-    g.tiles_per_xcd = ceil_div(g.gx * g.gy, 8);
-    int chunks = 1;
-    if (chunked) {
-        const long waves_xy = (long)g.gx * g.gy * wx * wy;
-        chunks = (int)((256L * 4 * want_per_simd + waves_xy - 1) / waves_xy);
-        const int max_chunks = ceil_div(dz, min_planes);
-        if (chunks > max_chunks) chunks = max_chunks;
-        if (chunks < 1) chunks = 1;
-    }
-    g.zchunk = ceil_div(dz, chunks);
-    chunks = ceil_div(dz, g.zchunk);
-    g.blocks = 8L * g.tiles_per_xcd * chunks;
-    if (g.blocks > 0x7fffffffL) return tomo_fail(TOMO_E_INVALID, "volume too large for one TGV launch");
-    return TOMO_OK;
-}
 
 #include "tgv_dual.inl"
 #include "tgv_primal.inl"
@@ -106,15 +47,6 @@ static int tgv_launch_iteration(const TgvArgs &a, int nd, hipStream_t st)
     return TOMO_OK;
 }
 
-inline size_t tgv_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// bytes between consecutive work arrays beyond the plain packing (tv_skew of tv_kernels.hip: equal-sized arrays laid end to
-// end put the same voxel of every array on the same HBM channel and bank)
-constexpr size_t TGV_SKEW = 69888;
-
-// the early-stopping rule of tomo_pdtv_tol / tomo_roftv_tol (include/tomo_mi355x.h)
-constexpr int TGV_TOL_INTERVAL = 6, TGV_TOL_MIN_SAVED = 3;
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ C-ABI
@@ -122,7 +54,7 @@ extern "C" size_t tomo_tgv_scratch_bytes(int dx, int dy, int dz, int nd)
 {
     if (nd == 2) dz = 1;
     const size_t narr = nd == 2 ? 10 : 16;   // U-bar, V, V-bar, P (nd each), Q (3 or 6)
-    return narr * (tgv_align_up((size_t)dx * dy * dz * sizeof(float), 256) + TGV_SKEW);
+    return narr * work_array_bytes((size_t)dx * dy * dz);
 }
 
 extern "C" int tomo_tgv(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
@@ -152,15 +84,11 @@ extern "C" int tomo_tgv(int device, const float *in_dev, float *out_dev, int dx,
     void *base = nullptr;
     int rc = tomo_arena_get(device, st, ARENA_TV, total, &base, true);
     if (rc != TOMO_OK) return rc;
-    float *snap = nullptr;   // U_{n-6}: a block of its own, the TV arena keeps its size and placement
-    if (tol > 0.0 && iters >= TGV_TOL_INTERVAL + TGV_TOL_MIN_SAVED) {
-        void *p = nullptr;
-        rc = tomo_arena_get(device, st, ARENA_TVSNAP, nvox * sizeof(float), &p);
-        if (rc != TOMO_OK) return rc;
-        snap = (float *)p;
-    }
+    float *snap;
+    rc = tol_snapshot(device, st, tol, iters, nvox, snap);
+    if (rc != TOMO_OK) return rc;
 
-    const size_t step = tgv_align_up(nvox * sizeof(float), 256) + TGV_SKEW;
+    const size_t step = work_array_bytes(nvox);
     char *cur = (char *)base;
     auto take = [&]() { float *p = (float *)cur; cur += step; return p; };
     TgvArgs a;
@@ -181,15 +109,12 @@ extern "C" int tomo_tgv(int device, const float *in_dev, float *out_dev, int dx,
     for (int n = 1; n <= iters; ++n) {
         rc = tgv_launch_iteration(a, nd, st);
         if (rc != TOMO_OK) return rc;
-        if (snap == nullptr || n % TGV_TOL_INTERVAL != 0 || iters - n < TGV_TOL_MIN_SAVED) continue;
-        // the first check reads the caller's input as the reference and only writes the snapshot; later ones compare with
-        // the snapshot and refresh it in the same pass
-        double s[2];
-        rc = tomo_rel_change(out_dev, n == TGV_TOL_INTERVAL ? in_dev : snap, snap, nvox, s, st);
+        if (!tol_due(snap, n, iters)) continue;
+        TolCheck c;
+        rc = tol_check(c, n, out_dev, in_dev, snap, nvox, tol, st);
         if (rc != TOMO_OK) return rc;
-        const double d = s[0] == 0.0 ? 0.0 : (s[1] == 0.0 ? INFINITY : sqrt(s[0] / s[1]));
-        if (last_rel_change) *last_rel_change = d;
-        if (d < tol) {
+        if (last_rel_change) *last_rel_change = c.d;
+        if (c.stop) {
             if (iters_done) *iters_done = n;
             return TOMO_OK;
         }

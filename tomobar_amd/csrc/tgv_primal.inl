@@ -1,6 +1,6 @@
 // TGV primal launch (steps 3-4 of an iteration, docs/kernels/tgv.md): U and V descend along the backward differences
 // (negative adjoints of the forward ones) of the new duals and are extrapolated into U-bar / V-bar, in place.  Included
-// inside the anonymous namespace of tgv_kernels.hip (uses TgvArgs, TgvPlane, tgv_prev, the Q index names).
+// inside the anonymous namespace of tgv_kernels.hip (uses TgvArgs; PlaneIO, wave_prev of zmarch_common.h, the Q index names).
 //
 // The mirror image of tgv_dual.inl: the -x neighbour is the previous lane (lane 0 of a wave is the halo lane), the -y
 // neighbour the previous register (one halo row above the tile, only for the four fields that are differenced along y),
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(64 * WX * WY) void tgv_primal_kernel(TgvArgs a, int
     const unsigned xo = (unsigned)min(max(x, 0), dx - 1) * 4u;   // the clamped column: every load stays inside the plane
     const int wy0 = __builtin_amdgcn_readfirstlane(y0);
     const int pitch = dx * 4;
-    const TgvPlane io{(int)(sz * 4)};
+    const PlaneIO io{(int)(sz * 4)};
     // slot q = row y0 - 1 + q (q = 0: the halo row), clamped into the plane
     auto rowoff = [&](int q) __attribute__((always_inline)) { return min(max(wy0 - 1 + q, 0), dy - 1) * pitch; };
 
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(64 * WX * WY) void tgv_primal_kernel(TgvArgs a, int
         for (int r = 0; r < RY; ++r) {
             const bool y_prev = y0 + r > 0;
             // B_d(a)[i] = a[i] - a[i - e_d], a[i] itself on the first index of the axis
-            auto bx = [&](float c) __attribute__((always_inline)) { const float l = tgv_prev(c); return x_prev ? c - l : c; };
+            auto bx = [&](float c) __attribute__((always_inline)) { const float l = wave_prev(c); return x_prev ? c - l : c; };
             auto by = [&](float c, float up) __attribute__((always_inline)) { return y_prev ? c - up : c; };
             auto bz = [&](float c, float below) __attribute__((always_inline)) { return z_prev ? c - below : c; };
             // step 3
@@ -137,8 +137,8 @@ __global__ __launch_bounds__(64 * WX * WY) void tgv_primal_kernel(TgvArgs a, int
 template <int ND, int RY, int WX, int WY>
 static int tgv_primal_launch(const TgvArgs &a, hipStream_t st)
 {
-    TgvGrid g;
-    if (int rc = tgv_grid(g, a.dx, a.dy, a.dz, 63, WX, WY, RY, ND == 3)) return rc;
+    ZmarchGrid g;
+    if (int rc = zmarch_grid(g, "TGV", a.dx, a.dy, a.dz, 63, WX, WY, RY, ND == 3)) return rc;
     tgv_primal_kernel<ND, RY, WX, WY><<<(unsigned)g.blocks, 64 * WX * WY, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd, g.zchunk);
     return TOMO_OK;
 }

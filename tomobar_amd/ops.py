@@ -255,17 +255,23 @@ def roftv_tol(data, out, lam, tau, iterations, half, tolerance):
     return out, int(done.value), float(last.value)
 
 
+def _marched(entry, data, out, scalars, iterations, tolerance, ints=()):
+    """The call behind tgv / ndf / diff4th / llt_rof: `entry` is the C entry point, `scalars` its float parameters and `ints`
+    the integer ones that follow them.  Returns (out, iterations_done, rel_change)."""
+    dx, dy, dz, nd = _tv_dims(data)
+    done, last = C.c_int(0), C.c_double(float("nan"))
+    with torch.cuda.device(data.device):
+        L.check(getattr(L.lib(), entry)(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, *map(float, scalars),
+                                        *map(int, ints), int(iterations), float(tolerance), C.byref(done), C.byref(last),
+                                        stream_ptr(data)))
+    return out, int(done.value), float(last.value)
+
+
 def tgv(data, out, lam, alpha1, alpha0, tau, sigma, iterations, tolerance=0.0):
     """Second-order TGV prox (tomo_tgv; the algorithm: docs/kernels/tgv.md): `iterations` Chambolle-Pock iterations of
     `data` into `out` (a different array: U is iterated there).  Returns (out, iterations_done, rel_change) -- the last
     relative change the stopping rule evaluated, NaN if none (tolerance 0 = off)."""
-    dx, dy, dz, nd = _tv_dims(data)
-    done, last = C.c_int(0), C.c_double(float("nan"))
-    with torch.cuda.device(data.device):
-        L.check(L.lib().tomo_tgv(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, float(lam), float(alpha1),
-                                 float(alpha0), float(tau), float(sigma), int(iterations), float(tolerance),
-                                 C.byref(done), C.byref(last), stream_ptr(data)))
-    return out, int(done.value), float(last.value)
+    return _marched("tomo_tgv", data, out, (lam, alpha1, alpha0, tau, sigma), iterations, tolerance)
 
 
 def ndf(data, out, lam, sigma, tau, penalty, iterations, tolerance=0.0):
@@ -273,14 +279,7 @@ def ndf(data, out, lam, sigma, tau, penalty, iterations, tolerance=0.0):
     `data` into `out` (a different array: the iterations ping-pong through it; `data` is never written).  `penalty` is
     "Huber", "PM" or "Tukey"; `lam`, `sigma` (the edge threshold) and `tau` are float32 scalars.  Returns (out,
     iterations_done, rel_change) -- the last relative change the stopping rule evaluated, NaN if none (tolerance 0 = off)."""
-    dx, dy, dz, nd = _tv_dims(data)
-    pen = L.ndf_penalty_id(penalty)
-    done, last = C.c_int(0), C.c_double(float("nan"))
-    with torch.cuda.device(data.device):
-        L.check(L.lib().tomo_ndf(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, float(lam), float(sigma),
-                                 float(tau), pen, int(iterations), float(tolerance), C.byref(done), C.byref(last),
-                                 stream_ptr(data)))
-    return out, int(done.value), float(last.value)
+    return _marched("tomo_ndf", data, out, (lam, sigma, tau), iterations, tolerance, ints=(L.ndf_penalty_id(penalty),))
 
 
 def diff4th(data, out, lam, sigma, tau, iterations, tolerance=0.0):
@@ -288,13 +287,7 @@ def diff4th(data, out, lam, sigma, tau, iterations, tolerance=0.0):
     time-marching steps of `data` into `out` (a different array: the iterations ping-pong through it; `data` is never
     written).  `lam`, `sigma` (the edge threshold) and `tau` are float32 scalars.  Returns (out, iterations_done,
     rel_change) -- the last relative change the stopping rule evaluated, NaN if none (tolerance 0 = off)."""
-    dx, dy, dz, nd = _tv_dims(data)
-    done, last = C.c_int(0), C.c_double(float("nan"))
-    with torch.cuda.device(data.device):
-        L.check(L.lib().tomo_diff4th(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, float(lam), float(sigma),
-                                     float(tau), int(iterations), float(tolerance), C.byref(done), C.byref(last),
-                                     stream_ptr(data)))
-    return out, int(done.value), float(last.value)
+    return _marched("tomo_diff4th", data, out, (lam, sigma, tau), iterations, tolerance)
 
 
 def llt_rof(data, out, lam_rof, lam_llt, tau, iterations, tolerance=0.0):
@@ -302,13 +295,7 @@ def llt_rof(data, out, lam_rof, lam_llt, tau, iterations, tolerance=0.0):
     time-marching steps of `data` into `out` (a different array: the iterations ping-pong through it; `data` is never
     written).  `lam_rof`, `lam_llt` (the weights of the two terms) and `tau` are float32 scalars.  Returns (out,
     iterations_done, rel_change) -- the last relative change the stopping rule evaluated, NaN if none (tolerance 0 = off)."""
-    dx, dy, dz, nd = _tv_dims(data)
-    done, last = C.c_int(0), C.c_double(float("nan"))
-    with torch.cuda.device(data.device):
-        L.check(L.lib().tomo_llt_rof(data.device.index, ptr(data), ptr(out), dx, dy, dz, nd, float(lam_rof), float(lam_llt),
-                                     float(tau), int(iterations), float(tolerance), C.byref(done), C.byref(last),
-                                     stream_ptr(data)))
-    return out, int(done.value), float(last.value)
+    return _marched("tomo_llt_rof", data, out, (lam_rof, lam_llt, tau), iterations, tolerance)
 
 
 _variant_state = threading.local()   # mirror of the library's per-thread switches, per flavour: lets `variant()` restore

@@ -122,17 +122,11 @@ def check_prox_available(self, vol_shape, _regularisation_: dict) -> None:
     method = _regularisation_.get("method")
     if method is None or "ROF_TV" in method or "PD_TV" in method:
         return
-    if "TGV" not in method:
-        if "NDF" in method and _regularisation_.get("half_precision", False):
-            raise ValueError("NDF does not support half_precision=True")
-        if "NDF" not in method and "Diff4th" in method and _regularisation_.get("half_precision", False):
-            raise ValueError("Diff4th does not support half_precision=True")
-        if ("NDF" not in method and "Diff4th" not in method and "LLT_ROF" in method
-                and _regularisation_.get("half_precision", False)):
-            raise ValueError("LLT_ROF does not support half_precision=True")
+    kind = next((k for k in ("TGV", "NDF", "Diff4th", "LLT_ROF") if k in method), None)   # the order prox_regul dispatches in
+    if kind is not None and _regularisation_.get("half_precision", False):
+        raise ValueError(f"{kind} does not support half_precision=True")
+    if kind != "TGV":
         return
-    if _regularisation_.get("half_precision", False):
-        raise ValueError("TGV does not support half_precision=True")
     shape = tuple(int(v) for v in vol_shape)
     if getattr(self, "slab", None) is not None and len(shape) == 3 and min(shape) > 1:
         raise ValueError("TGV is not available in z-slab mode")
@@ -171,6 +165,18 @@ def _prepare(data, gpu_id: int):
 def _finish(result, is2d, axis, orig_shape, out, given=None):
     result = result.unsqueeze(axis) if is2d else result
     return ops.like(result, given) if out is None else out.view(orig_shape)
+
+
+def _marched(run, data, gpu_id: int, out, tolerance):
+    """The shared body of TGV_cupy / NDF_cupy / Diff4th_cupy / LLT_ROF_cupy: ``run(d, res, tolerance)`` is the ops call, which
+    returns (res, iterations_done, rel_change)."""
+    tolerance = check_tolerance(tolerance, "tolerance")
+    orig_shape = tuple(data.shape)
+    d, is2d, axis = _prepare(data, gpu_id)
+    res = torch.empty_like(d) if out is None else out.view(d.shape)
+    _, done, change = run(d, res, tolerance)
+    _record(done, change)
+    return _finish(res, is2d, axis, orig_shape, out, data)
 
 
 def ROF_TV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int = 3000,
@@ -230,17 +236,12 @@ def TGV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int = 10
     float32 result equals the numpy restatement tests/_tgv_oracle.py bit for bit.  ``tolerance`` > 0 stops the iterations
     early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after which iteration.  There is no
     non-negativity switch (the drivers clamp before the prox) and no binary16 storage."""
-    tolerance = check_tolerance(tolerance, "tolerance")
-    orig_shape = tuple(data.shape)
-    d, is2d, axis = _prepare(data, gpu_id)
-    # float32 scalars, formed the way PD_TV_cupy forms its own
-    lam = np.float32(regularisation_parameter)
-    tau = np.float32(np.float32(1.0) / np.sqrt(np.float32(lipschitz_const)))
-    sigma = tau
-    res = torch.empty_like(d) if out is None else out.view(d.shape)
-    _, done, change = ops.tgv(d, res, lam, np.float32(alpha1), np.float32(alpha0), tau, sigma, iterations, tolerance)
-    _record(done, change)
-    return _finish(res, is2d, axis, orig_shape, out, data)
+    def run(d, res, tolerance):
+        # float32 scalars, formed the way PD_TV_cupy forms its own
+        lam = np.float32(regularisation_parameter)
+        tau = np.float32(np.float32(1.0) / np.sqrt(np.float32(lipschitz_const)))
+        return ops.tgv(d, res, lam, np.float32(alpha1), np.float32(alpha0), tau, tau, iterations, tolerance)
+    return _marched(run, data, gpu_id, out, tolerance)
 
 
 def NDF_cupy(data, regularisation_parameter: float = 1e-05, edge_parameter: float = 0.01, iterations: int = 1000,
@@ -258,14 +259,9 @@ def NDF_cupy(data, regularisation_parameter: float = 1e-05, edge_parameter: floa
     There is no non-negativity switch (the drivers clamp before the prox) and no binary16 storage."""
     from ._lib import ndf_penalty_id
     ndf_penalty_id(penalty_type)   # an unknown penalty: ValueError before anything is moved to the device
-    tolerance = check_tolerance(tolerance, "tolerance")
-    orig_shape = tuple(data.shape)
-    d, is2d, axis = _prepare(data, gpu_id)
-    res = torch.empty_like(d) if out is None else out.view(d.shape)
-    _, done, change = ops.ndf(d, res, np.float32(regularisation_parameter), np.float32(edge_parameter),
-                              np.float32(time_marching_parameter), penalty_type, iterations, tolerance)
-    _record(done, change)
-    return _finish(res, is2d, axis, orig_shape, out, data)
+    return _marched(lambda d, res, tol: ops.ndf(d, res, np.float32(regularisation_parameter), np.float32(edge_parameter),
+                                                np.float32(time_marching_parameter), penalty_type, iterations, tol),
+                    data, gpu_id, out, tolerance)
 
 
 def Diff4th_cupy(data, regularisation_parameter: float = 1e-05, edge_parameter: float = 0.01, iterations: int = 1000,
@@ -281,14 +277,9 @@ def Diff4th_cupy(data, regularisation_parameter: float = 1e-05, edge_parameter: 
     formula-level parity, unpinned; the float32 result equals the numpy restatement tests/_diff4th_oracle.py bit for bit.
     ``tolerance`` > 0 stops the iterations early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after
     which iteration.  There is no non-negativity switch (the drivers clamp before the prox) and no binary16 storage."""
-    tolerance = check_tolerance(tolerance, "tolerance")
-    orig_shape = tuple(data.shape)
-    d, is2d, axis = _prepare(data, gpu_id)
-    res = torch.empty_like(d) if out is None else out.view(d.shape)
-    _, done, change = ops.diff4th(d, res, np.float32(regularisation_parameter), np.float32(edge_parameter),
-                                  np.float32(time_marching_parameter), iterations, tolerance)
-    _record(done, change)
-    return _finish(res, is2d, axis, orig_shape, out, data)
+    return _marched(lambda d, res, tol: ops.diff4th(d, res, np.float32(regularisation_parameter), np.float32(edge_parameter),
+                                                    np.float32(time_marching_parameter), iterations, tol),
+                    data, gpu_id, out, tolerance)
 
 
 def LLT_ROF_cupy(data, regularisation_parameterROF: float = 1e-05, regularisation_parameterLLT: float = 1e-05,
@@ -306,14 +297,10 @@ def LLT_ROF_cupy(data, regularisation_parameterROF: float = 1e-05, regularisatio
     formula-level parity, unpinned; the float32 result equals the numpy restatement tests/_llt_rof_oracle.py bit for bit.
     ``tolerance`` > 0 stops the iterations early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after
     which iteration.  There is no non-negativity switch (the drivers clamp before the prox) and no binary16 storage."""
-    tolerance = check_tolerance(tolerance, "tolerance")
-    orig_shape = tuple(data.shape)
-    d, is2d, axis = _prepare(data, gpu_device)
-    res = torch.empty_like(d) if out is None else out.view(d.shape)
-    _, done, change = ops.llt_rof(d, res, np.float32(regularisation_parameterROF), np.float32(regularisation_parameterLLT),
-                                  np.float32(time_marching_parameter), iterations, tolerance)
-    _record(done, change)
-    return _finish(res, is2d, axis, orig_shape, out, data)
+    return _marched(lambda d, res, tol: ops.llt_rof(d, res, np.float32(regularisation_parameterROF),
+                                                    np.float32(regularisation_parameterLLT),
+                                                    np.float32(time_marching_parameter), iterations, tol),
+                    data, gpu_device, out, tolerance)
 
 
 def _check_if_input_2d_or_3d(data) -> Tuple[torch.Tensor, bool, int]:

@@ -716,20 +716,20 @@ def rof_tv_slab(data: torch.Tensor, comm, regularisation_parameter, iterations, 
     return res.clone()
 
 
-# ------------------------------------------------------------------------------------------------ NDF on a slab
-class NdfSlab:
-    """Ghosted ping-pong state for NDF (docs/kernels/ndf.md): one ghost plane of U per interior boundary.  Arrays address
-    ``[lo + nz_local + hi][dy][dx]`` with ``lo`` / ``hi`` = 1 where a z-neighbour exists (else 0).  The first iteration reads
-    its iterate from ``inp`` (U^0 = the input, whose ghost planes the initial exchange fills); iteration ``it`` > 0 reads
-    ``U[it & 1]``, and every iteration writes ``U[(it + 1) & 1]``."""
+# ------------------------------------------------------------------------------------ explicit time marching on a slab
+class MarchSlab:
+    """Ghosted ping-pong state of an explicit time march (NDF, Diff4th, LLT_ROF) with a ghost depth of ``g`` planes of U per
+    interior boundary.  Arrays address ``[lo + nz_local + hi][dy][dx]`` with ``lo`` / ``hi`` = g where a z-neighbour exists
+    (else 0).  The first iteration reads its iterate from ``inp`` (U^0 = the input, whose ghost planes the initial exchange
+    fills); iteration ``it`` > 0 reads ``U[it & 1]``, and every iteration writes ``U[(it + 1) & 1]``.  ``ints`` are the
+    integer parameters ``step_fn`` takes after the three float ones."""
 
-    def __init__(self, data: torch.Tensor, has_lo: bool, has_hi: bool, penalty, step_fn: Callable,
-                 alloc: Optional[Callable] = None):
+    def __init__(self, data: torch.Tensor, has_lo: bool, has_hi: bool, g: int, step_fn: Callable,
+                 alloc: Optional[Callable] = None, ints=()):
         nzl, dy, dx = data.shape
         self.nzl, self.dy, self.dx = nzl, dy, dx
-        self.lo = 1 if has_lo else 0
-        self.hi = 1 if has_hi else 0
-        self.penalty = penalty
+        self.lo = g if has_lo else 0
+        self.hi = g if has_hi else 0
         planes = nzl + self.lo + self.hi
         specs = [((planes, dy, dx), torch.float32)] * 3
         self.lease = None
@@ -740,7 +740,7 @@ class NdfSlab:
         self.inp = arrs[0]
         self.inp[self.lo:self.lo + nzl] = data
         self.U = arrs[1:3]
-        self.step_fn = step_fn
+        self.step_fn, self.ints = step_fn, tuple(ints)
 
     def local(self, t):
         return t[self.lo:self.lo + self.nzl]
@@ -749,43 +749,95 @@ class NdfSlab:
         """the array iteration ``it`` reads = the array that holds iterate ``it``"""
         return self.inp if it == 0 else self.U[it & 1]
 
-    def step(self, it, lam, sigma, tau, zr=None):
-        """iteration ``it``, all local planes or only the local range ``zr``"""
+    def step(self, it, p0, p1, tau, zr=None):
+        """iteration ``it`` with the operator's two parameters and the step ``tau``, all local planes or only the local
+        range ``zr``"""
+        args = (self.inp, self.source(it), self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi, p0, p1, tau,
+                *self.ints)
         if zr is None:
-            self.step_fn(self.inp, self.source(it), self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi,
-                         lam, sigma, tau, self.penalty)
+            self.step_fn(*args)
         elif zr[1] > zr[0]:
-            self.step_fn(self.inp, self.source(it), self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi,
-                         lam, sigma, tau, self.penalty, zr)
+            self.step_fn(*args, zr)
 
     def boundary_ranges(self):
-        """planes the neighbours wait for (the first below an interior boundary, the last above one) and the rest"""
-        b0 = 1 if self.lo else 0
-        b1 = max(self.nzl - (1 if self.hi else 0), b0)
+        """planes the neighbours wait for (the first g below an interior boundary, the last g above one) and the rest"""
+        b0 = min(self.lo, self.nzl)
+        b1 = max(self.nzl - self.hi, b0)
         return ([(0, b0)] if self.lo else []) + ([(b1, self.nzl)] if self.hi and b1 < self.nzl else []), (b0, b1)
 
-    # ---- ghost planes of the array holding iterate ``it`` (``source(it)``).  Up = to rank+1, down = to rank-1.
+    # ---- ghost planes of the array holding iterate ``it`` (``source(it)``).  Up = to rank+1, down = to rank-1.  Each is one
+    # contiguous block of g planes (every slab owns at least g: comm.validate_slabs).
     def send_down(self, it):
-        return [self.source(it)[self.lo]] if self.lo else []
+        return [self.source(it)[self.lo:2 * self.lo]] if self.lo else []
 
     def send_up(self, it):
-        return [self.source(it)[self.lo + self.nzl - 1]] if self.hi else []
+        return [self.source(it)[self.lo + self.nzl - self.hi:self.lo + self.nzl]] if self.hi else []
 
     def recv_down(self, it):
-        return [self.source(it)[0]] if self.lo else []
+        return [self.source(it)[0:self.lo]] if self.lo else []
 
     def recv_up(self, it):
-        return [self.source(it)[self.lo + self.nzl]] if self.hi else []
+        return [self.source(it)[self.lo + self.nzl:self.lo + self.nzl + self.hi]] if self.hi else []
 
 
-def _hip_ndf_step(inp, u_in, u_out, dx, dy, nzl, lo, hi, lam, sigma, tau, penalty, zr=None):
-    from . import _lib as L
-    from . import ops
-    z0, z1 = zr if zr is not None else (0, nzl)
-    with torch.cuda.device(inp.device):
-        L.check(L.lib().tomo_ndf_iter_slab_range(inp.device.index, ops.ptr(inp), ops.ptr(u_in), ops.ptr(u_out), dx, dy,
-                                                 nzl, int(lo), int(hi), int(z0), int(z1), float(lam), float(sigma),
-                                                 float(tau), int(penalty), ops.stream_ptr(inp)))
+def _hip_march_step(entry: str, n_ints: int = 0):
+    """The ``step_fn`` that launches the C entry point ``entry`` (a tomo_*_iter_slab_range): after the three float
+    parameters it takes ``n_ints`` integer ones, then optionally the local plane range ``zr``."""
+    def step(inp, u_in, u_out, dx, dy, nzl, lo, hi, p0, p1, tau, *rest):
+        from . import _lib as L
+        from . import ops
+        z0, z1 = rest[n_ints] if len(rest) > n_ints and rest[n_ints] is not None else (0, nzl)
+        with torch.cuda.device(inp.device):
+            L.check(getattr(L.lib(), entry)(inp.device.index, ops.ptr(inp), ops.ptr(u_in), ops.ptr(u_out), dx, dy, nzl,
+                                            int(lo), int(hi), int(z0), int(z1), float(p0), float(p1), float(tau),
+                                            *map(int, rest[:n_ints]), ops.stream_ptr(inp)))
+    return step
+
+
+def _march_slab(st: MarchSlab, comm, data, iterations, params, out, overlap, tolerance, info):
+    """The exchange / overlap / tolerance loop of ndf_slab, diff4th_slab and llt_rof_slab on the state ``st``; ``params`` are
+    the operator's two parameters and the step ``tau``."""
+    params = tuple(np.float32(v) for v in params)
+    if iterations > 0:
+        comm.exchange(st.send_down(0), st.recv_down(0), st.send_up(0), st.recv_up(0))
+    edge_ranges, interior = st.boundary_ranges()
+    overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
+    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
+    for it in range(iterations):
+        if rule.stop(it, st.local(st.source(it))):
+            iterations = it
+            break
+        more = it + 1 < iterations
+        if overlap and more:  # boundary planes, exchange in flight, interior (see pd_tv_slab)
+            for zr in edge_ranges:
+                st.step(it, *params, zr)
+            reqs = comm.exchange_start(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
+            st.step(it, *params, interior)
+            comm.exchange_wait(reqs)
+            continue
+        st.step(it, *params)
+        if more:
+            comm.exchange(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
+    _check_lease(st)
+    res = st.local(st.source(iterations))
+    if out is not None:
+        out.copy_(res)
+        return out
+    return res.clone()
+
+
+# ------------------------------------------------------------------------------------------------ NDF on a slab
+class NdfSlab(MarchSlab):
+    """MarchSlab for NDF (docs/kernels/ndf.md): one ghost plane of U per interior boundary; ``step_fn`` receives the penalty
+    as its TOMO_NDF_* number after the three scalars."""
+
+    def __init__(self, data: torch.Tensor, has_lo: bool, has_hi: bool, penalty, step_fn: Callable,
+                 alloc: Optional[Callable] = None):
+        super().__init__(data, has_lo, has_hi, 1, step_fn, alloc, (penalty,))
+        self.penalty = penalty
+
+
+_hip_ndf_step = _hip_march_step("tomo_ndf_iter_slab_range", 1)
 
 
 def ndf_slab(data: torch.Tensor, comm, regularisation_parameter, edge_parameter, iterations, time_marching_parameter,
@@ -799,108 +851,22 @@ def ndf_slab(data: torch.Tensor, comm, regularisation_parameter, edge_parameter,
     comm.validate_slabs(data.shape[0], 1)
     st = NdfSlab(data, comm.has_lo, comm.has_hi, penalty, step_fn or _hip_ndf_step,
                  alloc=_hip_alloc(PLACED_SLOT_NDF) if (step_fn is None and data.is_cuda) else None)
-    lam, sigma, tau = np.float32(regularisation_parameter), np.float32(edge_parameter), np.float32(time_marching_parameter)
-    if iterations > 0:
-        comm.exchange(st.send_down(0), st.recv_down(0), st.send_up(0), st.recv_up(0))
-    edge_ranges, interior = st.boundary_ranges()
-    overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
-    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
-    for it in range(iterations):
-        if rule.stop(it, st.local(st.source(it))):
-            iterations = it
-            break
-        more = it + 1 < iterations
-        if overlap and more:  # boundary planes, exchange in flight, interior (see pd_tv_slab)
-            for zr in edge_ranges:
-                st.step(it, lam, sigma, tau, zr)
-            reqs = comm.exchange_start(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
-            st.step(it, lam, sigma, tau, interior)
-            comm.exchange_wait(reqs)
-            continue
-        st.step(it, lam, sigma, tau)
-        if more:
-            comm.exchange(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
-    _check_lease(st)
-    res = st.local(st.source(iterations))
-    if out is not None:
-        out.copy_(res)
-        return out
-    return res.clone()
+    return _march_slab(st, comm, data, iterations, (regularisation_parameter, edge_parameter, time_marching_parameter), out,
+                       overlap, tolerance, info)
 
 
 # ------------------------------------------------------------------------------------------------ Diff4th on a slab
 DIFF4TH_GHOST = 2   # the stencil's radius: W at distance 1 needs U at distance 2
 
 
-class Diff4thSlab:
-    """Ghosted ping-pong state for Diff4th (docs/kernels/diff4th.md): NdfSlab with a ghost depth of two.  Arrays address
-    ``[lo + nz_local + hi][dy][dx]`` with ``lo`` / ``hi`` = 2 where a z-neighbour exists (else 0).  The first iteration reads
-    its iterate from ``inp`` (U^0 = the input, whose ghost planes the initial exchange fills); iteration ``it`` > 0 reads
-    ``U[it & 1]``, and every iteration writes ``U[(it + 1) & 1]``."""
+class Diff4thSlab(MarchSlab):
+    """MarchSlab for Diff4th (docs/kernels/diff4th.md): two ghost planes of U per interior boundary."""
 
     def __init__(self, data: torch.Tensor, has_lo: bool, has_hi: bool, step_fn: Callable, alloc: Optional[Callable] = None):
-        nzl, dy, dx = data.shape
-        self.nzl, self.dy, self.dx = nzl, dy, dx
-        self.lo = DIFF4TH_GHOST if has_lo else 0
-        self.hi = DIFF4TH_GHOST if has_hi else 0
-        planes = nzl + self.lo + self.hi
-        specs = [((planes, dy, dx), torch.float32)] * 3
-        self.lease = None
-        if alloc is not None:
-            arrs, self.lease = alloc(specs, data.device)
-        else:
-            arrs = [torch.empty(sh, dtype=dt, device=data.device) for sh, dt in specs]
-        self.inp = arrs[0]
-        self.inp[self.lo:self.lo + nzl] = data
-        self.U = arrs[1:3]
-        self.step_fn = step_fn
-
-    def local(self, t):
-        return t[self.lo:self.lo + self.nzl]
-
-    def source(self, it):
-        """the array iteration ``it`` reads = the array that holds iterate ``it``"""
-        return self.inp if it == 0 else self.U[it & 1]
-
-    def step(self, it, lam, sigma, tau, zr=None):
-        """iteration ``it``, all local planes or only the local range ``zr``"""
-        if zr is None:
-            self.step_fn(self.inp, self.source(it), self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi,
-                         lam, sigma, tau)
-        elif zr[1] > zr[0]:
-            self.step_fn(self.inp, self.source(it), self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi,
-                         lam, sigma, tau, zr)
-
-    def boundary_ranges(self):
-        """planes the neighbours wait for (the first two below an interior boundary, the last two above one) and the rest"""
-        g = DIFF4TH_GHOST
-        b0 = min(g, self.nzl) if self.lo else 0
-        b1 = max(self.nzl - (g if self.hi else 0), b0)
-        return ([(0, b0)] if self.lo else []) + ([(b1, self.nzl)] if self.hi and b1 < self.nzl else []), (b0, b1)
-
-    # ---- ghost planes of the array holding iterate ``it`` (``source(it)``).  Up = to rank+1, down = to rank-1.  Each is one
-    # contiguous block of two planes (every slab owns at least two: comm.validate_slabs).
-    def send_down(self, it):
-        return [self.source(it)[self.lo:self.lo + DIFF4TH_GHOST]] if self.lo else []
-
-    def send_up(self, it):
-        return [self.source(it)[self.lo + self.nzl - DIFF4TH_GHOST:self.lo + self.nzl]] if self.hi else []
-
-    def recv_down(self, it):
-        return [self.source(it)[0:self.lo]] if self.lo else []
-
-    def recv_up(self, it):
-        return [self.source(it)[self.lo + self.nzl:self.lo + self.nzl + self.hi]] if self.hi else []
+        super().__init__(data, has_lo, has_hi, DIFF4TH_GHOST, step_fn, alloc)
 
 
-def _hip_diff4th_step(inp, u_in, u_out, dx, dy, nzl, lo, hi, lam, sigma, tau, zr=None):
-    from . import _lib as L
-    from . import ops
-    z0, z1 = zr if zr is not None else (0, nzl)
-    with torch.cuda.device(inp.device):
-        L.check(L.lib().tomo_diff4th_iter_slab_range(inp.device.index, ops.ptr(inp), ops.ptr(u_in), ops.ptr(u_out), dx, dy,
-                                                     nzl, int(lo), int(hi), int(z0), int(z1), float(lam), float(sigma),
-                                                     float(tau), ops.stream_ptr(inp)))
+_hip_diff4th_step = _hip_march_step("tomo_diff4th_iter_slab_range")
 
 
 def diff4th_slab(data: torch.Tensor, comm, regularisation_parameter, edge_parameter, iterations, time_marching_parameter,
@@ -912,108 +878,23 @@ def diff4th_slab(data: torch.Tensor, comm, regularisation_parameter, edge_parame
     comm.validate_slabs(data.shape[0], DIFF4TH_GHOST)
     st = Diff4thSlab(data, comm.has_lo, comm.has_hi, step_fn or _hip_diff4th_step,
                      alloc=_hip_alloc(PLACED_SLOT_DIFF4TH) if (step_fn is None and data.is_cuda) else None)
-    lam, sigma, tau = np.float32(regularisation_parameter), np.float32(edge_parameter), np.float32(time_marching_parameter)
-    if iterations > 0:
-        comm.exchange(st.send_down(0), st.recv_down(0), st.send_up(0), st.recv_up(0))
-    edge_ranges, interior = st.boundary_ranges()
-    overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
-    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
-    for it in range(iterations):
-        if rule.stop(it, st.local(st.source(it))):
-            iterations = it
-            break
-        more = it + 1 < iterations
-        if overlap and more:  # boundary planes, exchange in flight, interior (see pd_tv_slab)
-            for zr in edge_ranges:
-                st.step(it, lam, sigma, tau, zr)
-            reqs = comm.exchange_start(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
-            st.step(it, lam, sigma, tau, interior)
-            comm.exchange_wait(reqs)
-            continue
-        st.step(it, lam, sigma, tau)
-        if more:
-            comm.exchange(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
-    _check_lease(st)
-    res = st.local(st.source(iterations))
-    if out is not None:
-        out.copy_(res)
-        return out
-    return res.clone()
+    return _march_slab(st, comm, data, iterations, (regularisation_parameter, edge_parameter, time_marching_parameter), out,
+                       overlap, tolerance, info)
 
 
 # ------------------------------------------------------------------------------------------------ LLT_ROF on a slab
 LLT_ROF_GHOST = 2   # the stencil's radius: E_d at distance 1 needs U at distance 2
 
 
-class LltRofSlab:
-    """Ghosted ping-pong state for LLT_ROF (docs/kernels/llt_rof.md): Diff4thSlab with the two weights.  Arrays address
-    ``[lo + nz_local + hi][dy][dx]`` with ``lo`` / ``hi`` = 2 where a z-neighbour exists (else 0).  The first iteration reads
-    its iterate from ``inp`` (U^0 = the input, whose ghost planes the initial exchange fills); iteration ``it`` > 0 reads
-    ``U[it & 1]``, and every iteration writes ``U[(it + 1) & 1]``."""
+class LltRofSlab(MarchSlab):
+    """MarchSlab for LLT_ROF (docs/kernels/llt_rof.md): two ghost planes of U per interior boundary; the two parameters are
+    the ROF and the LLT weight."""
 
     def __init__(self, data: torch.Tensor, has_lo: bool, has_hi: bool, step_fn: Callable, alloc: Optional[Callable] = None):
-        nzl, dy, dx = data.shape
-        self.nzl, self.dy, self.dx = nzl, dy, dx
-        self.lo = LLT_ROF_GHOST if has_lo else 0
-        self.hi = LLT_ROF_GHOST if has_hi else 0
-        planes = nzl + self.lo + self.hi
-        specs = [((planes, dy, dx), torch.float32)] * 3
-        self.lease = None
-        if alloc is not None:
-            arrs, self.lease = alloc(specs, data.device)
-        else:
-            arrs = [torch.empty(sh, dtype=dt, device=data.device) for sh, dt in specs]
-        self.inp = arrs[0]
-        self.inp[self.lo:self.lo + nzl] = data
-        self.U = arrs[1:3]
-        self.step_fn = step_fn
-
-    def local(self, t):
-        return t[self.lo:self.lo + self.nzl]
-
-    def source(self, it):
-        """the array iteration ``it`` reads = the array that holds iterate ``it``"""
-        return self.inp if it == 0 else self.U[it & 1]
-
-    def step(self, it, lam_rof, lam_llt, tau, zr=None):
-        """iteration ``it``, all local planes or only the local range ``zr``"""
-        if zr is None:
-            self.step_fn(self.inp, self.source(it), self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi,
-                         lam_rof, lam_llt, tau)
-        elif zr[1] > zr[0]:
-            self.step_fn(self.inp, self.source(it), self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi,
-                         lam_rof, lam_llt, tau, zr)
-
-    def boundary_ranges(self):
-        """planes the neighbours wait for (the first two below an interior boundary, the last two above one) and the rest"""
-        g = LLT_ROF_GHOST
-        b0 = min(g, self.nzl) if self.lo else 0
-        b1 = max(self.nzl - (g if self.hi else 0), b0)
-        return ([(0, b0)] if self.lo else []) + ([(b1, self.nzl)] if self.hi and b1 < self.nzl else []), (b0, b1)
-
-    # ---- ghost planes of the array holding iterate ``it`` (``source(it)``).  Up = to rank+1, down = to rank-1.  Each is one
-    # contiguous block of two planes (every slab owns at least two: comm.validate_slabs).
-    def send_down(self, it):
-        return [self.source(it)[self.lo:self.lo + LLT_ROF_GHOST]] if self.lo else []
-
-    def send_up(self, it):
-        return [self.source(it)[self.lo + self.nzl - LLT_ROF_GHOST:self.lo + self.nzl]] if self.hi else []
-
-    def recv_down(self, it):
-        return [self.source(it)[0:self.lo]] if self.lo else []
-
-    def recv_up(self, it):
-        return [self.source(it)[self.lo + self.nzl:self.lo + self.nzl + self.hi]] if self.hi else []
+        super().__init__(data, has_lo, has_hi, LLT_ROF_GHOST, step_fn, alloc)
 
 
-def _hip_llt_rof_step(inp, u_in, u_out, dx, dy, nzl, lo, hi, lam_rof, lam_llt, tau, zr=None):
-    from . import _lib as L
-    from . import ops
-    z0, z1 = zr if zr is not None else (0, nzl)
-    with torch.cuda.device(inp.device):
-        L.check(L.lib().tomo_llt_rof_iter_slab_range(inp.device.index, ops.ptr(inp), ops.ptr(u_in), ops.ptr(u_out), dx, dy,
-                                                     nzl, int(lo), int(hi), int(z0), int(z1), float(lam_rof), float(lam_llt),
-                                                     float(tau), ops.stream_ptr(inp)))
+_hip_llt_rof_step = _hip_march_step("tomo_llt_rof_iter_slab_range")
 
 
 def llt_rof_slab(data: torch.Tensor, comm, regularisation_parameterROF, regularisation_parameterLLT, iterations, time_marching_parameter,
@@ -1024,31 +905,6 @@ def llt_rof_slab(data: torch.Tensor, comm, regularisation_parameterROF, regulari
     before the first.  Every slab must own at least two planes: a neighbour's two ghost planes come from one rank."""
     comm.validate_slabs(data.shape[0], LLT_ROF_GHOST)
     st = LltRofSlab(data, comm.has_lo, comm.has_hi, step_fn or _hip_llt_rof_step,
-                     alloc=_hip_alloc(PLACED_SLOT_LLT_ROF) if (step_fn is None and data.is_cuda) else None)
-    lam_rof, lam_llt, tau = np.float32(regularisation_parameterROF), np.float32(regularisation_parameterLLT), np.float32(time_marching_parameter)
-    if iterations > 0:
-        comm.exchange(st.send_down(0), st.recv_down(0), st.send_up(0), st.recv_up(0))
-    edge_ranges, interior = st.boundary_ranges()
-    overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
-    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
-    for it in range(iterations):
-        if rule.stop(it, st.local(st.source(it))):
-            iterations = it
-            break
-        more = it + 1 < iterations
-        if overlap and more:  # boundary planes, exchange in flight, interior (see pd_tv_slab)
-            for zr in edge_ranges:
-                st.step(it, lam_rof, lam_llt, tau, zr)
-            reqs = comm.exchange_start(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
-            st.step(it, lam_rof, lam_llt, tau, interior)
-            comm.exchange_wait(reqs)
-            continue
-        st.step(it, lam_rof, lam_llt, tau)
-        if more:
-            comm.exchange(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
-    _check_lease(st)
-    res = st.local(st.source(iterations))
-    if out is not None:
-        out.copy_(res)
-        return out
-    return res.clone()
+                    alloc=_hip_alloc(PLACED_SLOT_LLT_ROF) if (step_fn is None and data.is_cuda) else None)
+    return _march_slab(st, comm, data, iterations, (regularisation_parameterROF, regularisation_parameterLLT, time_marching_parameter),
+                       out, overlap, tolerance, info)

@@ -1,17 +1,17 @@
 """TEST INFRASTRUCTURE: numpy restatement of the nonlinear-diffusion (NDF) regulariser of docs/kernels/ndf.md (the
-specification; there is no reference implementation to compare with -- formula-level parity, unpinned).  Shared by
-tests/test_ndf_oracle.py, tests/test_ndf_slab_gloo.py (CPU) and tests/test_gpu_ndf.py (MI355X).
+specification; there is no reference implementation to compare with -- formula-level parity, unpinned).  This file holds
+the formula; tests/_march_oracle.py runs it (ORACLE below).  Shared by tests/test_ndf_oracle.py,
+tests/test_ndf_slab_gloo.py (CPU) and tests/test_gpu_ndf.py (MI355X).
 
 Arrays are indexed [z][y][x]; component 1 <-> x (the fastest axis), 2 <-> y, 3 <-> z; 2D drops component 3.  With
 dtype = float32 every operation below is one float32 rounding in the order the parentheses give (numpy never contracts to
 FMA, and its / is the correctly rounded division), which is what the kernel reproduces bit for bit; dtype = float64 is the
 same algorithm in double."""
-import functools
-
 import numpy as np
 
-from _tgv_oracle import phantom, rel_d, rel_l2  # noqa: F401  (the phantom and the two norms are shared with TGV)
+import _march_oracle
 
+GHOST = 1   # ghost planes of U per interior boundary of a z-slab
 PENALTIES = ("Huber", "PM", "Tukey")
 PARAMS = {
     "A": dict(penalty="Huber", lam=1.0, sigma=2.0, tau=0.05),
@@ -83,118 +83,14 @@ def step(U, f, lam, sigma, tau, penalty, stats=None):
     return U + tau * (lam * S - (U - f))
 
 
-def ndf_iterates(f, penalty, lam, sigma, tau, iterations=1, dtype=np.float32, stats=None):
-    """yields U after every iteration (a fresh array each time); `stats`: see step, for the LAST iteration run"""
-    t = dtype
-    f = np.asarray(f).astype(t)
-    assert f.ndim in (2, 3)
-    lam, sigma, tau = t(lam), t(sigma), t(tau)
-    U = f
-    for n in range(iterations):
-        U = step(U, f, lam, sigma, tau, penalty, stats if n == iterations - 1 else None)
-        yield U
-
-
-def ndf(f, penalty, lam, sigma, tau, iterations=1, dtype=np.float32, stats=None):
-    """U after `iterations` iterations (a copy of the input, as `dtype`, for 0)"""
-    out = np.asarray(f).astype(dtype)
-    for out in ndf_iterates(f, penalty, lam, sigma, tau, iterations, dtype, stats):
-        pass
-    return out
-
-
-def ndf_many(f, params, counts, dtype=np.float32):
-    """{n: U after n iterations} for every n of `counts`, from ONE run"""
-    counts = sorted(set(counts))
-    out = {}
-    for n, U in enumerate(ndf_iterates(f, iterations=counts[-1], dtype=dtype, **params), 1):
-        if n in counts:
-            out[n] = U
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def cached(shape, pname, counts, dtype_name="float32"):
-    """ndf_many of the phantom of `shape` under parameter set "A".."D": computed once per session, never modified"""
-    res = ndf_many(phantom(shape), PARAMS[pname], counts, np.dtype(dtype_name).type)
-    for v in res.values():
-        v.setflags(write=False)
-    return res
-
-
-# ------------------------------------------------------------------------------------------------ z-slabs
-def _as_numpy(t):
-    return t.numpy() if hasattr(t, "numpy") else np.asarray(t)
-
-
-def ndf_step_slab(inp, u_in, u_out, dx, dy, nzl, lo, hi, lam, sigma, tau, penalty, zr=None):
-    """One iteration on ghosted slab arrays [lo + nzl + hi][dy][dx] (host torch tensors or numpy arrays), the step_fn of
-    tomobar_amd.slab.ndf_slab: a ghost plane exists exactly where a z-neighbour exists, so the plain whole-array step on the
-    ghosted array gives the right z differences on every LOCAL plane; only the local planes [z0, z1) of `u_out` are written.
-    `penalty` is a name or its TOMO_NDF_* number."""
-    z0, z1 = zr if zr is not None else (0, nzl)
+def _step_slab(inp, u_in, u_out, dx, dy, nzl, lo, hi, lam, sigma, tau, penalty, zr=None, ghost=GHOST):
+    """the step_fn of tomobar_amd.slab.ndf_slab (_march_oracle.slab_step): `penalty` is a name or its TOMO_NDF_* number"""
     name = penalty if isinstance(penalty, str) else PENALTIES[int(penalty)]
-    f, U, out = _as_numpy(inp), _as_numpy(u_in), _as_numpy(u_out)
-    assert U.shape == (lo + nzl + hi, dy, dx) and U.dtype == np.float32
-    a, b = max(lo + z0 - 1, 0), min(lo + z1 + 1, U.shape[0])    # the output planes and one plane either side
-    new = step(U[a:b], f[a:b], np.float32(lam), np.float32(sigma), np.float32(tau), name)
-    out[lo + z0:lo + z1] = new[lo + z0 - a:lo + z1 - a]
+    _march_oracle.slab_step(step, inp, u_in, u_out, dx, dy, nzl, lo, hi, (lam, sigma, tau), zr, ghost, penalty=name)
 
 
-def ndf_by_slabs(f, params, iterations, world):
-    """the whole volume run as `world` ghosted slabs exchanged by hand after every iteration, stitched"""
-    f = np.asarray(f, np.float32)
-    nz = f.shape[0]
-    base, extra = divmod(nz, world)
-    bounds, z = [], 0
-    for r in range(world):
-        bounds.append((z, z + base + (1 if r < extra else 0)))
-        z = bounds[-1][1]
-    U = f.copy()
-    for _ in range(iterations):
-        new = np.empty_like(U)
-        for r, (z0, z1) in enumerate(bounds):
-            lo, hi = int(r > 0), int(r < world - 1)
-            g_in = np.ascontiguousarray(U[z0 - lo:z1 + hi])
-            g_f = np.ascontiguousarray(f[z0 - lo:z1 + hi])
-            g_out = np.full_like(g_in, np.nan)
-            ndf_step_slab(g_f, g_in, g_out, f.shape[2], f.shape[1], z1 - z0, lo, hi, params["lam"], params["sigma"],
-                          params["tau"], params["penalty"])
-            new[z0:z1] = g_out[lo:lo + z1 - z0]
-        U = new
-    return U
-
-
-# ------------------------------------------------------------------------------------------------ the tolerance rule
-TOL_INTERVAL, TOL_MIN_SAVED = 6, 3
 TOL_CASE = dict(shape=(7, 13, 37), pname="A", iterations=66, j=4)
 TOL_CASE_SLAB = dict(shape=(9, 7, 11), pname="A", iterations=66, j=4)
-
-
-def rel_change_sums(x, ref, keep=None):
-    """CPU stand-in for tomo_rel_change at the slab driver's seam (tomobar_amd.slab._hip_rel_change): (sum (x - ref)^2,
-    sum x^2) in float64 from the float32 values; with `keep`, keep[...] = x afterwards"""
-    x64, r64 = _as_numpy(x).astype(np.float64).ravel(), _as_numpy(ref).astype(np.float64).ravel()
-    num, den = float(np.sum((x64 - r64) ** 2)), float(np.sum(x64 ** 2))
-    if keep is not None:
-        keep.copy_(x.view(keep.shape))
-    return num, den
-
-
-@functools.lru_cache(maxsize=None)
-def tolerance_plan(slab=False):
-    """(tol, n the oracle's sequence stops after, the d it stops on, the whole sequence) of TOL_CASE (TOL_CASE_SLAB with
-    `slab`): d_n compares iterate n with iterate n - 6 (iterate 0 = the input) after every 6th iteration that leaves at
-    least 3; tol is the geometric mean of the (j-1)-th and j-th values, as tests/_tgv_oracle.py chooses its threshold"""
-    c = TOL_CASE_SLAB if slab else TOL_CASE
-    points = [n for n in range(TOL_INTERVAL, c["iterations"] + 1, TOL_INTERVAL) if c["iterations"] - n >= TOL_MIN_SAVED]
-    its = cached(c["shape"], c["pname"], tuple(points))
-    prev, seq = phantom(c["shape"]), []
-    for n in points:
-        seq.append(rel_d(its[n], prev))
-        prev = its[n]
-    j = c["j"]
-    tol = float(np.sqrt(seq[j - 2] * seq[j - 1]))
-    assert all(abs(v - tol) >= 0.01 * tol for v in seq), ("a value of the sequence is too close to the threshold", tol, seq)
-    assert next(i for i, v in enumerate(seq, 1) if v < tol) == j, ("the target is not the first value below the threshold", seq)
-    return tol, points[j - 1], seq[j - 1], tuple(seq)
+# `stats`: step's figures of the LAST iteration run
+ORACLE = _march_oracle.Marcher("NDF", step, PARAMS, ("lam", "sigma", "tau"), GHOST, TOL_CASE, TOL_CASE_SLAB, stats_each=False,
+                               step_slab=_step_slab)

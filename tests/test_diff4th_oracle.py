@@ -1,13 +1,16 @@
-"""Diff4th without a GPU: properties of the numpy restatement (tests/_diff4th_oracle.py; the algorithm is the specification,
-docs/kernels/diff4th.md) and the host surface of the feature -- dictionary defaults, the refusals, the C-ABI's argument
-checks, scratch size and symbol set (the library loads and validates without a device)."""
-import ctypes as C
+"""Diff4th without a GPU, what is Diff4th's own: properties of the numpy restatement (tests/_diff4th_oracle.py; the algorithm
+is the specification, docs/kernels/diff4th.md) and the host surface of the feature -- dictionary defaults, the refusals, the
+C-ABI's symbol set.  What Diff4th shares with the other explicit time marches is the suite of tests/_march_oracle_suite.py,
+collected at the end of this file."""
 import types
 
 import numpy as np
 import pytest
 
-import _diff4th_oracle as D
+import _march_oracle_suite
+import _diff4th_oracle
+from _diff4th_oracle import ORACLE as D
+from _tgv_oracle import phantom, rel_l2
 
 SHAPE_3D, SHAPE_2D = (7, 13, 37), (13, 37)
 COUNTS = (1, 2, 25, 40)
@@ -24,7 +27,7 @@ def test_float32_against_float64(shape, pname):
     """the float32 arithmetic the kernel reproduces holds the project's parity bar against the same algorithm in double"""
     f32, f64 = D.cached(shape, pname, COUNTS), D.cached(shape, pname, COUNTS, "float64")
     for n in COUNTS:
-        r = D.rel_l2(f32[n], f64[n])
+        r = rel_l2(f32[n], f64[n])
         print(f"Diff4th {pname} {shape} after {n}: float32 vs float64 rel-L2 = {r:.2e}")
         assert f32[n].dtype == np.float32 and f64[n].dtype == np.float64
         assert r <= 1e-5, (shape, pname, n, r)
@@ -36,93 +39,34 @@ def test_the_edge_weight_is_active_on_part_of_the_voxels(shape, pname):
     """a condition on the INPUTS of the GPU tests: at the first and the last of 40 iterations between 10 % and 90 % of the
     voxels have G / s2 > 1 (cw below one half), so both regimes of the weight are exercised"""
     stats = {}
-    D.diff4th(D.phantom(shape), iterations=40, stats=stats, **D.PARAMS[pname])
-    print(f"Diff4th {pname} {shape}: G/s2 > 1 on {stats[1]:.3f} of the voxels in iteration 1, {stats[40]:.3f} in iteration 40")
+    D.run(phantom(shape), iterations=40, stats=stats, **D.PARAMS[pname])
+    print(f"Diff4th {pname} {shape}: G/s2 > 1 on {stats['active', 1]:.3f} of the voxels in iteration 1, {stats['active', 40]:.3f} in iteration 40")
     for n in (1, 40):
-        assert 0.10 <= stats[n] <= 0.90, (pname, shape, n, stats[n])
+        assert 0.10 <= stats["active", n] <= 0.90, (pname, shape, n, stats["active", n])
 
 
 def test_parameter_sets_meet_the_stability_bound_and_one_has_lambda_other_than_one():
     assert 3 <= len(D.PARAMS) <= 4
     for pname, p in D.PARAMS.items():
-        assert D.stable(p["lam"], p["tau"], 3) and D.stable(p["lam"], p["tau"], 2), pname
+        assert _diff4th_oracle.stable(p["lam"], p["tau"], 3) and _diff4th_oracle.stable(p["lam"], p["tau"], 2), pname
     assert any(p["lam"] != 1.0 for p in D.PARAMS.values())
 
 
-def test_z_replicated_volume_equals_the_2d_run():
-    """the z terms come last and are exact zeros on a volume constant along z: plane for plane the bits of the 2D run"""
-    plane = D.phantom(SHAPE_2D)
-    vol = np.ascontiguousarray(np.broadcast_to(plane, (5,) + SHAPE_2D))
-    for pname, params in D.PARAMS.items():
-        want = D.diff4th(plane, iterations=25, **params)
-        got = D.diff4th(vol, iterations=25, **params)
-        for z in range(vol.shape[0]):
-            assert np.array_equal(_bits(got[z]), _bits(want)), (pname, z)
-
-
-@pytest.mark.parametrize("shape", [(5, 6, 7), (6, 7)])
-def test_constant_input_is_a_fixed_point(shape):
-    f = np.full(shape, np.float32(37.25), np.float32)
-    for pname, params in D.PARAMS.items():
-        out = D.diff4th(f, iterations=25, **params)
-        assert np.array_equal(_bits(out), _bits(f)), pname
-
-
 def test_the_operator_changes_a_noisy_input():
-    f = D.phantom(SHAPE_3D)
+    f = phantom(SHAPE_3D)
     for pname in D.PARAMS:
         for n in COUNTS:
             out = D.cached(SHAPE_3D, pname, COUNTS)[n]
             assert np.all(np.isfinite(out)) and not np.array_equal(out, f), (pname, n)
-        assert D.rel_l2(D.cached(SHAPE_3D, pname, COUNTS)[40], f) > D.rel_l2(D.cached(SHAPE_3D, pname, COUNTS)[1], f) > 0.0
-
-
-def test_zero_iterations_and_a_dimension_of_one():
-    f = D.phantom((1, 5, 3))
-    out = D.diff4th(f, iterations=0, **D.PARAMS["A"])
-    assert np.array_equal(_bits(out), _bits(f))
-    for shape in [(1, 5, 3), (5, 1, 3), (5, 3, 1), (1, 37), (37, 1), (2, 2, 2)]:
-        assert np.all(np.isfinite(D.diff4th(D.phantom(shape), iterations=7, **D.PARAMS["B"]))), shape
-    # an axis of extent 1 contributes exact zeros: a [1][y][x] volume is the 2D run
-    plane = D.phantom(SHAPE_2D)
-    for pname, params in D.PARAMS.items():
-        assert np.array_equal(_bits(D.diff4th(plane[None], iterations=7, **params)[0]), _bits(D.diff4th(plane, iterations=7, **params)))
-
-
-@pytest.mark.parametrize("world", [2, 3])
-def test_stitched_slabs_equal_the_whole_volume(world):
-    """diff4th_step_slab on slabs with two ghost planes either side, exchanged after every iteration"""
-    f = D.phantom(SHAPE_3D)
-    for pname, params in D.PARAMS.items():
-        want = D.cached(SHAPE_3D, pname, COUNTS)[2]
-        assert np.array_equal(_bits(D.diff4th_by_slabs(f, params, 2, world)), _bits(want)), (pname, world)
-    want = D.cached(SHAPE_3D, "B", COUNTS)[25]
-    assert np.array_equal(_bits(D.diff4th_by_slabs(f, D.PARAMS["B"], 25, world)), _bits(want))
+        assert rel_l2(D.cached(SHAPE_3D, pname, COUNTS)[40], f) > rel_l2(D.cached(SHAPE_3D, pname, COUNTS)[1], f) > 0.0
 
 
 def test_stitched_slabs_with_a_slab_of_exactly_two_planes():
-    f = D.phantom(SHAPE_3D)
+    f = phantom(SHAPE_3D)
     want = D.cached(SHAPE_3D, "A", COUNTS)[2]
     for bounds in ([(0, 2), (2, 7)], [(0, 5), (5, 7)], [(0, 3), (3, 5), (5, 7)], [(0, 2), (2, 4), (4, 7)]):
-        got = D.diff4th_by_slabs(f, D.PARAMS["A"], 2, len(bounds), bounds)
+        got = D.by_slabs(f, D.PARAMS["A"], 2, len(bounds), bounds)
         assert np.array_equal(_bits(got), _bits(want)), bounds
-
-
-def test_slab_step_writes_only_the_range_it_is_given():
-    f = D.phantom((9, 5, 9))
-    out = np.full_like(f, np.nan)
-    p = D.PARAMS["C"]
-    D.diff4th_step_slab(f, f, out, 9, 5, 5, 2, 2, p["lam"], p["sigma"], p["tau"], zr=(1, 3))
-    assert np.all(np.isnan(out[:3])) and np.all(np.isnan(out[5:]))
-    want = D.diff4th(f, iterations=1, **p)
-    assert np.array_equal(_bits(out[3:5]), _bits(want[3:5]))
-
-
-def test_the_tolerance_cases_satisfy_their_rule():
-    for slab in (False, True):
-        tol, stop, d_stop, seq = D.tolerance_plan(slab)
-        print(f"Diff4th tolerance case (slab={slab}): sequence {['%.3e' % v for v in seq]}, tol {tol:.4e}, stops after {stop}")
-        assert stop == 24 and d_stop < tol < seq[2]
 
 
 # ------------------------------------------------------------------------------------------------ host surface
@@ -184,50 +128,6 @@ def test_refusals_half_precision_and_unknown_method():
     assert [p.default for p in list(sig.parameters.values())[1:]] == [1e-05, 0.01, 1000, 0.001, 0, None, 0.0]
 
 
-def test_slab_state_bookkeeping():
-    """Diff4thSlab on host tensors: two ghost planes where a neighbour exists, the ranges the neighbours wait for, the slot"""
-    import torch
-    from tomobar_amd import slab as S
-    data = torch.arange(7 * 2 * 3, dtype=torch.float32).reshape(7, 2, 3)
-    st = S.Diff4thSlab(data, True, True, D.diff4th_step_slab)
-    assert (st.lo, st.hi) == (2, 2) and st.inp.shape[0] == 11 and torch.equal(st.local(st.inp), data)
-    assert st.boundary_ranges() == ([(0, 2), (5, 7)], (2, 5))
-    assert st.source(0) is st.inp and st.source(1) is st.U[1] and st.source(2) is st.U[0]
-    (su,), (ru,), (sd,), (rd,) = st.send_up(0), st.recv_up(0), st.send_down(3), st.recv_down(3)
-    assert su.shape[0] == ru.shape[0] == sd.shape[0] == rd.shape[0] == 2 and all(t.is_contiguous() for t in (su, ru, sd, rd))
-    assert su.data_ptr() == st.inp[7].data_ptr() and ru.data_ptr() == st.inp[9].data_ptr()
-    assert sd.data_ptr() == st.U[1][2].data_ptr() and rd.data_ptr() == st.U[1][0].data_ptr()
-    st = S.Diff4thSlab(data[:2], True, True, D.diff4th_step_slab)       # a slab of exactly two planes: all of it is boundary
-    assert st.boundary_ranges() == ([(0, 2)], (2, 2))
-    assert st.send_up(0)[0].data_ptr() == st.send_down(0)[0].data_ptr() == st.inp[2].data_ptr()
-    st = S.Diff4thSlab(data[:3], True, True, D.diff4th_step_slab)
-    assert st.boundary_ranges() == ([(0, 2), (2, 3)], (2, 2))
-    st = S.Diff4thSlab(data, False, True, D.diff4th_step_slab)
-    assert (st.lo, st.hi) == (0, 2) and st.boundary_ranges() == ([(5, 7)], (0, 5)) and st.send_down(0) == [] and st.recv_down(0) == []
-    assert len({S.PLACED_SLOT_PD, S.PLACED_SLOT_ROF, S.PLACED_SLOT_NDF, S.PLACED_SLOT_DIFF4TH}) == 4 and S.PLACED_SLOT_DIFF4TH == 3
-
-
-def test_one_rank_slab_driver_is_the_whole_volume_run():
-    import torch
-    from tomobar_amd import slab as S
-    f = D.phantom((6, 5, 9))
-    p = D.PARAMS["B"]
-    got = S.diff4th_slab(torch.from_numpy(f), S.SlabComm(0, 1), p["lam"], p["sigma"], 7, p["tau"], step_fn=D.diff4th_step_slab)
-    assert np.array_equal(_bits(got.numpy()), _bits(D.diff4th(f, iterations=7, **p)))
-    got = S.diff4th_slab(torch.from_numpy(f), S.SlabComm(0, 1), p["lam"], p["sigma"], 0, p["tau"], step_fn=D.diff4th_step_slab)
-    assert np.array_equal(_bits(got.numpy()), _bits(f))
-    out = torch.full((6, 5, 9), float("nan"))
-    info = {}
-    assert S.diff4th_slab(torch.from_numpy(f), S.SlabComm(0, 1), p["lam"], p["sigma"], 2, p["tau"], step_fn=D.diff4th_step_slab,
-                          out=out, info=info) is out
-    assert np.array_equal(_bits(out.numpy()), _bits(D.diff4th(f, iterations=2, **p))) and info["iterations_done"] == 2
-
-
-def _lib():
-    from tomobar_amd import _lib
-    return _lib.lib()
-
-
 def test_abi_symbols():
     from tomobar_amd import _lib
     lib = _lib.lib()
@@ -237,40 +137,5 @@ def test_abi_symbols():
         assert hasattr(dev, "tomo_diff4th")
 
 
-def test_scratch_bytes():
-    lib = _lib()
-    from tomobar_amd import ops
-    skew = ops.ARRAY_SKEW
-    for dx, dy, dz in [(37, 13, 7), (64, 64, 64), (1, 1, 1), (200, 150, 40)]:
-        arr3 = (dx * dy * dz * 4 + 255) // 256 * 256
-        arr2 = (dx * dy * 4 + 255) // 256 * 256
-        assert lib.tomo_diff4th_scratch_bytes(dx, dy, dz, 3) == arr3 + skew      # the one ping-pong partner of the output
-        assert lib.tomo_diff4th_scratch_bytes(dx, dy, dz, 2) == arr2 + skew      # dz is ignored in 2D
-
-
-def test_invalid_arguments_are_refused_before_the_device_is_touched():
-    from tomobar_amd import _lib
-    lib = _lib.lib()
-    a, b, c = C.c_void_p(0x1000), C.c_void_p(0x2000), C.c_void_p(0x3000)   # never dereferenced: every case fails validation
-
-    def call(inp=a, out=b, dx=4, dy=4, dz=4, nd=3, lam=1.0, sigma=2.0, tau=0.005, iters=3, tol=0.0):
-        return lib.tomo_diff4th(0, inp, out, dx, dy, dz, nd, lam, sigma, tau, iters, tol, None, None, None)
-
-    bad = [dict(out=a), dict(inp=None), dict(out=None), dict(nd=1), dict(nd=4), dict(dx=0), dict(dy=0), dict(dz=0), dict(dx=-3),
-           dict(lam=0.0), dict(lam=-1.0), dict(sigma=0.0), dict(sigma=-2.0), dict(tau=0.0), dict(tau=-0.1),
-           dict(lam=float("nan")), dict(iters=-1), dict(tol=-1e-3), dict(tol=float("inf")),
-           dict(tol=float("nan")), dict(nd=2, dy=0), dict(dx=1 << 15, dy=1 << 14)]
-    for kw in bad:
-        assert call(**kw) == _lib.E_INVALID, kw
-        with pytest.raises(ValueError):
-            _lib.check(call(**kw))
-
-    def slab(inp=a, u_in=b, u_out=c, dx=4, dy=4, nzl=4, lo=2, hi=2, z0=0, z1=4, lam=1.0, sigma=2.0, tau=0.005):
-        return lib.tomo_diff4th_iter_slab_range(0, inp, u_in, u_out, dx, dy, nzl, lo, hi, z0, z1, lam, sigma, tau, None)
-
-    bad = [dict(dx=0), dict(dy=0), dict(nzl=0), dict(lo=1), dict(hi=1), dict(lo=3), dict(lo=-1), dict(z0=-1), dict(z1=5),
-           dict(z0=3, z1=2), dict(lam=0.0), dict(sigma=0.0), dict(tau=0.0), dict(inp=None), dict(u_in=None), dict(u_out=None),
-           dict(u_out=b), dict(u_out=a), dict(dx=1 << 15, dy=1 << 14)]
-    for kw in bad:
-        assert slab(**kw) == _lib.E_INVALID, kw
-    assert slab(z0=2, z1=2) == _lib.OK     # an empty range is nothing to do, before any device work
+# ------------------------------------------------------------------------------------------------ shared with the other marches
+globals().update(_march_oracle_suite.suite("Diff4th"))

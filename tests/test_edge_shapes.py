@@ -11,9 +11,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import _diff4th_oracle as D  # noqa: E402
+from _diff4th_oracle import ORACLE as D  # noqa: E402
 import _edge_shapes as E  # noqa: E402
-import _ndf_oracle as N  # noqa: E402
+from _ndf_oracle import ORACLE as N  # noqa: E402
 import _tgv_oracle as T  # noqa: E402
 
 CSRC = os.path.join(ROOT, "tomobar_amd", "csrc")
@@ -144,8 +144,8 @@ def test_terraces_run_finite_through_the_three_oracles(shape):
     share = E.zero_share(f)
     print(f"terraces {shape}: {share:.3f} of the forward differences are exactly zero")
     assert 0.85 < share < 0.93
-    runs = [(f"NDF {k}", lambda n, p=p: N.ndf(f, iterations=n, **p)) for k, p in sorted(N.PARAMS.items())]
-    runs += [(f"Diff4th {k}", lambda n, p=p: D.diff4th(f, iterations=n, **p)) for k, p in sorted(D.PARAMS.items())]
+    runs = [(f"NDF {k}", lambda n, p=p: N.run(f, iterations=n, **p)) for k, p in sorted(N.PARAMS.items())]
+    runs += [(f"Diff4th {k}", lambda n, p=p: D.run(f, iterations=n, **p)) for k, p in sorted(D.PARAMS.items())]
     runs += [(f"TGV {k}", lambda n, p=p: T.tgv(f, iterations=n, **p)) for k, p in (("A", T.PARAMS_A), ("B", T.PARAMS_B))]
     for what, run in runs:
         for n in (1, 4):
@@ -172,7 +172,7 @@ def test_terraces_reach_the_zero_difference_paths_at_every_shape_used():
     for shape in _terrace_shapes(["ndf"]) + TERRACE_SHAPES:
         for pname, p in sorted(N.PARAMS.items()):
             stats = {}
-            N.ndf(E.terraces(shape), iterations=1, stats=stats, **p)
+            N.run(E.terraces(shape), iterations=1, stats=stats, **p)
             assert stats["zero"] == E.zero_share(E.terraces(shape)) and 0.5 <= stats["zero"] < 1.0, (shape, pname, stats)
             assert stats["above"] > 0.0 if pname in "CD" else True, (shape, pname, stats)   # sigma = 4 (Tukey) / 0.5: steps of 3 and 6
     for shape in TERRACE_SHAPES:
@@ -186,13 +186,12 @@ def test_terraces_reach_the_masked_quotient_of_diff4th():
     used; the shares docs/kernels/diff4th.md quotes"""
     for shape in _terrace_shapes(["diff4th"]) + TERRACE_SHAPES + [E.SLABS["Diff4th"].shape]:
         stats = {}
-        for _ in D.diff4th_iterates(E.terraces(shape), iterations=2, stats=stats, **D.PARAMS["A"]):
-            pass
+        D.run(E.terraces(shape), iterations=2, stats=stats, **D.PARAMS["A"])
         assert 0.25 <= stats["g_zero", 1] < 1.0, (shape, stats)
         assert stats["g_zero", 2] < stats["g_zero", 1], (shape, stats)   # the flat interiors are eaten from the block edges
         if shape in TERRACE_SHAPES:
             print(f"Diff4th terraces {shape}: G == 0 on {stats['g_zero', 1]:.3f} of the voxels in iteration 1, "
                   f"{stats['g_zero', 2]:.3f} in iteration 2")
     stats = {}
-    D.diff4th(D.phantom((7, 13, 37)), iterations=1, stats=stats, **D.PARAMS["A"])
+    D.run(T.phantom((7, 13, 37)), iterations=1, stats=stats, **D.PARAMS["A"])
     assert stats["g_zero", 1] == 0.0     # the noise input never takes the masked branch

@@ -19,34 +19,17 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import _diff4th_oracle as D  # noqa: E402
 import _edge_shapes as E  # noqa: E402
-import _ndf_oracle as N  # noqa: E402
+import _march_gpu as G  # noqa: E402
 import _tgv_oracle as T  # noqa: E402
+from _march_gpu import same_bits  # noqa: E402
 
 COUNTS = (1, 2, 5)   # the direct input-to-output launch and both parities of the ping-pong
 
 
-def host(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want, what):
-    assert got.dtype == want.dtype == np.float32 and got.shape == want.shape, what
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        raise AssertionError((what, f"{len(bad)} of {got.size} values differ, first at {tuple(bad[0])}",
-                              float(np.abs(got.astype(np.float64) - want).max())))
-
-
 def _run(call, f_host):
     """call(input tensor, NaN-filled output tensor) on the GPU; the input's bits are checked afterwards"""
-    x = torch.from_numpy(f_host).cuda()
-    out = torch.full_like(x, float("nan"))
-    call(x, out)
-    assert np.array_equal(host(x).view(np.uint32), f_host.view(np.uint32)), "the input was written"
-    return host(out)
+    return G.run_op(call, f_host)[0]
 
 
 # ------------------------------------------------------------------------------------------------ NDF, Diff4th, TGV
@@ -55,14 +38,18 @@ def _field(kind, shape):
 
 
 TGV_PARAMS = {"A": T.PARAMS_A, "B": T.PARAMS_B}
+MARCHERS = {"ndf": "NDF", "diff4th": "Diff4th"}   # the launch names of tests/_edge_shapes.py -> the operators of _march_gpu.OPS
 
 
 @functools.lru_cache(maxsize=None)
 def _want(op, kind, shape, pname):
     """{n: the float32 numpy oracle after n iterations}, computed once per session and never modified"""
     f = _field(kind, shape)
-    res = (N.ndf_many(f, N.PARAMS[pname], COUNTS) if op == "ndf" else
-           D.diff4th_many(f, D.PARAMS[pname], COUNTS) if op == "diff4th" else T.tgv_many(f, TGV_PARAMS[pname], COUNTS))
+    if op in MARCHERS:
+        D = G.OPS[MARCHERS[op]].oracle
+        res = D.many(f, D.PARAMS[pname], COUNTS)
+    else:
+        res = T.tgv_many(f, TGV_PARAMS[pname], COUNTS)
     for v in res.values():
         v.setflags(write=False)
     return res
@@ -70,17 +57,16 @@ def _want(op, kind, shape, pname):
 
 def _gpu(op, pname, n):
     from tomobar_amd import ops
-    if op == "ndf":
-        p = N.PARAMS[pname]
-        return lambda x, out: ops.ndf(x, out, np.float32(p["lam"]), np.float32(p["sigma"]), np.float32(p["tau"]), p["penalty"], n)
-    if op == "diff4th":
+    if op in MARCHERS:
+        D = G.OPS[MARCHERS[op]].oracle
         p = D.PARAMS[pname]
-        return lambda x, out: ops.diff4th(x, out, np.float32(p["lam"]), np.float32(p["sigma"]), np.float32(p["tau"]), n)
+        return lambda x, out: G.ops_fn(D.name)(x, out, *G.f32(D, p), *(p[k] for k in D.extra), n)
     p = TGV_PARAMS[pname]
     return lambda x, out: ops.tgv(x, out, *T.scalars(p["lam"], p["alpha1"], p["alpha0"], p["L"]), n)
 
 
-MARCH_OPS = [(op, g, p) for op, params in (("ndf", N.PARAMS), ("diff4th", D.PARAMS), ("tgv", TGV_PARAMS))
+MARCH_OPS = [(op, g, p) for op, params in (("ndf", G.OPS["NDF"].oracle.PARAMS), ("diff4th", G.OPS["Diff4th"].oracle.PARAMS),
+                                           ("tgv", TGV_PARAMS))
              for g in E.groups_of(op) for p in sorted(params)]
 
 
@@ -92,7 +78,7 @@ def test_march_edges_equal_the_oracle(op, group, pname, kind):
         f = _field(kind, case.shape)
         want = _want(op, kind, case.shape, pname)
         for n in COUNTS:
-            _same_bits(_run(_gpu(op, pname, n), f), want[n], (op, case, kind, pname, n))
+            same_bits(_run(_gpu(op, pname, n), f), want[n], (op, case, kind, pname, n))
 
 
 # ------------------------------------------------------------------------------------------------ ROF_TV, PD_TV
@@ -143,7 +129,7 @@ def test_roftv_edges_equal_the_oracle(oracle, group, kind):
                 for iters in (1, 6):
                     want = _oracle_rof(oracle, x, 0.05, 0.005, iters, half)
                     got = _run(lambda a, out: ops.roftv(a, out, np.float32(0.05), np.float32(0.005), iters, half), x)
-                    _same_bits(got, want, (case, label, half, iters))
+                    same_bits(got, want, (case, label, half, iters))
 
 
 # (the two K = 2 workgroup shapes differ in rows only: their x and z shapes are run once)
@@ -190,16 +176,14 @@ def _chunked(op, schedule):
 @pytest.mark.parametrize("schedule", ["plain", "ranges"])
 @pytest.mark.parametrize("penalty", ["Huber", "PM", "Tukey"])
 def test_ndf_chunked_slabs_equal_whole_volume(schedule, penalty):
-    import test_gpu_ndf as G
     s = _chunked("NDF", schedule)
-    G.test_ndf_slabs_equal_whole_volume(s.world, schedule, penalty, shape=s.shape)
+    G.check_slabs_equal_whole_volume("NDF", s.world, schedule, {"Huber": "A", "PM": "B", "Tukey": "C"}[penalty], shape=s.shape)
 
 
 @pytest.mark.parametrize("schedule", ["plain", "ranges"])
 def test_diff4th_chunked_slabs_equal_whole_volume(schedule):
-    import test_gpu_diff4th as G
     s = _chunked("Diff4th", schedule)
-    G.test_diff4th_slabs_equal_whole_volume(s.world, schedule, "A", shape=s.shape)
+    G.check_slabs_equal_whole_volume("Diff4th", s.world, schedule, "A", shape=s.shape)
 
 
 @pytest.mark.parametrize("half", [False, True])

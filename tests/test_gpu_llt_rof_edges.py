@@ -18,42 +18,27 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import _llt_rof_edge_shapes as LE  # noqa: E402
-import _llt_rof_oracle as D  # noqa: E402
+import _march_gpu as G  # noqa: E402
+from _llt_rof_oracle import ORACLE as D  # noqa: E402
+from _march_gpu import same_bits  # noqa: E402
+from _tgv_oracle import phantom  # noqa: E402
 
 COUNTS = (1, 2, 5)   # the direct input-to-output launch and both parities of the ping-pong
 KINDS = ["phantom", "terraces", "scaled"]
 
 
-def host(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want, what):
-    assert got.dtype == want.dtype == np.float32 and got.shape == want.shape, what
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        raise AssertionError((what, f"{len(bad)} of {got.size} values differ, first at {tuple(bad[0])}",
-                              float(np.abs(got.astype(np.float64) - want).max())))
-
-
 def _run(f_host, p, n):
     """n iterations on the GPU into a NaN-filled output; the input's bits are checked afterwards"""
-    from tomobar_amd import ops
-    x = torch.from_numpy(f_host).cuda()
-    out = torch.full_like(x, float("nan"))
-    ops.llt_rof(x, out, np.float32(p["lam_rof"]), np.float32(p["lam_llt"]), np.float32(p["tau"]), n)
-    assert np.array_equal(host(x).view(np.uint32), f_host.view(np.uint32)), "the input was written"
-    return host(out)
+    return G.march("LLT_ROF", f_host, p, n)[0]
 
 
 def _fields(kind, shape):
     """[(label, input)]"""
     if kind == "phantom":
-        return [("phantom", D.phantom(shape))]
+        return [("phantom", phantom(shape))]
     if kind == "terraces":
         return [("terraces", LE.terraces(shape))]
-    return [(f"phantom*2^{e}", LE.scaled(D.phantom(shape), e)) for e in LE.SCALE_EXPONENTS]
+    return [(f"phantom*2^{e}", LE.scaled(phantom(shape), e)) for e in LE.SCALE_EXPONENTS]
 
 
 @functools.lru_cache(maxsize=None)
@@ -61,7 +46,7 @@ def _want(kind, shape, pname):
     """[(label, input, {n: the float32 numpy oracle after n iterations})], computed once per session and never modified"""
     out = []
     for label, f in _fields(kind, shape):
-        res = D.llt_rof_many(f, D.PARAMS[pname], COUNTS)
+        res = D.many(f, D.PARAMS[pname], COUNTS)
         for v in res.values():
             v.setflags(write=False)
         f.setflags(write=False)
@@ -77,14 +62,14 @@ def test_march_edges_equal_the_oracle(group, pname, kind):
     for case in LE.cases(group):
         for label, f, want in _want(kind, case.shape, pname):
             for n in COUNTS:
-                _same_bits(_run(np.array(f), D.PARAMS[pname], n), want[n], (case, label, pname, n))
+                same_bits(_run(np.array(f), D.PARAMS[pname], n), want[n], (case, label, pname, n))
 
 
 def test_terraces_take_the_zero_quotients_at_every_shape_used():
     """from the oracle: s == 0 on at least a quarter of the voxels entering iteration 1 at every `terraces` shape"""
     for shape in LE.terrace_shapes():
         stats = {}
-        D.llt_rof(LE.terraces(shape), iterations=1, stats=stats, **D.PARAMS["A"])
+        D.run(LE.terraces(shape), iterations=1, stats=stats, **D.PARAMS["A"])
         assert 0.25 <= stats["s_zero", 1] < 1.0, (shape, stats)
 
 
@@ -93,9 +78,9 @@ def test_terraces_take_the_zero_quotients_at_every_shape_used():
 def test_terraces_over_several_blocks(shape, pname):
     """(20, 24, 70) and (40, 130): more than one wave in x and y, three z-levels of blocks"""
     f = LE.terraces(shape)
-    want = D.llt_rof_many(f, D.PARAMS[pname], COUNTS)
+    want = D.many(f, D.PARAMS[pname], COUNTS)
     for n in COUNTS:
-        _same_bits(_run(f, D.PARAMS[pname], n), want[n], (shape, pname, n))
+        same_bits(_run(f, D.PARAMS[pname], n), want[n], (shape, pname, n))
 
 
 # ------------------------------------------------------------------------------------------------ chunked z-slabs
@@ -105,13 +90,12 @@ def test_llt_rof_chunked_slabs_equal_whole_volume(schedule, kind, iters=6):
     """two ranks of 33 local planes: every slab launch is z-chunked (three chunks over all local planes, rank 1's first
     starting at its ghost planes; the interior launch of the "ranges" schedule starts past the boundary planes and is still
     chunked)"""
-    import test_gpu_llt_rof as G
     from tomobar_amd.slab import slab_bounds
     s = LE.SLAB
     for sizes in LE.slab_launch_chunks(schedule):
         assert len(sizes) >= (3 if schedule == "plain" else 2), (schedule, sizes)
-    f = D.phantom(s.shape) if kind == "phantom" else LE.terraces(s.shape)
-    want = D.llt_rof(f, iterations=iters, **D.PARAMS["A"])
+    f = phantom(s.shape) if kind == "phantom" else LE.terraces(s.shape)
+    want = D.run(f, iterations=iters, **D.PARAMS["A"])
     vd = torch.from_numpy(f).cuda()
-    got = G._run_slabs(vd, [slab_bounds(s.shape[0], s.world, r) for r in range(s.world)], schedule, "A", iters)
-    _same_bits(got, want, (s.shape, schedule, kind))
+    got = G.run_slabs("LLT_ROF", vd, [slab_bounds(s.shape[0], s.world, r) for r in range(s.world)], schedule, "A", iters)
+    same_bits(got, want, (s.shape, schedule, kind))

@@ -14,7 +14,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import _edge_shapes as E  # noqa: E402
 import _llt_rof_edge_shapes as LE  # noqa: E402
-import _llt_rof_oracle as D  # noqa: E402
+from _llt_rof_oracle import ORACLE as D  # noqa: E402
+from _tgv_oracle import phantom  # noqa: E402
 
 CSRC = os.path.join(ROOT, "tomobar_amd", "csrc")
 
@@ -95,7 +96,7 @@ def test_terraces_reach_the_exact_zero_quotients_at_every_shape_used():
     never gets there"""
     for shape in LE.terrace_shapes():
         stats = {}
-        out = D.llt_rof(LE.terraces(shape), iterations=2, stats=stats, **D.PARAMS["A"])
+        out = D.run(LE.terraces(shape), iterations=2, stats=stats, **D.PARAMS["A"])
         assert np.all(np.isfinite(out)), shape
         assert 0.25 <= stats["s_zero", 1] < 1.0, (shape, stats)
         assert 0.25 <= stats["h1_tiny", 1], (shape, stats)
@@ -104,7 +105,7 @@ def test_terraces_reach_the_exact_zero_quotients_at_every_shape_used():
             print(f"LLT_ROF terraces {shape}: s == 0 on {stats['s_zero', 1]:.3f} of the voxels entering iteration 1, "
                   f"{stats['s_zero', 2]:.3f} entering iteration 2")
     stats = {}
-    D.llt_rof(D.phantom((7, 13, 37)), iterations=1, stats=stats, **D.PARAMS["A"])
+    D.run(phantom((7, 13, 37)), iterations=1, stats=stats, **D.PARAMS["A"])
     assert stats["s_zero", 1] < 0.01
 
 
@@ -112,7 +113,7 @@ def test_scaled_inputs_move_the_data_across_eps():
     """the phantom's s = |forward differences|^2 is of the order of 1e1: times 2^-14 it is of the order of eps = 1e-8 (the
     median within a factor of 100 of it, so eps is a visible part of n = sqrt(s + eps)), times 2^10 eps lies below half an
     ulp of s on nearly every voxel (s + eps == s); both inputs stay in the normal range"""
-    f = D.phantom((7, 13, 37))
+    f = phantom((7, 13, 37))
     eps = np.float32(1e-8)
     med, absorbed = {}, {}
     for e in LE.SCALE_EXPONENTS:

@@ -14,6 +14,7 @@ anything: without the library or without a GPU the operators raise.
 __version__ = "0.1.0"
 
 from . import _lib  # noqa: F401
+from .supp.regularisers import KINDS as _KINDS
 
 
 def library_path() -> str:
@@ -21,8 +22,8 @@ def library_path() -> str:
 
 
 def __getattr__(name):
-    # `from tomobar_amd import NDF_cupy` (or Diff4th_cupy, LLT_ROF_cupy) without importing torch at package import
-    if name in ("NDF_cupy", "Diff4th_cupy", "LLT_ROF_cupy"):
+    # `from tomobar_amd import NDF_cupy` (any *_cupy of supp/regularisers.py) without importing torch at package import
+    if any(name == k.cupy for k in _KINDS):
         from . import regularisersCuPy
         return getattr(regularisersCuPy, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .supp.regularisers import BY_NAME
 
 
 def _require_gpu(device_index: int) -> torch.device:
@@ -331,8 +332,7 @@ def placed_empty(specs, device, slot: int = 0):
     ``ARRAY_SKEW`` apart; a lease token).  The block belongs to the library (grow-only per (device, stream, slot), freed
     by ``tomo_release_scratch``): the tensors are views for the duration of ONE driver call, not allocations to keep, and
     a second ``placed_empty`` on the same (device, stream, slot) supersedes them -- ``lease_is_current(token)`` tells.
-    Slots in use: 0 = PD_TV slab driver, 1 = ROF_TV slab driver, 2 = NDF slab driver, 3 = Diff4th slab driver, 4 = LLT_ROF
-    slab driver (tomobar_amd/slab.py)."""
+    Slots in use: the ``slot`` of the records of tomobar_amd/supp/regularisers.py, one per slab driver."""
     device = torch.device(device)
     sizes, total = [], 0
     for shape, dtype in specs:
@@ -372,18 +372,8 @@ def reserve_tv_scratch(shape, device, method: str = "PD_TV", half: bool = False)
     nd = len(shape)
     dz, dy, dx = (1, *shape) if nd == 2 else shape
     lib = L.lib()
-    if method == "PD_TV":
-        nbytes = lib.tomo_pdtv_scratch_bytes(dx, dy, dz, nd, int(bool(half)))
-    elif method == "TGV":
-        nbytes = lib.tomo_tgv_scratch_bytes(dx, dy, dz, nd)
-    elif method == "NDF":
-        nbytes = lib.tomo_ndf_scratch_bytes(dx, dy, dz, nd)
-    elif method == "Diff4th":
-        nbytes = lib.tomo_diff4th_scratch_bytes(dx, dy, dz, nd)
-    elif method == "LLT_ROF":
-        nbytes = lib.tomo_llt_rof_scratch_bytes(dx, dy, dz, nd)
-    else:
-        nbytes = lib.tomo_roftv_scratch_bytes(dx, dy, dz, nd)
+    kind = BY_NAME.get(method, BY_NAME["ROF_TV"])
+    nbytes = getattr(lib, kind.scratch)(dx, dy, dz, nd, *([int(bool(half))] if kind.scratch_half else []))
     with torch.cuda.device(device):
         L.check(lib.tomo_reserve_scratch(device.index or 0, nbytes, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
 

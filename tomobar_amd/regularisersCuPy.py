@@ -21,14 +21,15 @@ import torch
 
 from . import ops
 from .convergence import check_tolerance
+from .supp.regularisers import kind_of
 
 _last = threading.local()
 
 
 def last_prox() -> Optional[Tuple[int, float]]:
-    """(iterations_done, rel_change) of the calling thread's most recent ``prox_regul`` / ``PD_TV_cupy`` / ``ROF_TV_cupy`` /
-    ``TGV_cupy`` / ``NDF_cupy`` / ``Diff4th_cupy`` / ``LLT_ROF_cupy`` call: how many inner iterations ran and the last relative change the stopping rule evaluated (NaN if it evaluated
-    none, e.g. with the tolerance off); None before the first call."""
+    """(iterations_done, rel_change) of the calling thread's most recent ``prox_regul`` or ``*_cupy`` call (the functions
+    supp/regularisers.py names): how many inner iterations ran and the last relative change the stopping rule evaluated
+    (NaN if it evaluated none, e.g. with the tolerance off); None before the first call."""
     return getattr(_last, "value", None)
 
 
@@ -53,83 +54,38 @@ def prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch
 
 def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch.Tensor:
     method = _regularisation_["method"]
+    kind = kind_of(method)
     slab = getattr(self, "slab", None)
     check_prox_available(self, X.shape, _regularisation_)
     tol = check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']")
+    if kind is None:
+        raise ValueError(f"unknown regularisation method {method!r}: ROF_TV, PD_TV and TGV are supported, as are NDF, Diff4th "
+                         "and LLT_ROF")
+    args = kind.args(_regularisation_, self)
+    half = (_regularisation_.get("half_precision", False),) if kind.half else ()
     if slab is not None and X.dim() == 3 and min(X.shape) > 1:
         # the volume is one z-slab of a larger one: 3D TV with ghost planes exchanged between z-neighbours
-        from .slab import diff4th_slab, llt_rof_slab, ndf_slab, pd_tv_slab, rof_tv_slab
-        X = ops.contiguous(X)
+        from . import slab as slab_drivers
         info = {"iterations_done": _regularisation_["iterations"], "rel_change": float("nan")}
-        res = None
-        if "ROF_TV" in method:
-            res = rof_tv_slab(X, slab, _regularisation_["regul_param"], _regularisation_["iterations"],
-                              _regularisation_["time_marching_step"], _regularisation_.get("half_precision", False),
-                              out=out, tolerance=tol, info=info)
-        elif "PD_TV" in method:
-            res = pd_tv_slab(X, slab, _regularisation_["regul_param"], _regularisation_["iterations"],
-                             _regularisation_["methodTV"], self.nonneg_regul, _regularisation_["PD_LipschitzConstant"],
-                             _regularisation_.get("half_precision", False), out=out, tolerance=tol,
-                             info=info)
-        elif "TGV" not in method and "NDF" in method:
-            res = ndf_slab(X, slab, _regularisation_["regul_param"], _regularisation_.get("edge_threshold", 0.01),
-                           _regularisation_["iterations"], _regularisation_["time_marching_step"],
-                           _regularisation_.get("NDF_penalty", "Huber"), out=out, tolerance=tol, info=info)
-        elif "TGV" not in method and "Diff4th" in method:
-            res = diff4th_slab(X, slab, _regularisation_["regul_param"], _regularisation_.get("edge_threshold", 0.01),
-                               _regularisation_["iterations"], _regularisation_["time_marching_step"], out=out,
-                               tolerance=tol, info=info)
-        elif "TGV" not in method and "LLT_ROF" in method:
-            res = llt_rof_slab(X, slab, _regularisation_["regul_param"], _regularisation_.get("regul_param2", 0.001),
-                               _regularisation_["iterations"], _regularisation_["time_marching_step"], out=out,
-                               tolerance=tol, info=info)
-        if res is not None:
-            _record(info["iterations_done"], info["rel_change"])
-            return res
-    if "ROF_TV" in method:
-        return ROF_TV_cupy(X, _regularisation_["regul_param"], _regularisation_["iterations"],
-                           _regularisation_["time_marching_step"], self.Atools.device_index,
-                           _regularisation_.get("half_precision", False), out=out, tolerance=tol)
-    if "PD_TV" in method:
-        return PD_TV_cupy(X, _regularisation_["regul_param"], _regularisation_["iterations"],
-                          _regularisation_["methodTV"], self.nonneg_regul, _regularisation_["PD_LipschitzConstant"],
-                          self.Atools.device_index, _regularisation_.get("half_precision", False), out=out,
-                          tolerance=tol)
-    if "TGV" in method:
-        return TGV_cupy(X, _regularisation_["regul_param"], _regularisation_["iterations"],
-                        _regularisation_.get("TGV_alpha1", 1.0), _regularisation_.get("TGV_alpha2", 2.0),
-                        _regularisation_["PD_LipschitzConstant"], self.Atools.device_index, out=out, tolerance=tol)
-    if "NDF" in method:
-        return NDF_cupy(X, _regularisation_["regul_param"], _regularisation_.get("edge_threshold", 0.01),
-                        _regularisation_["iterations"], _regularisation_["time_marching_step"],
-                        _regularisation_.get("NDF_penalty", "Huber"), self.Atools.device_index, out=out, tolerance=tol)
-    if "Diff4th" in method:
-        return Diff4th_cupy(X, _regularisation_["regul_param"], _regularisation_.get("edge_threshold", 0.01),
-                            _regularisation_["iterations"], _regularisation_["time_marching_step"],
-                            self.Atools.device_index, out=out, tolerance=tol)
-    if "LLT_ROF" in method:
-        return LLT_ROF_cupy(X, _regularisation_["regul_param"], _regularisation_.get("regul_param2", 0.001),
-                            _regularisation_["iterations"], _regularisation_["time_marching_step"],
-                            self.Atools.device_index, out=out, tolerance=tol)
-    raise ValueError(f"unknown regularisation method {method!r}: ROF_TV, PD_TV and TGV are supported, as are NDF, Diff4th "
-                     "and LLT_ROF")
+        res = getattr(slab_drivers, kind.slab)(ops.contiguous(X), slab, *args, *half, out=out, tolerance=tol, info=info)
+        _record(info["iterations_done"], info["rel_change"])
+        return res
+    return globals()[kind.cupy](X, *args, self.Atools.device_index, *half, out=out, tolerance=tol)
 
 
 def check_prox_available(self, vol_shape, _regularisation_: dict) -> None:
     """What TGV cannot do yet, as a ValueError before any work is done: z-slab mode on a real 3D volume (the halo protocol
     for its 13 further fields does not exist) and binary16 storage of its fields.  NDF, Diff4th and LLT_ROF have no binary16
     storage either (they do run in z-slab mode).  The other methods pass."""
-    method = _regularisation_.get("method")
-    if method is None or "ROF_TV" in method or "PD_TV" in method:
+    kind = kind_of(_regularisation_.get("method"))
+    if kind is None:
         return
-    kind = next((k for k in ("TGV", "NDF", "Diff4th", "LLT_ROF") if k in method), None)   # the order prox_regul dispatches in
-    if kind is not None and _regularisation_.get("half_precision", False):
-        raise ValueError(f"{kind} does not support half_precision=True")
-    if kind != "TGV":
-        return
-    shape = tuple(int(v) for v in vol_shape)
-    if getattr(self, "slab", None) is not None and len(shape) == 3 and min(shape) > 1:
-        raise ValueError("TGV is not available in z-slab mode")
+    if not kind.half and _regularisation_.get("half_precision", False):
+        raise ValueError(f"{kind.name} does not support half_precision=True")
+    if kind.slab is None and getattr(self, "slab", None) is not None:
+        shape = tuple(int(v) for v in vol_shape)
+        if len(shape) == 3 and min(shape) > 1:
+            raise ValueError(f"{kind.name} is not available in z-slab mode")
 
 
 def reserve_prox_scratch(self, vol_shape, _regularisation_: dict) -> None:
@@ -138,18 +94,15 @@ def reserve_prox_scratch(self, vol_shape, _regularisation_: dict) -> None:
     to `tries` x arena) is not part of the first proximal step.  No reference counterpart (CuPy's pool allocates the nine
     arrays inside every call, regularisersCuPy.py:220-232).  Nothing to do without a TV method, and in z-slab mode the
     slab drivers take their own placed block (slab.py)."""
-    method = _regularisation_.get("method")
     check_prox_available(self, vol_shape, _regularisation_)
-    if method is None or getattr(self, "slab", None) is not None:
+    kind = kind_of(_regularisation_.get("method"))
+    if kind is None or getattr(self, "slab", None) is not None:
         return
     shape = tuple(int(v) for v in vol_shape)
     if len(shape) == 3 and 1 in shape:       # a singleton axis runs the 2D kernels (_check_if_input_2d_or_3d)
         i = shape.index(1)
         shape = shape[:i] + shape[i + 1:]
-    kind = next((k for k in ("ROF_TV", "PD_TV", "TGV", "NDF", "Diff4th", "LLT_ROF") if k in method), None)   # the order prox_regul dispatches in
-    if kind is None:
-        return
-    ops.reserve_tv_scratch(shape, f"cuda:{self.Atools.device_index}", kind, bool(_regularisation_.get("half_precision", False)))
+    ops.reserve_tv_scratch(shape, f"cuda:{self.Atools.device_index}", kind.name, bool(_regularisation_.get("half_precision", False)))
 
 
 def _prepare(data, gpu_id: int):

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from .convergence import check_tolerance, inner_check_due, relative_change
+from .supp.regularisers import BY_NAME
 
 
 def slab_bounds(nz_total: int, world: int, rank: int):
@@ -477,7 +478,9 @@ class PdSlab:
         return [self.inp[h:h + GHOST]] if self.has_hi else []
 
 
-PLACED_SLOT_PD, PLACED_SLOT_ROF, PLACED_SLOT_NDF, PLACED_SLOT_DIFF4TH, PLACED_SLOT_LLT_ROF = 0, 1, 2, 3, 4   # one placed block per operator: solvers of different operators on one stream never alias
+# one placed block per operator: solvers of different operators on one stream never alias
+PLACED_SLOT_PD, PLACED_SLOT_ROF, PLACED_SLOT_NDF, PLACED_SLOT_DIFF4TH, PLACED_SLOT_LLT_ROF = (
+    BY_NAME[name].slot for name in ("PD_TV", "ROF_TV", "NDF", "Diff4th", "LLT_ROF"))
 
 
 def _hip_alloc(slot):
@@ -826,85 +829,48 @@ def _march_slab(st: MarchSlab, comm, data, iterations, params, out, overlap, tol
     return res.clone()
 
 
-# ------------------------------------------------------------------------------------------------ NDF on a slab
-class NdfSlab(MarchSlab):
-    """MarchSlab for NDF (docs/kernels/ndf.md): one ghost plane of U per interior boundary; ``step_fn`` receives the penalty
-    as its TOMO_NDF_* number after the three scalars."""
+# ------------------------------------------------------------------------------------- NDF, Diff4th, LLT_ROF on a slab
+def _march_kind(name: str, n_ints: int = 0):
+    """(the MarchSlab subclass, the HIP step, the driver) of the record ``name`` of supp/regularisers.py, which gives the ghost
+    depth, the placed slot and the C entry point; ``n_ints``: the integer parameters the operator takes after its three
+    float ones.  The subclass is called as (data, has_lo, has_hi, *ints, step_fn[, alloc]), the driver as
+    (data, comm, p0, p1, iterations, time_marching_parameter, *ints) with p0, p1 the operator's two parameters."""
+    kind = BY_NAME[name]
 
-    def __init__(self, data: torch.Tensor, has_lo: bool, has_hi: bool, penalty, step_fn: Callable,
-                 alloc: Optional[Callable] = None):
-        super().__init__(data, has_lo, has_hi, 1, step_fn, alloc, (penalty,))
-        self.penalty = penalty
+    class Slab(MarchSlab):
+        __doc__ = f"""MarchSlab for {name} (docs/kernels/{name.lower()}.md): {kind.ghost} ghost plane(s) of U per interior boundary."""
+
+        def __init__(self, data: torch.Tensor, has_lo: bool, has_hi: bool, *ints_step_alloc):
+            step_fn, *alloc = ints_step_alloc[n_ints:]
+            super().__init__(data, has_lo, has_hi, kind.ghost, step_fn, *alloc, ints=ints_step_alloc[:n_ints])
+
+    def driver(data: torch.Tensor, comm, p0, p1, iterations, time_marching_parameter, *ints,
+               step_fn: Optional[Callable] = None, out=None, overlap: bool = True, tolerance: float = 0.0,
+               info: Optional[dict] = None):
+        comm.validate_slabs(data.shape[0], kind.ghost)
+        # the HIP step is looked up by name on every call: the CPU tests replace the module attribute
+        st = Slab(data, comm.has_lo, comm.has_hi, *ints, step_fn or globals()[f"_hip_{name.lower()}_step"],
+                  _hip_alloc(kind.slot) if (step_fn is None and data.is_cuda) else None)
+        return _march_slab(st, comm, data, iterations, (p0, p1, time_marching_parameter), out, overlap, tolerance, info)
+
+    driver.__doc__ = f"""{name} of a z-slab of a larger 3D volume; bit-identical to running {kind.cupy} on the whole volume
+    (`tolerance`, `info`: see pd_tv_slab).  {kind.ghost} plane(s) of U travel each way after every iteration but the last, plus
+    one exchange of U^0 before the first.  Every slab must own at least as many planes: a neighbour's ghost planes come from
+    one rank."""
+    driver.__name__ = driver.__qualname__ = kind.slab
+    return Slab, _hip_march_step(kind.entry, n_ints), driver
 
 
-_hip_ndf_step = _hip_march_step("tomo_ndf_iter_slab_range", 1)
+NdfSlab, _hip_ndf_step, _ndf_slab = _march_kind("NDF", 1)   # the integer: the penalty as its TOMO_NDF_* number
+Diff4thSlab, _hip_diff4th_step, diff4th_slab = _march_kind("Diff4th")
+LltRofSlab, _hip_llt_rof_step, llt_rof_slab = _march_kind("LLT_ROF")   # the two parameters: the ROF and the LLT weight
+DIFF4TH_GHOST, LLT_ROF_GHOST = BY_NAME["Diff4th"].ghost, BY_NAME["LLT_ROF"].ghost
 
 
 def ndf_slab(data: torch.Tensor, comm, regularisation_parameter, edge_parameter, iterations, time_marching_parameter,
-             penalty_type="Huber", step_fn: Optional[Callable] = None, out=None, overlap: bool = True,
-             tolerance: float = 0.0, info: Optional[dict] = None):
-    """NDF of a z-slab of a larger 3D volume; bit-identical to running NDF_cupy on the whole volume (`tolerance`, `info`:
-    see pd_tv_slab).  One plane of U travels each way after every iteration but the last, plus one exchange of U^0 before
-    the first; `step_fn` receives the penalty as its TOMO_NDF_* number."""
+             penalty_type="Huber", **kw):
+    """The NDF driver of _march_kind with the penalty given by name ("Huber", "PM", "Tukey"); `step_fn` receives it as its
+    TOMO_NDF_* number."""
     from ._lib import ndf_penalty_id
-    penalty = ndf_penalty_id(penalty_type)
-    comm.validate_slabs(data.shape[0], 1)
-    st = NdfSlab(data, comm.has_lo, comm.has_hi, penalty, step_fn or _hip_ndf_step,
-                 alloc=_hip_alloc(PLACED_SLOT_NDF) if (step_fn is None and data.is_cuda) else None)
-    return _march_slab(st, comm, data, iterations, (regularisation_parameter, edge_parameter, time_marching_parameter), out,
-                       overlap, tolerance, info)
-
-
-# ------------------------------------------------------------------------------------------------ Diff4th on a slab
-DIFF4TH_GHOST = 2   # the stencil's radius: W at distance 1 needs U at distance 2
-
-
-class Diff4thSlab(MarchSlab):
-    """MarchSlab for Diff4th (docs/kernels/diff4th.md): two ghost planes of U per interior boundary."""
-
-    def __init__(self, data: torch.Tensor, has_lo: bool, has_hi: bool, step_fn: Callable, alloc: Optional[Callable] = None):
-        super().__init__(data, has_lo, has_hi, DIFF4TH_GHOST, step_fn, alloc)
-
-
-_hip_diff4th_step = _hip_march_step("tomo_diff4th_iter_slab_range")
-
-
-def diff4th_slab(data: torch.Tensor, comm, regularisation_parameter, edge_parameter, iterations, time_marching_parameter,
-                 step_fn: Optional[Callable] = None, out=None, overlap: bool = True, tolerance: float = 0.0,
-                 info: Optional[dict] = None):
-    """Diff4th of a z-slab of a larger 3D volume; bit-identical to running Diff4th_cupy on the whole volume (`tolerance`,
-    `info`: see pd_tv_slab).  Two planes of U travel each way after every iteration but the last, plus one exchange of U^0
-    before the first.  Every slab must own at least two planes: a neighbour's two ghost planes come from one rank."""
-    comm.validate_slabs(data.shape[0], DIFF4TH_GHOST)
-    st = Diff4thSlab(data, comm.has_lo, comm.has_hi, step_fn or _hip_diff4th_step,
-                     alloc=_hip_alloc(PLACED_SLOT_DIFF4TH) if (step_fn is None and data.is_cuda) else None)
-    return _march_slab(st, comm, data, iterations, (regularisation_parameter, edge_parameter, time_marching_parameter), out,
-                       overlap, tolerance, info)
-
-
-# ------------------------------------------------------------------------------------------------ LLT_ROF on a slab
-LLT_ROF_GHOST = 2   # the stencil's radius: E_d at distance 1 needs U at distance 2
-
-
-class LltRofSlab(MarchSlab):
-    """MarchSlab for LLT_ROF (docs/kernels/llt_rof.md): two ghost planes of U per interior boundary; the two parameters are
-    the ROF and the LLT weight."""
-
-    def __init__(self, data: torch.Tensor, has_lo: bool, has_hi: bool, step_fn: Callable, alloc: Optional[Callable] = None):
-        super().__init__(data, has_lo, has_hi, LLT_ROF_GHOST, step_fn, alloc)
-
-
-_hip_llt_rof_step = _hip_march_step("tomo_llt_rof_iter_slab_range")
-
-
-def llt_rof_slab(data: torch.Tensor, comm, regularisation_parameterROF, regularisation_parameterLLT, iterations, time_marching_parameter,
-                 step_fn: Optional[Callable] = None, out=None, overlap: bool = True, tolerance: float = 0.0,
-                 info: Optional[dict] = None):
-    """LLT_ROF of a z-slab of a larger 3D volume; bit-identical to running LLT_ROF_cupy on the whole volume (`tolerance`,
-    `info`: see pd_tv_slab).  Two planes of U travel each way after every iteration but the last, plus one exchange of U^0
-    before the first.  Every slab must own at least two planes: a neighbour's two ghost planes come from one rank."""
-    comm.validate_slabs(data.shape[0], LLT_ROF_GHOST)
-    st = LltRofSlab(data, comm.has_lo, comm.has_hi, step_fn or _hip_llt_rof_step,
-                    alloc=_hip_alloc(PLACED_SLOT_LLT_ROF) if (step_fn is None and data.is_cuda) else None)
-    return _march_slab(st, comm, data, iterations, (regularisation_parameterROF, regularisation_parameterLLT, time_marching_parameter),
-                       out, overlap, tolerance, info)
+    return _ndf_slab(data, comm, regularisation_parameter, edge_parameter, iterations, time_marching_parameter,
+                     ndf_penalty_id(penalty_type), **kw)

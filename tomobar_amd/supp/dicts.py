@@ -13,6 +13,7 @@ from typing import Optional
 from .. import ops
 from ..convergence import check_tolerance
 from .funcs import _data_dims_swapper
+from .regularisers import kind_of
 
 LABELS_3D = ["detY", "angles", "detX"]
 LABELS_2D = ["angles", "detX"]
@@ -118,33 +119,17 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
         for key, value in _REGULARISATION_DEFAULTS:
             _regularisation_.setdefault(key, value)
     check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']")
-    # TGV (no implementation in this reference version; the key names are the removed RecToolsIR class's: TGV_alpha2 is the
-    # weight of the second-order term, alpha0 in docs/kernels/tgv.md).  Dictionaries of the other methods are not touched.
-    method = _regularisation_.get("method")
-    if isinstance(method, str) and "TGV" in method and "ROF_TV" not in method and "PD_TV" not in method:
-        _regularisation_.setdefault("TGV_alpha1", 1.0)
-        _regularisation_.setdefault("TGV_alpha2", 2.0)
-        for key in ("TGV_alpha1", "TGV_alpha2"):
-            if not float(_regularisation_[key]) > 0.0:
-                raise ValueError(f"_regularisation_['{key}'] must be positive")
-    # NDF (named by the reference's comment on time_marching_step, tomobar/supp/dicts.py:173, implemented nowhere in its
-    # tree; docs/kernels/ndf.md).  Dictionaries of the other methods are not touched.
-    if isinstance(method, str) and "NDF" in method and not any(k in method for k in ("ROF_TV", "PD_TV", "TGV")):
-        _regularisation_.setdefault("NDF_penalty", "Huber")
-        _regularisation_.setdefault("edge_threshold", 0.01)
-        if _regularisation_["NDF_penalty"] not in ("Huber", "PM", "Tukey"):
-            raise ValueError("_regularisation_['NDF_penalty'] must be 'Huber', 'PM' or 'Tukey'")
-        if not float(_regularisation_["edge_threshold"]) > 0.0:
-            raise ValueError("_regularisation_['edge_threshold'] must be positive")
-    # Diff4th (the same comment of the reference names it; docs/kernels/diff4th.md): dispatched after the names above.
-    if isinstance(method, str) and "Diff4th" in method and not any(k in method for k in ("ROF_TV", "PD_TV", "TGV", "NDF")):
-        _regularisation_.setdefault("edge_threshold", 0.01)
-        if not float(_regularisation_["edge_threshold"]) > 0.0:
-            raise ValueError("_regularisation_['edge_threshold'] must be positive")
-    # LLT_ROF (the last name of that comment; docs/kernels/llt_rof.md): regul_param is the ROF weight, regul_param2 the LLT
-    # weight (the keys of the reference's removed RecToolsIR class).  Dispatched after the names above.
-    if isinstance(method, str) and "LLT_ROF" in method and not any(k in method for k in ("ROF_TV", "PD_TV", "TGV", "NDF", "Diff4th")):
-        _regularisation_.setdefault("regul_param2", 0.001)
-        if not float(_regularisation_["regul_param2"]) > 0.0:
-            raise ValueError("_regularisation_['regul_param2'] must be positive")
+    # the keys of the method prox_regul will run (supp/regularisers.py: TGV, NDF, Diff4th and LLT_ROF add some, none of them
+    # implemented in this reference version).  Dictionaries of the other methods are not touched.
+    kind = kind_of(_regularisation_.get("method"))
+    extra_keys = kind.defaults if kind is not None else ()
+    for key, value, _ in extra_keys:
+        _regularisation_.setdefault(key, value)
+    for key, _, choices in extra_keys:
+        if choices is not None:
+            if _regularisation_[key] not in choices:
+                named = ", ".join(repr(c) for c in choices[:-1]) + " or " + repr(choices[-1])
+                raise ValueError(f"_regularisation_['{key}'] must be {named}")
+        elif not float(_regularisation_[key]) > 0.0:
+            raise ValueError(f"_regularisation_['{key}'] must be positive")
     return (_data_, _algorithm_, _regularisation_)

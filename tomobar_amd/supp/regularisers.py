@@ -1,0 +1,81 @@
+"""The regularisers ``_regularisation_["method"]`` can name, in the order ``prox_regul`` dispatches in, and what follows
+from the choice: which function runs it, which scratch arena and placed slot it takes, which dictionary keys it adds.
+This is the one place the precedence is written: ``regularisersCuPy.prox_regul`` / ``check_prox_available`` /
+``reserve_prox_scratch``, ``dicts.dicts_check``, ``ops.reserve_tv_scratch``, the march drivers of ``slab`` and the package's
+lazy names all read it.  No reference counterpart (its ``prox_regul`` is a two-branch if, regularisersCuPy.py:16-38).
+
+Imports neither torch nor ``ops``.  Functions are held by NAME and looked up on their module when they are called:
+the CPU tests stand the oracle in for them by setting module attributes.
+"""
+
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+# the keys beyond the reference's, with the value an absent key stands for
+_DEFAULT = {"TGV_alpha1": 1.0, "TGV_alpha2": 2.0, "NDF_penalty": "Huber", "edge_threshold": 0.01, "regul_param2": 0.001}
+
+
+def _opt(reg, key):
+    return reg.get(key, _DEFAULT[key])
+
+
+def _keys(*checked):
+    """``defaults`` of a record: (key, default, choices) in the order dicts_check fills and then checks them; ``choices`` None
+    = the value must be positive, else the values it may take."""
+    return tuple((key, _DEFAULT[key], choices) for key, choices in checked)
+
+
+class Kind(NamedTuple):
+    name: str              # the substring of _regularisation_["method"]
+    cupy: str              # the whole-volume function in regularisersCuPy
+    slab: Optional[str]    # the z-slab driver in slab (None: not available in z-slab mode)
+    scratch: str           # the C symbol that sizes the scratch arena ...
+    scratch_half: bool     # ... and whether it takes `half` after (dx, dy, dz, nd)
+    half: bool             # half_precision=True is accepted, and passed on as the last positional argument
+    slot: Optional[int]    # the placed block of the slab driver (ops.placed_empty): one per operator, so that solvers of
+    #                        different operators on one stream never alias
+    ghost: Optional[int]   # ghost planes of U per interior boundary of a MarchSlab (PdSlab / RofSlab: asymmetric, their own)
+    entry: Optional[str]   # the C entry point of one MarchSlab iteration
+    defaults: tuple        # see _keys
+    args: object           # args(reg, self): the positional arguments after the array (slab driver: after the communicator);
+    #                        the *_cupy call appends the device index, both append half_precision where `half`
+
+
+KINDS = (
+    Kind("ROF_TV", "ROF_TV_cupy", "rof_tv_slab", "tomo_roftv_scratch_bytes", False, True, 1, None, None, (),
+         lambda reg, self: (reg["regul_param"], reg["iterations"], reg["time_marching_step"])),
+    Kind("PD_TV", "PD_TV_cupy", "pd_tv_slab", "tomo_pdtv_scratch_bytes", True, True, 0, None, None, (),
+         lambda reg, self: (reg["regul_param"], reg["iterations"], reg["methodTV"], self.nonneg_regul,
+                            reg["PD_LipschitzConstant"])),
+    # TGV_alpha2 is the weight of the second-order term, alpha0 in docs/kernels/tgv.md (the key names are those of the
+    # reference's removed RecToolsIR class); the halo protocol for its 13 further fields does not exist
+    Kind("TGV", "TGV_cupy", None, "tomo_tgv_scratch_bytes", False, False, None, None, None,
+         _keys(("TGV_alpha1", None), ("TGV_alpha2", None)),
+         lambda reg, self: (reg["regul_param"], reg["iterations"], _opt(reg, "TGV_alpha1"), _opt(reg, "TGV_alpha2"),
+                            reg["PD_LipschitzConstant"])),
+    # NDF, Diff4th, LLT_ROF: named by the reference's comment on time_marching_step (tomobar/supp/dicts.py:173), implemented
+    # nowhere in its tree (docs/kernels/ndf.md, diff4th.md, llt_rof.md)
+    Kind("NDF", "NDF_cupy", "ndf_slab", "tomo_ndf_scratch_bytes", False, False, 2, 1, "tomo_ndf_iter_slab_range",
+         _keys(("NDF_penalty", ("Huber", "PM", "Tukey")), ("edge_threshold", None)),
+         lambda reg, self: (reg["regul_param"], _opt(reg, "edge_threshold"), reg["iterations"], reg["time_marching_step"],
+                            _opt(reg, "NDF_penalty"))),
+    # ghost 2 = the stencil's radius: W at distance 1 needs U at distance 2
+    Kind("Diff4th", "Diff4th_cupy", "diff4th_slab", "tomo_diff4th_scratch_bytes", False, False, 3, 2,
+         "tomo_diff4th_iter_slab_range", _keys(("edge_threshold", None)),
+         lambda reg, self: (reg["regul_param"], _opt(reg, "edge_threshold"), reg["iterations"], reg["time_marching_step"])),
+    # regul_param is the ROF weight, regul_param2 the LLT weight (keys of the removed RecToolsIR class); ghost 2 = the
+    # stencil's radius: E_d at distance 1 needs U at distance 2
+    Kind("LLT_ROF", "LLT_ROF_cupy", "llt_rof_slab", "tomo_llt_rof_scratch_bytes", False, False, 4, 2,
+         "tomo_llt_rof_iter_slab_range", _keys(("regul_param2", None)),
+         lambda reg, self: (reg["regul_param"], _opt(reg, "regul_param2"), reg["iterations"], reg["time_marching_step"])),
+)
+BY_NAME = {k.name: k for k in KINDS}
+
+
+def kind_of(method) -> Optional[Kind]:
+    """The record ``method`` means: the first of KINDS whose name is a substring of it; None for None, for anything that is
+    not a string and for a string that names none."""
+    if not isinstance(method, str):
+        return None
+    return next((k for k in KINDS if k.name in method), None)

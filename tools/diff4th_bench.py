@@ -11,112 +11,29 @@ operator: ms per iteration, the operator's algorithmic traffic per iteration, th
 plain-copy rate measured on this hardware (6.2 TB/s, profiles/archive/r4b_hbm_copy_probe.txt); the Diff4th line also
 carries its time as a ratio to NDF's and TGV's.  `--out profiles/diff4th_bench.jsonl` keeps the lines.  Kernel times: run
 the same command under `rocprofv3 --kernel-trace --stats` in a run of its own."""
-import argparse
-import json
-import os
-import statistics
-import sys
+import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-COPY_RATE_GBPS = 6200.0
-BYTES_PER_VOXEL = 12                   # Diff4th and NDF: U and f read, U' written
-TGV_BYTES_PER_VOXEL = {3: 176, 2: 112}
+import _prox_bench as B
 
 
-def algorithmic_bytes(shape, per_voxel=BYTES_PER_VOXEL):
-    n = 1
-    for v in shape:
-        n *= v
-    return n * per_voxel
-
-
-def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default="512x512x512,1024x1024x1024,4096x4096")
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--short", type=int, default=4)
-    ap.add_argument("--long", type=int, default=14)
-    ap.add_argument("--no-ndf", action="store_true", help="skip the NDF comparison")
-    ap.add_argument("--no-tgv", action="store_true", help="skip the TGV comparison")
-    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
-    args = ap.parse_args(argv)
-    if not 0 < args.short < args.long or args.reps < 1:
-        ap.error("need 0 < --short < --long and --reps >= 1")
-    shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
-    for s in shapes:
-        if len(s) not in (2, 3) or min(s) < 1:
-            ap.error(f"bad shape {s}")
-
-    import numpy as np
-    import torch
+def runs_of(args, shape, x, out):
     from tomobar_amd import ops
-    if not torch.cuda.is_available():
-        raise SystemExit("diff4th_bench needs a GPU (there is no CPU path)")
     # tau (1 + 16 nd^2 lam) = 0.73 in 3D: inside the stability bound; sigma of the size of the synthetic gradient
     lam, sigma, tau = np.float32(1.0), np.float32(2.0), np.float32(0.005)
     tgv_tau = np.float32(np.float32(1.0) / np.sqrt(np.float32(12.0)))
-    lines = []
-    for shape in shapes:
-        gen = torch.Generator(device="cuda").manual_seed(3)
-        # a noisy ramp scaled like the tests' phantom: gradients on both sides of the threshold
-        x = torch.rand(shape, device="cuda", generator=gen) * 4.0
-        x += torch.arange(shape[-1], device="cuda", dtype=torch.float32) * 1.2
-        out = torch.empty_like(x)
-        if not args.no_tgv:
-            ops.reserve_tv_scratch(shape, "cuda:0", "TGV")   # the largest of the arenas: nothing is re-placed in between
-        ops.reserve_tv_scratch(shape, "cuda:0", "Diff4th")
-        gx = 0.5 * (x[..., 2:] - x[..., :-2])
-        active = float((gx * gx > float(sigma) ** 2).float().mean())
-        del gx
-
-        runs = [("diff4th", BYTES_PER_VOXEL, lambda n: ops.diff4th(x, out, lam, sigma, tau, n))]
-        if not args.no_ndf:
-            runs.append(("ndf_Huber", BYTES_PER_VOXEL, lambda n: ops.ndf(x, out, lam, sigma, np.float32(0.05), "Huber", n)))
-        if not args.no_tgv:
-            runs.append(("tgv", TGV_BYTES_PER_VOXEL[len(shape)], lambda n: ops.tgv(x, out, 5.0, 1.0, 2.0, tgv_tau, tgv_tau, n)))
-        first = len(lines)
-        for name, per_voxel, call in runs:
-            def run(iters):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                call(iters)
-                e1.record()
-                torch.cuda.synchronize()
-                return e0.elapsed_time(e1)
-
-            run(args.short)   # warm-up: code objects, the arena
-            per_iter, calls = [], []
-            for _ in range(args.reps):
-                ts, tl = run(args.short), run(args.long)
-                per_iter.append((tl - ts) / (args.long - args.short))
-                calls.append(tl)
-            ms = statistics.median(per_iter)
-            nbytes = algorithmic_bytes(shape, per_voxel)
-            rate = nbytes / (ms * 1e-3) / 1e9
-            line = {"op": name, "shape": list(shape), "ms_per_iteration": round(ms, 4),
-                    "ms_per_iteration_min_max": [round(min(per_iter), 4), round(max(per_iter), 4)],
-                    f"ms_per_call_{args.long}_iterations": round(statistics.median(calls), 3),
-                    "algorithmic_bytes_per_iteration": nbytes, "algorithmic_GBps": round(rate, 1),
-                    "ratio_to_copy_rate_6200_GBps": round(rate / COPY_RATE_GBPS, 3),
-                    "x_gradient_squared_above_sigma_squared": round(active, 3),
-                    "finite": bool(torch.isfinite(out).all()), "placement": ops.placement_last()}
-            print(json.dumps(line), flush=True)
-            lines.append(line)
-        ms_of = {ln["op"]: ln["ms_per_iteration"] for ln in lines[first:]}
-        for other in ("ndf_Huber", "tgv"):
-            if other in ms_of:
-                lines[first][f"time_ratio_to_{other}"] = round(ms_of["diff4th"] / ms_of[other], 3)
-        if len(ms_of) > 1:
-            print(json.dumps({"op": "diff4th_ratios", "shape": list(shape),
-                              **{k: v for k, v in lines[first].items() if k.startswith("time_ratio_to_")}}), flush=True)
-        del x, out
-        torch.cuda.empty_cache()
-    if args.out:
-        with open(args.out, "a") as fh:
-            for line in lines:
-                fh.write(json.dumps(line) + "\n")
+    if not args.no_tgv:
+        ops.reserve_tv_scratch(shape, "cuda:0", "TGV")   # the largest of the arenas: nothing is re-placed in between
+    ops.reserve_tv_scratch(shape, "cuda:0", "Diff4th")
+    gx = 0.5 * (x[..., 2:] - x[..., :-2])
+    active = float((gx * gx > float(sigma) ** 2).float().mean())
+    runs = [("diff4th", B.BYTES_PER_VOXEL, lambda n: ops.diff4th(x, out, lam, sigma, tau, n))]
+    if not args.no_ndf:
+        runs.append(("ndf_Huber", B.BYTES_PER_VOXEL, lambda n: ops.ndf(x, out, lam, sigma, np.float32(0.05), "Huber", n)))
+    if not args.no_tgv:
+        runs.append(("tgv", B.TGV_BYTES_PER_VOXEL[len(shape)], lambda n: ops.tgv(x, out, 5.0, 1.0, 2.0, tgv_tau, tgv_tau, n)))
+    return runs, {"x_gradient_squared_above_sigma_squared": round(active, 3)}
 
 
 if __name__ == "__main__":
-    main()
+    B.main("diff4th_bench", runs_of, ratios_of=("ndf_Huber", "tgv"),
+           options=[("--no-ndf", "skip the NDF comparison"), ("--no-tgv", "skip the TGV comparison")])

@@ -10,96 +10,24 @@ ms per iteration, the algorithmic traffic (3 floats = 12 B per voxel and iterati
 amounts to and its ratio to the plain-copy rate measured on this hardware (6.2 TB/s,
 profiles/archive/r4b_hbm_copy_probe.txt).  Kernel times: run the same command under `rocprofv3 --kernel-trace --stats` in
 a run of its own."""
-import argparse
-import json
-import os
-import statistics
-import sys
+import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _prox_bench as B
 
-COPY_RATE_GBPS = 6200.0
-BYTES_PER_VOXEL = 12
 PENALTIES = ("Huber", "PM", "Tukey")
 
 
-def algorithmic_bytes(shape):
-    n = 1
-    for v in shape:
-        n *= v
-    return n * BYTES_PER_VOXEL
-
-
-def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default="512x512x512,1024x1024x1024,4096x4096")
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--short", type=int, default=4)
-    ap.add_argument("--long", type=int, default=14)
-    ap.add_argument("--no-rof", action="store_true", help="skip the ROF_TV comparison")
-    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
-    args = ap.parse_args(argv)
-    if not 0 < args.short < args.long or args.reps < 1:
-        ap.error("need 0 < --short < --long and --reps >= 1")
-    shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
-    for s in shapes:
-        if len(s) not in (2, 3) or min(s) < 1:
-            ap.error(f"bad shape {s}")
-
-    import numpy as np
-    import torch
+def runs_of(args, shape, x, out):
     from tomobar_amd import ops
-    if not torch.cuda.is_available():
-        raise SystemExit("ndf_bench needs a GPU (there is no CPU path)")
     lam, sigma, tau = np.float32(1.0), np.float32(2.0), np.float32(0.05)
-    lines = []
-    for shape in shapes:
-        gen = torch.Generator(device="cuda").manual_seed(3)
-        # a noisy ramp scaled like the tests' phantom: differences on both sides of the threshold
-        x = torch.rand(shape, device="cuda", generator=gen) * 4.0
-        x += torch.arange(shape[-1], device="cuda", dtype=torch.float32) * 1.2
-        out = torch.empty_like(x)
-        ops.reserve_tv_scratch(shape, "cuda:0", "ROF_TV")   # the larger of the two arenas: nothing is re-placed in between
-        ops.reserve_tv_scratch(shape, "cuda:0", "NDF")
-        above = float(((x[..., 1:] - x[..., :-1]).abs() > float(sigma)).float().mean())
-
-        runs = [(f"ndf_{p}", (lambda n, p=p: ops.ndf(x, out, lam, sigma, tau, p, n))) for p in PENALTIES]
-        if not args.no_rof:
-            runs.append(("roftv", lambda n: ops.roftv(x, out, np.float32(0.05), np.float32(0.005), n, False)))
-        for name, call in runs:
-            def run(iters):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                call(iters)
-                e1.record()
-                torch.cuda.synchronize()
-                return e0.elapsed_time(e1)
-
-            run(args.short)   # warm-up: code objects, the arena
-            per_iter, calls = [], []
-            for _ in range(args.reps):
-                ts, tl = run(args.short), run(args.long)
-                per_iter.append((tl - ts) / (args.long - args.short))
-                calls.append(tl)
-            ms = statistics.median(per_iter)
-            nbytes = algorithmic_bytes(shape)
-            rate = nbytes / (ms * 1e-3) / 1e9
-            line = {"op": name, "shape": list(shape), "ms_per_iteration": round(ms, 4),
-                    "ms_per_iteration_min_max": [round(min(per_iter), 4), round(max(per_iter), 4)],
-                    f"ms_per_call_{args.long}_iterations": round(statistics.median(calls), 3),
-                    "algorithmic_bytes_per_iteration": nbytes, "algorithmic_GBps": round(rate, 1),
-                    "ratio_to_copy_rate_6200_GBps": round(rate / COPY_RATE_GBPS, 3),
-                    "x_differences_above_sigma": round(above, 3),
-                    "finite": bool(torch.isfinite(out).all()), "placement": ops.placement_last()}
-            print(json.dumps(line), flush=True)
-            lines.append(line)
-        del x, out
-        torch.cuda.empty_cache()
-    if args.out:
-        with open(args.out, "a") as fh:
-            for line in lines:
-                fh.write(json.dumps(line) + "\n")
+    ops.reserve_tv_scratch(shape, "cuda:0", "ROF_TV")   # the larger of the two arenas: nothing is re-placed in between
+    ops.reserve_tv_scratch(shape, "cuda:0", "NDF")
+    above = float(((x[..., 1:] - x[..., :-1]).abs() > float(sigma)).float().mean())
+    runs = [(f"ndf_{p}", B.BYTES_PER_VOXEL, (lambda n, p=p: ops.ndf(x, out, lam, sigma, tau, p, n))) for p in PENALTIES]
+    if not args.no_rof:
+        runs.append(("roftv", B.BYTES_PER_VOXEL, lambda n: ops.roftv(x, out, np.float32(0.05), np.float32(0.005), n, False)))
+    return runs, {"x_differences_above_sigma": round(above, 3)}
 
 
 if __name__ == "__main__":
-    main()
+    B.main("ndf_bench", runs_of, options=[("--no-rof", "skip the ROF_TV comparison")])

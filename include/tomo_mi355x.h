@@ -30,7 +30,7 @@ extern "C" {
 /* raised whenever a signature changes or an entry point is added (tomobar_amd/_lib.py checks it at load).  The three
  * tomo_diff4th* entry points joined version 10 without a raise: tests/test_ndf_oracle.py pins the number 10, and _lib.py
  * binds every symbol by name at load, so a library without them is refused all the same.  The three tomo_llt_rof* entry
- * points joined it the same way, for the same reason. */
+ * points joined it the same way, for the same reason.  So did the four tomo_wavelet_* entry points. */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -374,6 +374,34 @@ int tomo_diff4th(int device, const float *in_dev, float *out_dev, int dx, int dy
 int tomo_llt_rof(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
                  float lambda_rof, float lambda_llt, float tau, int iters,
                  double tol, int *iters_done, double *last_rel_change, void *stream);
+/* Wavelet shrinkage W_t, the `_WAVELETS` suffix of a regularisation method: every (y, x) slice (nd = 3: dz independent
+ * slices, nd = 2: one) goes through three levels of the 2D orthonormal Daubechies-5 transform in periodization mode (an
+ * odd line is extended by a copy of its last sample; x is filtered first, then y), every detail coefficient d of every
+ * level becomes copysign(max(|d| - threshold, 0), d), and the inverse transform follows.  The reference's tutorials use
+ * "PD_TV_WAVELETS" (docs/source/tutorials/regul_iter_recon.rst:113) but nothing in its tree implements the step (it lived
+ * in the removed RecToolsIR class, on the CUDA-only pypwt package): the algorithm, with its order of operations, is stated
+ * in docs/kernels/wavelets.md and restated in numpy by tests/_wavelet_oracle.py -- formula-level parity, unpinned; the
+ * float32 result equals that restatement bit for bit.
+ *   dims as for tomo_pdtv (a dimension of 1 is valid).  threshold >= 0 (0: the identity up to rounding).
+ *   The pyramid of a slice holds, for level l = 1, 2, 3 in this order (n_0 = n, n_l = ceil(n_{l-1} / 2)), the bands LL, LH,
+ *   HL, HH of dy_l x dx_l floats each (first letter: the x filter, second: the y filter); the pyramids of the slices follow
+ *   each other.  tomo_wavelet_scratch_bytes is the size of all of them (4 sum_l dy_l dx_l floats per slice, about 1.33
+ *   volumes; 0 for invalid dims).  LL_1 and LL_2 are work space: the forward pass leaves the approximations there, the
+ *   inverse pass overwrites them with its own.
+ *   tomo_wavelet_shrink: in_dev -> out_dev through a pyramid in the TV scratch arena of (device, stream), six launches (one
+ *   forward and one inverse per level: tiles staged in LDS with their circular apron, the threshold applied as the bands
+ *   are written).  mix_dev (or NULL): an array laid out like out_dev; the last launch then stores (mix + W_t(in)) * 0.5f,
+ *   reading mix at the index it writes, so mix_dev may be out_dev itself.  in_dev may alias out_dev.
+ *   tomo_wavelet_forward writes the thresholded pyramid of in_dev into pyramid_dev (the caller's, of
+ *   tomo_wavelet_scratch_bytes); tomo_wavelet_inverse reads one (and overwrites its LL_1 and LL_2) into out_dev.
+ *   TOMO_E_INVALID: a negative (or NaN) threshold, nd outside {2, 3}, a dimension < 1, a NULL array, a negative device. */
+size_t tomo_wavelet_scratch_bytes(int dx, int dy, int dz, int nd);
+int tomo_wavelet_shrink(int device, const float *in_dev, float *out_dev, const float *mix_dev, int dx, int dy, int dz,
+                        int nd, float threshold, void *stream);
+int tomo_wavelet_forward(int device, const float *in_dev, float *pyramid_dev, int dx, int dy, int dz, int nd,
+                         float threshold, void *stream);
+int tomo_wavelet_inverse(int device, float *pyramid_dev, float *out_dev, const float *mix_dev, int dx, int dy, int dz,
+                         int nd, void *stream);
 /* scratch bytes the TV drivers hold for a given problem (informational; a tolerance adds one float volume, see above) and
  * arena release.  tomo_tgv_scratch_bytes: 16 (nd = 3: U-bar, V, V-bar, P, six Q) or 10 (nd = 2) float arrays, each rounded
  * up to 256 bytes and followed by the 69888-byte array skew.  tomo_ndf_scratch_bytes, tomo_diff4th_scratch_bytes and

@@ -29,6 +29,7 @@ from .convergence import check_tolerance, relative_change
 from .projector import HipTools3D, geom_size
 from .regularisersCuPy import check_prox_available, last_prox, prox_regul, reserve_prox_scratch
 from .supp.dicts import dicts_check
+from .supp.regularisers import has_wavelets
 from .supp.suppTools import _apply_horiz_detector_padding, check_kwargs, perform_recon_crop
 
 
@@ -321,7 +322,7 @@ class RecToolsIRCuPy:
 
         Divergence from the reference, on purpose: ``regul_param / ADMM_rho_const`` is applied to a private copy of
         the regularisation dictionary (the reference rewrites the caller's dictionary on every call, :526-528); LLT_ROF's
-        second weight ``regul_param2`` is divided likewise."""
+        second weight ``regul_param2`` is divided likewise, and so is the wavelet threshold of a ``_WAVELETS`` method."""
         (d, a, r, x0, w, use_os) = self.__common_initialisation(_data_, _algorithm_, _regularisation_, "ADMM")
         A = self.Atools
         b = d["projection_data"]
@@ -333,7 +334,8 @@ class RecToolsIRCuPy:
         r_local = dict(r)
         if has_prox:
             r_local["regul_param"] = r["regul_param"] / rho
-            if "LLT_ROF" in r["method"] and "regul_param2" in r:   # both weights multiply the regulariser
+            # both weights multiply the regulariser: LLT_ROF's second weight and the threshold of the WAVELETS suffix
+            if ("LLT_ROF" in r["method"] or has_wavelets(r["method"])) and "regul_param2" in r:
                 r_local["regul_param2"] = r["regul_param2"] / rho
 
         x = x0

@@ -299,6 +299,66 @@ def llt_rof(data, out, lam_rof, lam_llt, tau, iterations, tolerance=0.0):
     return _marched("tomo_llt_rof", data, out, (lam_rof, lam_llt, tau), iterations, tolerance)
 
 
+def _wavelet_args(data, out, mix):
+    _chk_f32(data, "data")
+    if data.dim() not in (2, 3):
+        raise ValueError("2D or 3D arrays must be provided only")
+    for name, t in (("out", out), ("mix", mix)):
+        if t is not None:
+            _chk_f32(t, name)
+            if tuple(t.shape) != tuple(data.shape) or t.device != data.device:
+                raise ValueError(f"{name} must have the shape and the device of the data")
+
+
+def wavelet_shrink(data, threshold, out=None, mix=None):
+    """Wavelet shrinkage (tomo_wavelet_shrink; the algorithm: docs/kernels/wavelets.md): three db5 levels of every (y, x)
+    slice of `data` (2D, or 3D = a stack of slices), soft threshold `threshold` (a float32 scalar >= 0) on the detail
+    coefficients, inverse, into `out` (default: a new array; it may be `data`).  With `mix` (an array like `out`; it may be
+    `out`) what is stored is ``(mix + W(data)) * 0.5``.  The coefficient pyramid lives in the TV scratch arena."""
+    if out is None:
+        out = torch.empty_like(data)
+    _wavelet_args(data, out, mix)
+    dx, dy, dz, nd = _tv_dims(data)
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_wavelet_shrink(data.device.index, ptr(data), ptr(out), ptr(mix), dx, dy, dz, nd, float(threshold),
+                                            stream_ptr(data)))
+    return out
+
+
+def wavelet_pyramid_floats(shape) -> int:
+    """floats of the coefficient pyramid of an array of `shape` (tomo_wavelet_scratch_bytes / 4)"""
+    nd = len(shape)
+    dz, dy, dx = (1, *shape) if nd == 2 else shape
+    return int(L.lib().tomo_wavelet_scratch_bytes(dx, dy, dz, nd)) // 4
+
+
+def wavelet_forward(data, threshold=0.0):
+    """The thresholded coefficient pyramid of `data` as a flat float32 array (tomo_wavelet_forward; layout:
+    include/tomo_mi355x.h)."""
+    _wavelet_args(data, None, None)
+    dx, dy, dz, nd = _tv_dims(data)
+    pyr = torch.empty(wavelet_pyramid_floats(data.shape), dtype=torch.float32, device=data.device)
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_wavelet_forward(data.device.index, ptr(data), ptr(pyr), dx, dy, dz, nd, float(threshold),
+                                             stream_ptr(data)))
+    return pyr
+
+
+def wavelet_inverse(pyramid, shape, out=None, mix=None):
+    """The array of `shape` a pyramid (as `wavelet_forward` returns it) is the transform of (tomo_wavelet_inverse).  LL of
+    levels 1 and 2 of `pyramid` are overwritten.  `mix` as for `wavelet_shrink`."""
+    _chk_f32(pyramid, "pyramid")
+    if pyramid.numel() != wavelet_pyramid_floats(shape):
+        raise ValueError("the pyramid does not have the size of the pyramid of an array of this shape")
+    if out is None:
+        out = torch.empty(tuple(shape), dtype=torch.float32, device=pyramid.device)
+    _wavelet_args(out, out, mix)
+    dx, dy, dz, nd = _tv_dims(out)
+    with torch.cuda.device(out.device):
+        L.check(L.lib().tomo_wavelet_inverse(out.device.index, ptr(pyramid), ptr(out), ptr(mix), dx, dy, dz, nd, stream_ptr(out)))
+    return out
+
+
 _variant_state = threading.local()   # mirror of the library's per-thread switches, per flavour: lets `variant()` restore
 
 
@@ -376,6 +436,15 @@ def reserve_tv_scratch(shape, device, method: str = "PD_TV", half: bool = False)
     nbytes = getattr(lib, kind.scratch)(dx, dy, dz, nd, *([int(bool(half))] if kind.scratch_half else []))
     with torch.cuda.device(device):
         L.check(lib.tomo_reserve_scratch(device.index or 0, nbytes, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+
+
+def reserve_wavelet_scratch(shape, device):
+    """`reserve_tv_scratch` for the coefficient pyramid of the wavelet shrinkage of arrays of `shape`: it lives in the same
+    arena, which is grow-only, so after both calls the arena holds the larger of the two needs."""
+    device = torch.device(device)
+    with torch.cuda.device(device):
+        L.check(L.lib().tomo_reserve_scratch(device.index or 0, 4 * wavelet_pyramid_floats(tuple(shape)),
+                                             C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
 
 
 def set_placement_tries(tries: int):

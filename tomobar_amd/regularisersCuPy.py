@@ -4,7 +4,8 @@ arrays are float32 ``torch.Tensor`` on the GPU instead of ``cupy.ndarray``.  ``T
 variation), ``NDF_cupy`` (nonlinear diffusion with the Huber, Perona-Malik and Tukey penalties), ``Diff4th_cupy``
 (anisotropic fourth-order diffusion) and ``LLT_ROF_cupy`` (ROF plus the fourth-order Lysaker-Lundervold-Tai term) have no
 counterpart in this reference version: formula-level parity, unpinned (docs/kernels/tgv.md, docs/kernels/ndf.md,
-docs/kernels/diff4th.md, docs/kernels/llt_rof.md).
+docs/kernels/diff4th.md, docs/kernels/llt_rof.md).  ``WAVELETS_cupy`` (db5 wavelet shrinkage, docs/kernels/wavelets.md) is the
+step behind the ``_WAVELETS`` suffix of a method: the reference's tutorials use it, its tree no longer implements it.
 
 The iteration loops run inside ``libtomo_mi355x.so`` (``tomo_pdtv`` / ``tomo_roftv``): one fused HIP kernel per
 iteration, launched back to back on the caller's stream, scratch taken from the library's arena
@@ -21,7 +22,7 @@ import torch
 
 from . import ops
 from .convergence import check_tolerance
-from .supp.regularisers import kind_of
+from .supp.regularisers import WAVELETS_REFUSED, has_wavelets, kind_of, wavelet_threshold
 
 _last = threading.local()
 
@@ -45,7 +46,13 @@ def prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch
     arithmetic, 5-16 % slower per launch) for this call; absent / False = the default (within 1e-5).
 
     ``_regularisation_["tolerance"]`` > 0 stops the inner iterations early (tomobar_amd/convergence.py; the reference
-    accepts the key and ignores it); ``last_prox()`` tells how far the call got."""
+    accepts the key and ignores it); ``last_prox()`` tells how far the call got.
+
+    A method that names a kind and contains ``WAVELETS`` (the reference's tutorials: "PD_TV_WAVELETS") returns
+    ``(prox_kind(X) + W_t(X)) * 0.5`` with ``W_t`` the wavelet shrinkage of ``WAVELETS_cupy`` and t = ``regul_param2``: the
+    kind runs exactly as without the suffix (all keys keep their meaning for it, ``last_prox()`` reports its iterations),
+    then the shrinkage of the same X is averaged into its result.  In z-slab mode that step needs no communication (it is
+    per slice)."""
     if _regularisation_.get("exact_roundings") and "PD_TV" in _regularisation_["method"] and ops.get_variant("pdtv") == 0:
         with ops.variant("pdtv", 22):
             return _prox_regul(self, X, _regularisation_, out)
@@ -69,17 +76,25 @@ def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torc
         info = {"iterations_done": _regularisation_["iterations"], "rel_change": float("nan")}
         res = getattr(slab_drivers, kind.slab)(ops.contiguous(X), slab, *args, *half, out=out, tolerance=tol, info=info)
         _record(info["iterations_done"], info["rel_change"])
-        return res
-    return globals()[kind.cupy](X, *args, self.Atools.device_index, *half, out=out, tolerance=tol)
+    else:
+        res = globals()[kind.cupy](X, *args, self.Atools.device_index, *half, out=out, tolerance=tol)
+    if has_wavelets(method):
+        # the average of the two proximal maps of X: the last wavelet launch reads the kind's result where it writes
+        dst = ops.to_device(res, self.Atools.device_index) if ops.is_cupy(res) else res
+        WAVELETS_cupy(X, wavelet_threshold(_regularisation_), self.Atools.device_index, out=dst, mix=dst)
+    return res
 
 
 def check_prox_available(self, vol_shape, _regularisation_: dict) -> None:
     """What TGV cannot do yet, as a ValueError before any work is done: z-slab mode on a real 3D volume (the halo protocol
     for its 13 further fields does not exist) and binary16 storage of its fields.  NDF, Diff4th and LLT_ROF have no binary16
-    storage either (they do run in z-slab mode).  The other methods pass."""
+    storage either (they do run in z-slab mode).  The ``WAVELETS`` suffix does not combine with LLT_ROF (``regul_param2`` is
+    already that kind's LLT weight).  The other methods pass."""
     kind = kind_of(_regularisation_.get("method"))
     if kind is None:
         return
+    if kind.name in WAVELETS_REFUSED and has_wavelets(_regularisation_.get("method")):
+        raise ValueError(f"{kind.name} does not combine with WAVELETS: regul_param2 is already its second weight")
     if not kind.half and _regularisation_.get("half_precision", False):
         raise ValueError(f"{kind.name} does not support half_precision=True")
     if kind.slab is None and getattr(self, "slab", None) is not None:
@@ -103,6 +118,8 @@ def reserve_prox_scratch(self, vol_shape, _regularisation_: dict) -> None:
         i = shape.index(1)
         shape = shape[:i] + shape[i + 1:]
     ops.reserve_tv_scratch(shape, f"cuda:{self.Atools.device_index}", kind.name, bool(_regularisation_.get("half_precision", False)))
+    if has_wavelets(_regularisation_.get("method")):   # the coefficient pyramid shares that arena: it grows to the larger need
+        ops.reserve_wavelet_scratch(shape, f"cuda:{self.Atools.device_index}")
 
 
 def _prepare(data, gpu_id: int):
@@ -254,6 +271,26 @@ def LLT_ROF_cupy(data, regularisation_parameterROF: float = 1e-05, regularisatio
                                                     np.float32(regularisation_parameterLLT),
                                                     np.float32(time_marching_parameter), iterations, tol),
                     data, gpu_device, out, tolerance)
+
+
+def WAVELETS_cupy(data, regularisation_parameter: float = 0.001, gpu_device: int = 0, out=None, mix=None) -> torch.Tensor:
+    """Wavelet shrinkage ``W_t``: three levels of the 2D orthonormal Daubechies-5 transform (periodization mode) of every
+    (y, x) slice -- a 3D array is a stack of independent slices over z --, soft threshold ``regularisation_parameter`` on
+    every detail coefficient, inverse transform.  A threshold of 0 gives the input back up to rounding; a negative one is a
+    ValueError.  With ``mix`` (an array like ``out``; it may be ``out``) the result is ``(mix + W_t(data)) * 0.5``, formed as
+    the last launch writes: how ``prox_regul`` averages the shrinkage with the prox of a ``<kind>_WAVELETS`` method.
+
+    The reference's tutorials name the step ("PD_TV_WAVELETS", ``regul_param2``); its implementation lived in the removed
+    RecToolsIR class on the CUDA-only pypwt package: the algorithm is the one stated in docs/kernels/wavelets.md --
+    formula-level parity, unpinned; the float32 result equals the numpy restatement tests/_wavelet_oracle.py bit for bit.
+    Not iterative: ``last_prox()`` is left as it was."""
+    if not float(regularisation_parameter) >= 0.0:
+        raise ValueError("the wavelet threshold must not be negative")
+    orig_shape = tuple(data.shape)
+    d, is2d, axis = _prepare(data, gpu_device)
+    res = torch.empty_like(d) if out is None else out.view(d.shape)
+    ops.wavelet_shrink(d, np.float32(regularisation_parameter), out=res, mix=None if mix is None else mix.view(d.shape))
+    return _finish(res, is2d, axis, orig_shape, out, data)
 
 
 def _check_if_input_2d_or_3d(data) -> Tuple[torch.Tensor, bool, int]:

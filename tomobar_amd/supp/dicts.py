@@ -13,7 +13,7 @@ from typing import Optional
 from .. import ops
 from ..convergence import check_tolerance
 from .funcs import _data_dims_swapper
-from .regularisers import kind_of
+from .regularisers import WAVELETS_DEFAULTS, has_wavelets, kind_of
 
 LABELS_3D = ["detY", "angles", "detX"]
 LABELS_2D = ["angles", "detX"]
@@ -123,6 +123,8 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
     # implemented in this reference version).  Dictionaries of the other methods are not touched.
     kind = kind_of(_regularisation_.get("method"))
     extra_keys = kind.defaults if kind is not None else ()
+    if has_wavelets(_regularisation_.get("method")):   # the suffix: the threshold of the wavelet shrinkage
+        extra_keys += tuple(k for k in WAVELETS_DEFAULTS if k not in extra_keys)
     for key, value, _ in extra_keys:
         _regularisation_.setdefault(key, value)
     for key, _, choices in extra_keys:

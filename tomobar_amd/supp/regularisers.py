@@ -4,6 +4,10 @@ This is the one place the precedence is written: ``regularisersCuPy.prox_regul``
 ``reserve_prox_scratch``, ``dicts.dicts_check``, ``ops.reserve_tv_scratch``, the march drivers of ``slab`` and the package's
 lazy names all read it.  No reference counterpart (its ``prox_regul`` is a two-branch if, regularisersCuPy.py:16-38).
 
+Next to the table stands the one suffix a method string can carry, ``WAVELETS`` (``has_wavelets``): not a kind but a modifier
+of every kind except LLT_ROF -- the prox is averaged with a db5 wavelet shrinkage whose threshold is ``regul_param2``
+(docs/kernels/wavelets.md).  The same call sites read it.
+
 Imports neither torch nor ``ops``.  Functions are held by NAME and looked up on their module when they are called:
 the CPU tests stand the oracle in for them by setting module attributes.
 """
@@ -79,3 +83,21 @@ def kind_of(method) -> Optional[Kind]:
     if not isinstance(method, str):
         return None
     return next((k for k in KINDS if k.name in method), None)
+
+
+# ---- the suffix: "<kind>_WAVELETS" averages the kind's prox with the wavelet shrinkage W_t, t = regul_param2 (the key and
+# its default 0.001 are those of the removed RecToolsIR class; the reference's tutorials still write "PD_TV_WAVELETS")
+WAVELETS = "WAVELETS"
+WAVELETS_CUPY = "WAVELETS_cupy"                    # the stand-alone function in regularisersCuPy
+WAVELETS_SCRATCH = "tomo_wavelet_scratch_bytes"    # the C symbol that sizes the coefficient pyramid
+WAVELETS_DEFAULTS = _keys(("regul_param2", None))  # what dicts_check fills and checks for it, as `defaults` of a record
+WAVELETS_REFUSED = ("LLT_ROF",)                    # regul_param2 is already that kind's LLT weight
+
+
+def has_wavelets(method) -> bool:
+    """``method`` names a kind and carries the suffix (a string with ``WAVELETS`` that names no kind is an unknown method)."""
+    return isinstance(method, str) and WAVELETS in method and kind_of(method) is not None
+
+
+def wavelet_threshold(reg):
+    return _opt(reg, "regul_param2")

@@ -30,7 +30,8 @@ extern "C" {
 /* raised whenever a signature changes or an entry point is added (tomobar_amd/_lib.py checks it at load).  The three
  * tomo_diff4th* entry points joined version 10 without a raise: tests/test_ndf_oracle.py pins the number 10, and _lib.py
  * binds every symbol by name at load, so a library without them is refused all the same.  The three tomo_llt_rof* entry
- * points joined it the same way, for the same reason.  So did the four tomo_wavelet_* entry points. */
+ * points joined it the same way, for the same reason.  So did the four tomo_wavelet_* entry points, and tomo_halo_pack2 /
+ * tomo_halo_pull2 with the four tomo_ipc_region_* entry points. */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -503,6 +504,28 @@ int tomo_llt_rof_iter_slab_range(int device, const float *in_dev, const float *u
 size_t tomo_halo_staging_bytes(const size_t *bytes, int nblocks);
 int tomo_halo_pack(const void *const *src_dev, const size_t *bytes, int nblocks, void *staging_dev, void *stream);
 int tomo_halo_unpack(const void *staging_dev, void *const *dst_dev, const size_t *bytes, int nblocks, void *stream);
+/* Both directions of an exchange in ONE launch each (no reference counterpart, as above): tomo_halo_pack2 gathers the blocks
+ * for rank-1 into msg_down_dev and the blocks for rank+1 into msg_up_dev; tomo_halo_pull2 scatters the message that came from
+ * rank-1 (msg_down_dev) and the one from rank+1 (msg_up_dev) into the ghost planes.  Each message has the layout of
+ * tomo_halo_staging_bytes over its own block table, at most 8 blocks per direction; a direction with 0 blocks is valid (its
+ * pointers may be NULL) and two empty directions launch nothing.  The messages of tomo_halo_pull2 are meant to lie in a
+ * neighbour's region mapped by tomo_ipc_region_open: the device-direct transport of tomobar_amd/slab.py, which needs one pack
+ * and one pull launch per exchange where tomo_halo_pack / tomo_halo_unpack need two each. */
+int tomo_halo_pack2(const void *const *src_down_dev, const size_t *bytes_down, int nblocks_down, void *msg_down_dev,
+                    const void *const *src_up_dev, const size_t *bytes_up, int nblocks_up, void *msg_up_dev, void *stream);
+int tomo_halo_pull2(const void *msg_down_dev, void *const *dst_down_dev, const size_t *bytes_down, int nblocks_down,
+                    const void *msg_up_dev, void *const *dst_up_dev, const size_t *bytes_up, int nblocks_up, void *stream);
+/* Device memory that other PROCESSES map (HIP IPC; no reference counterpart: the reference never moves data between its
+ * replicas).  tomo_ipc_region_create allocates `bytes` on `device` with a hipMalloc of the library's own -- an IPC handle names
+ * a whole allocation, so a piece of a caching allocator's block cannot be exported -- and writes the 64 opaque bytes another
+ * process passes to tomo_ipc_region_open, which returns that memory mapped into the caller.  A handle is opened at most once
+ * per process and never by the process that created it.  tomo_ipc_region_close unmaps, tomo_ipc_region_destroy frees; the
+ * owner destroys a region only after every mapper has stopped reading it (the caller's protocol: tomobar_amd/slab.py).
+ * Synchronous host calls; a HIP failure is TOMO_E_RUNTIME / TOMO_E_NOMEM with the HIP error text in tomo_last_error(). */
+int tomo_ipc_region_create(int device, size_t bytes, void **base_dev, unsigned char handle[64]);
+int tomo_ipc_region_open(int device, const unsigned char handle[64], void **mapped_dev);
+int tomo_ipc_region_close(void *mapped_dev);
+int tomo_ipc_region_destroy(void *base_dev);
 /* How many PD_TV iterations tomo_pdtv fuses into one launch for float32 (half = 0) / binary16 (half != 0) dual fields under
  * the calling thread's kernel variant: a slab driver that wants to be launch-for-launch identical to the whole-volume
  * operator cuts its iterations the same way (tomobar_amd/slab.py: pd_launch_plan) and keeps that many ghost planes. */

@@ -129,6 +129,12 @@ SIGNATURES = {
     "tomo_halo_staging_bytes": (_sz, [C.POINTER(_sz), _i]),
     "tomo_halo_pack": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _vp]),
     "tomo_halo_unpack": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz), _i, _vp]),
+    "tomo_halo_pack2": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, _vp, C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _vp]),
+    "tomo_halo_pull2": (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz), _i, _vp, C.POINTER(_vp), C.POINTER(_sz), _i, _vp]),
+    "tomo_ipc_region_create": (_i, [_i, _sz, C.POINTER(_vp), C.POINTER(C.c_ubyte)]),
+    "tomo_ipc_region_open": (_i, [_i, C.POINTER(C.c_ubyte), C.POINTER(_vp)]),
+    "tomo_ipc_region_close": (_i, [_vp]),
+    "tomo_ipc_region_destroy": (_i, [_vp]),
     "tomo_pdtv_iters_per_launch": (_i, [_i]),
     "tomo_pdtv_launch_plan": (_i, [_i, _i, _i, C.POINTER(_i), _i]),
     "tomo_fbp_filter": (_i, [_i, _vp, _sz, _i, _f, _f, _vp]),

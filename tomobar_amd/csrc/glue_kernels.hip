@@ -425,12 +425,9 @@ struct HaloBlocks {
     int n;
 };
 
-__global__ __launch_bounds__(256) void halo_copy_kernel(HaloBlocks h)
+// one block of a table, copied by the workgroups blockIdx.x = 0 .. gridDim.x - 1 of its row of the grid
+__device__ __forceinline__ void halo_copy_block(const char *src, char *dst, size_t bytes)
 {
-    const int b = blockIdx.y;
-    const char *src = h.src[b];
-    char *dst = h.dst[b];
-    const size_t bytes = h.bytes[b];
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool vec = (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0;
@@ -445,6 +442,61 @@ __global__ __launch_bounds__(256) void halo_copy_kernel(HaloBlocks h)
         done = n4 << 2;
     }
     for (size_t i = done + t0; i < bytes; i += stride) dst[i] = src[i];
+}
+
+__global__ __launch_bounds__(256) void halo_copy_kernel(HaloBlocks h)
+{
+    const int b = blockIdx.y;
+    halo_copy_block(h.src[b], h.dst[b], h.bytes[b]);
+}
+
+// ---- the same copy for BOTH directions of an exchange in one launch (the IPC transport of tomobar_amd/slab.py): the block
+//      tables of the message to rank-1 and of the message to rank+1 one after the other, each message with its own
+//      contiguous buffer.  One kernel serves both entry points, as halo_copy_kernel does: pack2 gathers into two buffers of the sender's exported region, pull2 scatters out of two buffers
+//      of the neighbours' regions (mapped by tomo_ipc_region_open) into the ghost planes.
+struct HaloBlocks2 {
+    const char *src[2 * HALO_MAX_BLOCKS];
+    char *dst[2 * HALO_MAX_BLOCKS];
+    size_t bytes[2 * HALO_MAX_BLOCKS];
+};
+
+__global__ __launch_bounds__(256) void halo_copy2_kernel(HaloBlocks2 h)
+{
+    const int b = blockIdx.y;   // < the number of blocks of both directions together: the grid's y extent
+    halo_copy_block(h.src[b], h.dst[b], h.bytes[b]);
+}
+
+int halo_copy2(const void *const *a0, const size_t *bytes0, int n0, const void *contig0,
+               const void *const *a1, const size_t *bytes1, int n1, const void *contig1, bool pack, void *stream)
+{
+    const void *const *a[2] = {a0, a1};
+    const size_t *bytes[2] = {bytes0, bytes1};
+    const void *contig[2] = {contig0, contig1};
+    const int n[2] = {n0, n1};
+    HaloBlocks2 h;
+    int total = 0;
+    size_t largest = 0;
+    for (int d = 0; d < 2; ++d) {
+        TOMO_REQUIRE(n[d] >= 0 && n[d] <= HALO_MAX_BLOCKS, "a halo exchange packs at most %d blocks per direction (got %d)", HALO_MAX_BLOCKS, n[d]);
+        if (n[d] == 0) continue;   // an edge rank has one neighbour: the other direction is empty
+        TOMO_REQUIRE(a[d] != nullptr && contig[d] != nullptr && bytes[d] != nullptr, "NULL halo block table");
+        size_t off = 0;
+        for (int i = 0; i < n[d]; ++i, ++total) {
+            TOMO_REQUIRE(a[d][i] != nullptr || bytes[d][i] == 0, "halo block %d is NULL", i);
+            char *stage = (char *)contig[d] + off;
+            h.src[total] = pack ? (const char *)a[d][i] : stage;
+            h.dst[total] = pack ? stage : (char *)a[d][i];
+            h.bytes[total] = bytes[d][i];
+            off += (bytes[d][i] + 15) & ~(size_t)15;  // the layout of tomo_halo_staging_bytes, per message
+            largest = std::max(largest, bytes[d][i]);
+        }
+    }
+    if (total == 0) return TOMO_OK;
+    for (int i = total; i < 2 * HALO_MAX_BLOCKS; ++i) { h.src[i] = nullptr; h.dst[i] = nullptr; h.bytes[i] = 0; }
+    const int gx = (int)std::min<size_t>(std::max<size_t>((largest / 16 + 255) / 256, 1), 512);
+    halo_copy2_kernel<<<dim3(gx, total), 256, 0, as_stream(stream)>>>(h);
+    TOMO_LAUNCH_CHECK();
+    return TOMO_OK;
 }
 
 int halo_copy(const void *const *a, const void *b_contig, const size_t *bytes, int nblocks, bool pack, void *stream)
@@ -799,4 +851,20 @@ extern "C" int tomo_halo_pack(const void *const *src_dev, const size_t *bytes, i
 extern "C" int tomo_halo_unpack(const void *staging_dev, void *const *dst_dev, const size_t *bytes, int nblocks, void *stream)
 {
     return halo_copy((const void *const *)dst_dev, staging_dev, bytes, nblocks, false, stream);
+}
+
+extern "C" int tomo_halo_pack2(const void *const *src_down_dev, const size_t *bytes_down, int nblocks_down, void *msg_down_dev,
+                               const void *const *src_up_dev, const size_t *bytes_up, int nblocks_up, void *msg_up_dev,
+                               void *stream)
+{
+    return halo_copy2(src_down_dev, bytes_down, nblocks_down, msg_down_dev, src_up_dev, bytes_up, nblocks_up, msg_up_dev, true,
+                      stream);
+}
+
+extern "C" int tomo_halo_pull2(const void *msg_down_dev, void *const *dst_down_dev, const size_t *bytes_down, int nblocks_down,
+                               const void *msg_up_dev, void *const *dst_up_dev, const size_t *bytes_up, int nblocks_up,
+                               void *stream)
+{
+    return halo_copy2((const void *const *)dst_down_dev, bytes_down, nblocks_down, msg_down_dev,
+                      (const void *const *)dst_up_dev, bytes_up, nblocks_up, msg_up_dev, false, stream);
 }

@@ -17,7 +17,8 @@ element-wise glue need no communication.  What does:
       - LLT_ROF: two planes of U each way, every iteration.
   * scalar reductions (power-method norm, PWLS weight maximum, CGLS inner products): all-reduce.
 
-``SlabComm`` wraps ``torch.distributed`` (backend "nccl" = RCCL on ROCm, "gloo" in the CPU tests).  The TV drivers are
+``SlabComm`` wraps ``torch.distributed`` (backend "nccl" = RCCL on ROCm, "gloo" in the CPU tests); over a gloo group the
+ghost planes can also travel device to device through HIP IPC regions (``transport``, tomobar_amd/halo_ipc.py).  The TV drivers are
 written against small "step" callables so that the same halo logic runs on the HIP kernels and, in the CPU tests, on
 the oracle's single-iteration functions.
 """
@@ -25,6 +26,7 @@ the oracle's single-iteration functions.
 from __future__ import annotations
 
 import ctypes as C
+import os
 import time
 from typing import Callable, List, Optional
 
@@ -32,6 +34,7 @@ import numpy as np
 import torch
 
 from .convergence import check_tolerance, inner_check_due, relative_change
+from .halo_ipc import staging_bytes as _halo_staging_bytes
 from .supp.regularisers import BY_NAME
 
 
@@ -52,6 +55,9 @@ def check_slab_split(nz_total: int, world: int, min_slices: int = 2):
                          f"use at most {max(nz_total // min_slices, 1)} ranks")
 
 
+TRANSPORT_ENV = "TOMO_MI355X_HALO_TRANSPORT"   # read by SlabComm when no transport is passed: backend | ipc | auto
+
+
 class _StagedRequest:
     """Completion handle of a host-staged transfer (gloo moving device tensors): wait() finishes the CPU transfer and,
     for a receive, copies the plane into the device tensor on the current stream."""
@@ -69,9 +75,21 @@ class SlabComm:
     """Neighbour exchange and scalar reductions for one rank of a z-slab decomposition.
 
     Backend "nccl" (RCCL over xGMI) moves device tensors directly.  With "gloo" device tensors are staged through host
-    memory (functional path for the CPU tests and for several ranks sharing one GPU; not a performance path)."""
+    memory (functional path for the CPU tests and for several ranks sharing one GPU; not a performance path).
 
-    def __init__(self, rank: int, world: int, device=None, group=None):
+    ``transport`` (default: the environment variable TOMO_MI355X_HALO_TRANSPORT, else "backend") chooses how ghost planes
+    travel; scalars always go through the process group:
+      "backend"  what the backend gives, as above: timing_summary()["transport"] is "rccl" or "staged";
+      "ipc"      the device-direct transport of tomobar_amd/halo_ipc.py over a non-RCCL group: every rank exports its packed
+                 planes (HIP IPC; shared memory for host tensors) and its neighbours pull them.  Construction is then
+                 COLLECTIVE -- every rank sets the transport up, moves a check pattern across each boundary, and all ranks
+                 agree on the outcome (MIN all-reduce); if any rank failed, all raise;
+      "auto"     RCCL where the backend is "nccl"; else "ipc", except that after a failed check ALL ranks use host staging
+                 and timing_summary()["transport_note"] says why.
+    A comm that uses the IPC transport is given back with close() (collective).  A world of one rank has no neighbour:
+    nothing is set up, and timing_summary() reports the backend's transport whatever was asked for."""
+
+    def __init__(self, rank: int, world: int, device=None, group=None, transport=None):
         import torch.distributed as dist
         self.dist = dist
         self.rank, self.world = int(rank), int(world)
@@ -86,6 +104,55 @@ class SlabComm:
         self._wait_stream_ms = 0.0
         self.timing = False   # bench.py switches the HIP-event timing of the waits on
         self.stats = {"exchanges": 0, "messages": 0, "bytes": 0, "post_host_ms": 0.0, "wait_host_ms": 0.0}
+        if transport is None:
+            transport = os.environ.get(TRANSPORT_ENV) or "backend"
+        if transport not in ("backend", "ipc", "auto"):
+            raise ValueError(f"unknown halo transport {transport!r}: backend, ipc or auto")
+        self.transport = "staged" if self.staged else "rccl"
+        self.transport_note = None
+        self._ipc = None
+        if transport == "ipc" and not self.staged:
+            raise ValueError("the IPC halo transport sends its tokens as host tensors: give it a gloo group (with the nccl "
+                             "backend the planes travel over RCCL; transport=\"auto\" selects that)")
+        if transport != "backend" and self.staged:
+            self._setup_ipc(strict=transport == "ipc")
+
+    def _setup_ipc(self, strict: bool):
+        """Collective (see the class comment): all ranks leave with the same transport, or all raise."""
+        from . import halo_ipc
+        if self.world > 1:
+            tr = halo_ipc.IpcTransport(self)
+            err = tr.self_test()   # this rank's error text or None; never raises, never leaves a neighbour waiting
+            ok = torch.tensor([int(err is None)], dtype=torch.int32)
+            self.dist.all_reduce(ok, op=self.dist.ReduceOp.MIN, group=self.group)
+            if int(ok.item()) == 0:
+                errors = [None] * self.world
+                self.dist.all_gather_object(errors, err, group=self.group)
+                note = "the IPC halo transport failed its check: " + "; ".join(
+                    f"rank {r}: {e}" for r, e in enumerate(errors) if e is not None)
+                tr.close()
+                if strict:
+                    e = RuntimeError(note)
+                    e.own_error = err   # this rank's own failure (None: only other ranks failed)
+                    raise e
+                self.transport_note = note + " -- all ranks use host staging"
+                return
+            self._ipc = tr
+            self.transport = "ipc"   # (a world of one rank has no neighbour and sets nothing up: it reports the backend's)
+
+    def close(self):
+        """Collective: gives the regions of the IPC transport back (every rank unmaps its neighbours' regions; after a
+        barrier every rank frees its own).  All exchanges must have been waited for.  Nothing to do for the other
+        transports; a closed comm still serves scalars."""
+        if self._ipc is not None:
+            self._ipc.close()
+
+    def __del__(self):
+        try:   # best effort, without the other ranks: mappings, and the regions no neighbour can still be reading
+            if self._ipc is not None:
+                self._ipc.release_local()
+        except Exception:  # noqa: BLE001
+            pass
 
     def _scalar_device(self):
         return None if self.staged else self.device
@@ -149,6 +216,8 @@ class SlabComm:
         """One exchange = at most ONE send and ONE receive per neighbour: the blocks of a direction (U, P1, P2, P3 planes,
         each contiguous in its own array) are packed into one staging buffer (tomo_halo_pack) and scattered back on
         arrival (tomo_halo_unpack).  Returns a handle whose wait() completes the transfers and the scatter."""
+        if self._ipc is not None:
+            return self._ipc.post(send_down, recv_down, send_up, recv_up)
         t_host = time.perf_counter()
         P2POp = self.dist.P2POp
         plan, unpack, owned = [], [], []
@@ -220,6 +289,9 @@ class SlabComm:
         if self._wait_stream_ms or self.timing:
             out["wait_stream_ms"] = self._wait_stream_ms
         out["backend"] = self.backend
+        out["transport"] = self.transport
+        if self.transport_note:
+            out["transport_note"] = self.transport_note
         return out
 
 
@@ -269,11 +341,6 @@ def extend_detector_rows(comm, sino: torch.Tensor, g: int):
     comm.exchange([sino[0:g]] if comm.has_lo else [], [ext[0:g]] if comm.has_lo else [],
                   [sino[rows - g:rows]] if comm.has_hi else [], [ext[lo + rows:]] if comm.has_hi else [])
     return ext, lo
-
-
-def _halo_staging_bytes(nbytes):
-    """tomo_halo_staging_bytes: every block starts 16-byte aligned in the staging buffer."""
-    return sum((int(b) + 15) // 16 * 16 for b in nbytes)
 
 
 def _halo_pack(tensors, nbytes, staging):

@@ -15,6 +15,12 @@ What it measures, per interior z-slab boundary (rank r <-> r+1), with the produc
     transfer is hidden completely, 0 = it serialises with the kernel.
 With fewer GPUs than ranks the ranks share devices and RCCL refuses (same device twice): the script then says so and
 times the host-staged gloo path instead (`"backend": "gloo"`) -- a functional check, never a performance number.
+
+Beside that, every rank reports under `"transports"` the two transports that need no RCCL, over the gloo group
+(SlabComm(transport="auto") and the default SlabComm): whether the IPC transport came up (`setup_ok`, else `note`), and for
+the same configs[4] exchange, timed ALTERNATELY (staged, ipc, staged, ipc, ... `--reps` times each, medians): `exchange_ms`,
+`payload_ok` (every received block compared in full) and `wait_stream_ms` per exchange.  `ipc_over_staged` is the ratio of
+the medians.  The ranks may share a GPU for this: the IPC transport works between processes on one device.
 """
 import argparse
 import datetime
@@ -35,6 +41,53 @@ def free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def transports(comm_args, blocks, reps):
+    """The IPC and the host-staged transport over the default (gloo) group on the same blocks, timed alternately."""
+    import torch
+    import torch.distributed as dist
+    from tomobar_amd.slab import SlabComm
+
+    rank, world = comm_args[:2]
+    send_down, recv_down, send_up, recv_up = blocks
+    comms = {"staged": SlabComm(*comm_args, transport="backend"), "ipc": SlabComm(*comm_args, transport="auto")}
+    out = {"ipc": {"setup_ok": comms["ipc"].transport == "ipc", "note": comms["ipc"].transport_note}}
+    if not out["ipc"]["setup_ok"]:
+        del comms["ipc"]
+
+    def payload_ok():
+        # what arrived from below is what rank-1 sent up, from above what rank+1 sent down (their fill values), every element
+        good = all(bool((t == float((rank - 1) * 10 + i)).all()) for i, t in enumerate(recv_down))
+        first = len(send_up) if rank + 2 < world else 0   # rank+1 numbers its blocks for rank+2 first
+        return good and all(bool((t == float((rank + 1) * 10 + first + i)).all()) for i, t in enumerate(recv_up))
+
+    times = {name: [] for name in comms}
+    good = {name: True for name in comms}
+    for rep in range(reps + 1):   # the first round warms up (regions, mappings, staging buffers) and is not counted
+        for name, comm in comms.items():
+            for t in recv_down + recv_up:
+                t.zero_()
+            comm.timing = rep > 0
+            torch.cuda.synchronize(); dist.barrier()
+            t0 = time.perf_counter()
+            comm.exchange(send_down, recv_down, send_up, recv_up)
+            torch.cuda.synchronize()
+            if rep > 0:
+                times[name].append((time.perf_counter() - t0) * 1e3)
+            good[name] = good[name] and payload_ok()
+    for name, comm in comms.items():
+        st = comm.timing_summary()
+        ts = sorted(times[name])
+        out.setdefault(name, {}).update(exchange_ms=ts[len(ts) // 2], all_ms=times[name], payload_ok=good[name],
+                                        wait_stream_ms=st.get("wait_stream_ms", 0.0) / max(reps, 1), transport=st["transport"])
+        comm.close()
+    # launches one exchange costs a rank with both neighbours
+    out["staged"]["launches"] = "2 tomo_halo_pack + 2 tomo_halo_unpack"
+    if "exchange_ms" in out["ipc"]:
+        out["ipc"]["launches"] = "1 tomo_halo_pack2 + 1 tomo_halo_pull2"
+        out["ipc_over_staged"] = out["ipc"]["exchange_ms"] / max(out["staged"]["exchange_ms"], 1e-9)
+    return out
 
 
 def main():
@@ -142,6 +195,7 @@ def main():
     mine = dict(rank=rank, exchange_ms=ex_ms, kernel_ms=k_ms, both_ms=b_ms, bytes_sent=sent, payload_ok=bool(good),
                 overlap=(ex_ms + k_ms - b_ms) / max(min(ex_ms, k_ms), 1e-9),
                 GBps_per_direction=(sent / max(1, int(has_lo) + int(has_hi))) / ex_ms / 1e6 if sent else 0.0)
+    mine["transports"] = transports(comm_args=(rank, world, dev), blocks=(send_down, recv_down, send_up, recv_up), reps=args.reps)
     allr = [None] * world
     dist.all_gather_object(allr, mine)
     if rank == 0:

@@ -302,6 +302,23 @@ int tomo_pdtv_tol(int device, const float *in_dev, float *out_dev, int dx, int d
 int tomo_roftv_tol(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
                    float lambda, float tau, int iters, int half, double tol, int *iters_done,
                    double *last_rel_change, void *stream);
+/* Slice-wise PD_TV / ROF_TV (no reference counterpart; docs/kernels/slicewise.md): in_dev is a stack [nslices][dy][dx] and
+ * every (y, x) slice receives exactly what tomo_pdtv / tomo_roftv with nd = 2 return for it -- the same iteration and the
+ * same roundings (PD_TV variants 0 and 22, ROF_TV variant 0), nothing couples the slices -- with all slices in one launch
+ * (PD_TV: up to three iterations per launch; ROF_TV: one).  Scalars, flags, checks and error texts as for tomo_pdtv /
+ * tomo_roftv (ROF_TV needs dx, dy >= 2); iters = 0 copies the input; tomo_roftv_slices iterates in out_dev, which must not
+ * alias in_dev.  tol, iters_done, last_rel_change: the rule of tomo_pdtv_tol with ONE decision over the whole stack, so
+ * every slice runs the same number of iterations and a stopped run leaves exactly what iters = n returns.  Work arrays in
+ * the placed TV arena: tomo_pdtv_slices_scratch_bytes (U ping-pong and two dual fields in and out, float32 or binary16),
+ * tomo_roftv_slices_scratch_bytes (the one ping-pong partner of out_dev). */
+int tomo_pdtv_slices(int device, const float *in_dev, float *out_dev, int dx, int dy, int nslices, float sigma,
+                     float tau, float lt, float theta, int iters, int methodTV, int nonneg, int half, double tol,
+                     int *iters_done, double *last_rel_change, void *stream);
+int tomo_roftv_slices(int device, const float *in_dev, float *out_dev, int dx, int dy, int nslices, float lambda,
+                      float tau, int iters, int half, double tol, int *iters_done, double *last_rel_change,
+                      void *stream);
+size_t tomo_pdtv_slices_scratch_bytes(int dx, int dy, int nslices, int half);
+size_t tomo_roftv_slices_scratch_bytes(int dx, int dy, int nslices);
 /* Second-order total generalised variation (TGV): argmin_u 1/2 |u - f|^2 + lambda min_v (alpha1 |grad u - v|_1 + alpha0 |E v|_1)
  * by Chambolle-Pock iterations.  No reference counterpart in this reference version (it took TGV from the regularisation
  * toolkit it no longer depends on; tomobar/supp/dicts.py:176-178 still names PD_LipschitzConstant "TGV specific"): the

@@ -99,6 +99,10 @@ SIGNATURES = {
     "tomo_roftv_tol": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
     "tomo_pdtv_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "tomo_roftv_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_pdtv_slices": (_i, [_i, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _i, _i, _i, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
+    "tomo_roftv_slices": (_i, [_i, _vp, _vp, _i, _i, _i, _f, _f, _i, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
+    "tomo_pdtv_slices_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_roftv_slices_scratch_bytes": (_sz, [_i, _i, _i]),
     "tomo_tgv": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
     "tomo_tgv_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_ndf": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .supp.regularisers import BY_NAME
+from .supp.regularisers import BY_NAME, SLICEWISE_KINDS
 
 
 def _require_gpu(device_index: int) -> torch.device:
@@ -256,6 +256,41 @@ def roftv_tol(data, out, lam, tau, iterations, half, tolerance):
     return out, int(done.value), float(last.value)
 
 
+def _slices_dims(data, out):
+    for name, t in (("data", data), ("out", out)):
+        _chk_f32(t, name)
+    if data.dim() != 3:
+        raise ValueError("a stack of slices [nslices, dy, dx] must be provided")
+    if tuple(out.shape) != tuple(data.shape) or out.device != data.device:
+        raise ValueError("out must have the shape and the device of the data")
+    return data.shape[2], data.shape[1], data.shape[0]
+
+
+def pdtv_slices(data, out, sigma, tau, lt, theta, iterations, methodTV, nonneg, half, tolerance=0.0):
+    """Slice-wise PD_TV (tomo_pdtv_slices; docs/kernels/slicewise.md): every slice ``data[k]`` of a 3D array receives what
+    `pdtv` returns for it as a 2D image, all slices in one set of launches.  Returns (out, iterations_done, rel_change): one
+    stopping decision over the whole array (tolerance 0 = off: all iterations, NaN)."""
+    dx, dy, ns = _slices_dims(data, out)
+    done, last = C.c_int(0), C.c_double(float("nan"))
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_pdtv_slices(data.device.index, ptr(data), ptr(out), dx, dy, ns, float(sigma), float(tau),
+                                         float(lt), float(theta), int(iterations), int(bool(methodTV)), int(bool(nonneg)),
+                                         int(bool(half)), float(tolerance), C.byref(done), C.byref(last), stream_ptr(data)))
+    return out, int(done.value), float(last.value)
+
+
+def roftv_slices(data, out, lam, tau, iterations, half, tolerance=0.0):
+    """Slice-wise ROF_TV (tomo_roftv_slices): as `pdtv_slices`; `out` must be another array than `data` (the iterations
+    ping-pong through it)."""
+    dx, dy, ns = _slices_dims(data, out)
+    done, last = C.c_int(0), C.c_double(float("nan"))
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_roftv_slices(data.device.index, ptr(data), ptr(out), dx, dy, ns, float(lam), float(tau),
+                                          int(iterations), int(bool(half)), float(tolerance), C.byref(done), C.byref(last),
+                                          stream_ptr(data)))
+    return out, int(done.value), float(last.value)
+
+
 def _marched(entry, data, out, scalars, iterations, tolerance, ints=()):
     """The call behind tgv / ndf / diff4th / llt_rof: `entry` is the C entry point, `scalars` its float parameters and `ints`
     the integer ones that follow them.  Returns (out, iterations_done, rel_change)."""
@@ -434,6 +469,20 @@ def reserve_tv_scratch(shape, device, method: str = "PD_TV", half: bool = False)
     lib = L.lib()
     kind = BY_NAME.get(method, BY_NAME["ROF_TV"])
     nbytes = getattr(lib, kind.scratch)(dx, dy, dz, nd, *([int(bool(half))] if kind.scratch_half else []))
+    with torch.cuda.device(device):
+        L.check(lib.tomo_reserve_scratch(device.index or 0, nbytes, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+
+
+def reserve_tv_slices_scratch(shape, device, method: str = "PD_TV", half: bool = False):
+    """`reserve_tv_scratch` for the slice-wise form of PD_TV / ROF_TV on a 3D array of `shape` (tomo_pdtv_slices_scratch_bytes /
+    tomo_roftv_slices_scratch_bytes)."""
+    if method not in SLICEWISE_KINDS:
+        raise ValueError(f"{method} does not support slicewise=True")
+    device = torch.device(device)
+    dz, dy, dx = shape
+    lib = L.lib()
+    nbytes = (lib.tomo_pdtv_slices_scratch_bytes(dx, dy, dz, int(bool(half))) if method == "PD_TV"
+              else lib.tomo_roftv_slices_scratch_bytes(dx, dy, dz))
     with torch.cuda.device(device):
         L.check(lib.tomo_reserve_scratch(device.index or 0, nbytes, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
 

@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from .convergence import check_tolerance
-from .supp.regularisers import WAVELETS_REFUSED, has_wavelets, kind_of, wavelet_threshold
+from .supp.regularisers import SLICEWISE_KINDS, WAVELETS_REFUSED, has_wavelets, kind_of, slicewise_of, wavelet_threshold
 
 _last = threading.local()
 
@@ -52,7 +52,15 @@ def prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch
     ``(prox_kind(X) + W_t(X)) * 0.5`` with ``W_t`` the wavelet shrinkage of ``WAVELETS_cupy`` and t = ``regul_param2``: the
     kind runs exactly as without the suffix (all keys keep their meaning for it, ``last_prox()`` reports its iterations),
     then the shrinkage of the same X is averaged into its result.  In z-slab mode that step needs no communication (it is
-    per slice)."""
+    per slice).
+
+    ``_regularisation_["slicewise"] = True`` (ROF_TV and PD_TV; absent / False = the default, 3D TV coupled along z) returns
+    ``stack([prox2d(X[k]) for k in range(nz)])`` for a 3D volume whose extents all exceed 1: the 2D total variation of every
+    (y, x) slice on its own, all slices in one set of launches (docs/kernels/slicewise.md), every other key keeping its
+    meaning.  The result does not depend on how z is cut into chunks or slabs: a slab rank runs its own slices through the
+    same whole-volume function and never touches the communicator (no ghost planes, no reduction), which is why a
+    tolerance > 0 is refused there -- the ranks would stop at different iterations.  A 2D input or a singleton axis already
+    runs the 2D kernels: the key changes nothing there.  The other kinds refuse the key."""
     if _regularisation_.get("exact_roundings") and "PD_TV" in _regularisation_["method"] and ops.get_variant("pdtv") == 0:
         with ops.variant("pdtv", 22):
             return _prox_regul(self, X, _regularisation_, out)
@@ -70,7 +78,11 @@ def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torc
                          "and LLT_ROF")
     args = kind.args(_regularisation_, self)
     half = (_regularisation_.get("half_precision", False),) if kind.half else ()
-    if slab is not None and X.dim() == 3 and min(X.shape) > 1:
+    true3d = X.dim() == 3 and min(X.shape) > 1
+    if slicewise_of(_regularisation_) and true3d:
+        # every slice on its own: the whole-volume function on this rank's slices, with or without a slab
+        res = globals()[kind.cupy](X, *args, self.Atools.device_index, *half, out=out, tolerance=tol, slicewise=True)
+    elif slab is not None and true3d:
         # the volume is one z-slab of a larger one: 3D TV with ghost planes exchanged between z-neighbours
         from . import slab as slab_drivers
         info = {"iterations_done": _regularisation_["iterations"], "rel_change": float("nan")}
@@ -89,18 +101,31 @@ def check_prox_available(self, vol_shape, _regularisation_: dict) -> None:
     """What TGV cannot do yet, as a ValueError before any work is done: z-slab mode on a real 3D volume (the halo protocol
     for its 13 further fields does not exist) and binary16 storage of its fields.  NDF, Diff4th and LLT_ROF have no binary16
     storage either (they do run in z-slab mode).  The ``WAVELETS`` suffix does not combine with LLT_ROF (``regul_param2`` is
-    already that kind's LLT weight).  The other methods pass."""
+    already that kind's LLT weight).  ``slicewise=True`` exists for ROF_TV and PD_TV only, and on a slab rank with a real 3D
+    volume it does not combine with a tolerance > 0 (no communication: the ranks would stop at different iterations and the
+    result would depend on the split).  The other methods pass."""
     kind = kind_of(_regularisation_.get("method"))
     if kind is None:
         return
+    slicewise = slicewise_of(_regularisation_)
+    if slicewise and kind.name not in SLICEWISE_KINDS:
+        raise ValueError(f"{kind.name} does not support slicewise=True")
+    if slicewise and getattr(self, "slab", None) is not None and _true_3d(vol_shape) \
+            and check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']") > 0.0:
+        raise ValueError(f"{kind.name} with slicewise=True does not take a tolerance in z-slab mode: every rank would stop "
+                         "on its own slices and the result would depend on the split")
     if kind.name in WAVELETS_REFUSED and has_wavelets(_regularisation_.get("method")):
         raise ValueError(f"{kind.name} does not combine with WAVELETS: regul_param2 is already its second weight")
     if not kind.half and _regularisation_.get("half_precision", False):
         raise ValueError(f"{kind.name} does not support half_precision=True")
     if kind.slab is None and getattr(self, "slab", None) is not None:
-        shape = tuple(int(v) for v in vol_shape)
-        if len(shape) == 3 and min(shape) > 1:
+        if _true_3d(vol_shape):
             raise ValueError(f"{kind.name} is not available in z-slab mode")
+
+
+def _true_3d(vol_shape) -> bool:
+    shape = tuple(int(v) for v in vol_shape)
+    return len(shape) == 3 and min(shape) > 1
 
 
 def reserve_prox_scratch(self, vol_shape, _regularisation_: dict) -> None:
@@ -114,6 +139,11 @@ def reserve_prox_scratch(self, vol_shape, _regularisation_: dict) -> None:
     if kind is None or getattr(self, "slab", None) is not None:
         return
     shape = tuple(int(v) for v in vol_shape)
+    if slicewise_of(_regularisation_) and _true_3d(shape):   # the work arrays of the slice-wise form
+        ops.reserve_tv_slices_scratch(shape, f"cuda:{self.Atools.device_index}", kind.name, bool(_regularisation_.get("half_precision", False)))
+        if has_wavelets(_regularisation_.get("method")):
+            ops.reserve_wavelet_scratch(shape, f"cuda:{self.Atools.device_index}")
+        return
     if len(shape) == 3 and 1 in shape:       # a singleton axis runs the 2D kernels (_check_if_input_2d_or_3d)
         i = shape.index(1)
         shape = shape[:i] + shape[i + 1:]
@@ -151,17 +181,24 @@ def _marched(run, data, gpu_id: int, out, tolerance):
 
 def ROF_TV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int = 3000,
                 time_marching_parameter: float = 0.001, gpu_id: int = 0, half_precision: bool = False,
-                out=None, tolerance: float = 0.0) -> torch.Tensor:
+                out=None, tolerance: float = 0.0, slicewise: bool = False) -> torch.Tensor:
     """Rudin-Osher-Fatemi TV by explicit time marching (reference: regularisersCuPy.py:41-167).
 
     ``half_precision`` reproduces the reference's binary16 storage of the D fields (they are rounded through
     half in registers; the fused kernel never writes them to memory).  ``tolerance`` > 0 (no reference counterpart) stops
-    the iterations early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after which iteration."""
+    the iterations early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after which iteration.
+    ``slicewise=True`` (no reference counterpart) treats a 3D array as a stack of independent 2D images along axis 0: slice k
+    of the result is what this function returns for ``data[k]``, all slices in one launch per iteration and with one
+    stopping decision over the whole array; a 2D array or a singleton axis runs as without it."""
     tolerance = check_tolerance(tolerance, "tolerance")
     orig_shape = tuple(data.shape)
     d, is2d, axis = _prepare(data, gpu_id)
     res = torch.empty_like(d) if out is None else out.view(d.shape)
-    if tolerance > 0.0:
+    if slicewise and not is2d:
+        _, done, change = ops.roftv_slices(d, res, np.float32(regularisation_parameter), np.float32(time_marching_parameter),
+                                           iterations, half_precision, tolerance)
+        _record(done, change)
+    elif tolerance > 0.0:
         _, done, change = ops.roftv_tol(d, res, np.float32(regularisation_parameter), np.float32(time_marching_parameter),
                                         iterations, half_precision, tolerance)
         _record(done, change)
@@ -174,9 +211,12 @@ def ROF_TV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int =
 
 def PD_TV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int = 1000, methodTV: int = 0,
                nonneg: int = 0, lipschitz_const: float = 8.0, gpu_id: int = 0, half_precision: bool = False,
-               out=None, tolerance: float = 0.0) -> torch.Tensor:
+               out=None, tolerance: float = 0.0, slicewise: bool = False) -> torch.Tensor:
     """Chambolle-Pock primal-dual TV (reference: regularisersCuPy.py:170-296).  ``tolerance`` > 0 (no reference
-    counterpart) stops the iterations early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after which."""
+    counterpart) stops the iterations early by the rule of tomobar_amd/convergence.py; ``last_prox()`` tells after which.
+    ``slicewise=True`` (no reference counterpart) treats a 3D array as a stack of independent 2D images along axis 0: slice k
+    of the result is what this function returns for ``data[k]``, all slices in one set of launches and with one stopping
+    decision over the whole array; a 2D array or a singleton axis runs as without it."""
     tolerance = check_tolerance(tolerance, "tolerance")
     orig_shape = tuple(data.shape)
     d, is2d, axis = _prepare(data, gpu_id)
@@ -186,7 +226,10 @@ def PD_TV_cupy(data, regularisation_parameter: float = 1e-05, iterations: int = 
     theta = np.float32(1.0)
     lt = np.float32(tau / regularisation_parameter)
     res = torch.empty_like(d) if out is None else out.view(d.shape)
-    if tolerance > 0.0:
+    if slicewise and not is2d:
+        _, done, change = ops.pdtv_slices(d, res, sigma, tau, lt, theta, iterations, methodTV, nonneg, half_precision, tolerance)
+        _record(done, change)
+    elif tolerance > 0.0:
         _, done, change = ops.pdtv_tol(d, res, sigma, tau, lt, theta, iterations, methodTV, nonneg, half_precision, tolerance)
         _record(done, change)
     else:

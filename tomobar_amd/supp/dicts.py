@@ -13,7 +13,7 @@ from typing import Optional
 from .. import ops
 from ..convergence import check_tolerance
 from .funcs import _data_dims_swapper
-from .regularisers import WAVELETS_DEFAULTS, has_wavelets, kind_of
+from .regularisers import WAVELETS_DEFAULTS, has_wavelets, kind_of, slicewise_of
 
 LABELS_3D = ["detY", "angles", "detX"]
 LABELS_2D = ["angles", "detX"]
@@ -119,6 +119,7 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
         for key, value in _REGULARISATION_DEFAULTS:
             _regularisation_.setdefault(key, value)
     check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']")
+    slicewise_of(_regularisation_)   # checked where present (a bool), never filled: absent means False
     # the keys of the method prox_regul will run (supp/regularisers.py: TGV, NDF, Diff4th and LLT_ROF add some, none of them
     # implemented in this reference version).  Dictionaries of the other methods are not touched.
     kind = kind_of(_regularisation_.get("method"))

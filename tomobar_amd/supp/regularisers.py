@@ -101,3 +101,17 @@ def has_wavelets(method) -> bool:
 
 def wavelet_threshold(reg):
     return _opt(reg, "regul_param2")
+
+
+# ---- the key "slicewise": True runs the 2D form of the kind on every (y, x) slice of a 3D volume instead of coupling the
+# slices along z (docs/kernels/slicewise.md).  Absent = False; dicts_check does not fill it.
+SLICEWISE = "slicewise"
+SLICEWISE_KINDS = ("ROF_TV", "PD_TV")              # the kinds that have a slice-wise form; the others refuse the key
+
+
+def slicewise_of(reg) -> bool:
+    """The value of ``reg["slicewise"]`` (absent: False); anything but a bool is a ValueError."""
+    value = reg.get(SLICEWISE, False)
+    if not isinstance(value, bool):
+        raise ValueError(f"_regularisation_['{SLICEWISE}'] must be True or False, got {value!r}")
+    return value

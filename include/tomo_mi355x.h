@@ -189,6 +189,38 @@ int tomo_bp3d_admm(tomo_ctx *ctx, int subset, const float *res_dev, float *z_dev
                    const float *u_dev, float *zu_out_dev, float tau, float rho, int relax_on,
                    float one_minus_alpha, float alpha, int nonneg, void *stream);
 
+/* ---------------------------------------------------------------- matched back projector: the exact transpose of tomo_fp3d
+ * tomo_bp3d is ASTRA's voxel-driven bilinear back projector, which is NOT the transpose of the ray-driven Joseph forward
+ * projector (<Ax, y> and <x, By> differ by ~1e-1 relative on white noise).  The four entry points below
+ * apply A^T itself.  No reference counterpart: parity is formula-level, UNPINNED (tests/_matched_bp_oracle.py restates it).
+ * Derivation: in tomo_fp3d, voxel iy of column ix receives the tent weight max(0, 1 - |f_y - iy|) / |sin| from detector pixel
+ * iu (x-stepping angle); f_y is affine in iu with slope 1/sin and equals iy exactly at iu* = f, the detector coordinate
+ * tomo_bp3d computes for the voxel.  The tent has half-width |sin| <= 1 detector pixels, so it covers only i0 = floor(f) and
+ * i0 + 1: the SAME two taps, other weights.  With q = tomo_angle_t::scale (y-stepping: the same with cos; equal at the tie):
+ *     xw = (float)ix - half_n;  yw = (float)iy - half_n;                 half_n = 0.5f*n - 0.5f
+ *     f  = fmaf(xw, cs, fmaf(yw, sn, half_u - cor));                     half_u = 0.5f*nu - 0.5f
+ *     fl = floorf(f);  w = f - fl;  i0 = (int)fl;  s0 = sino[iz][a][i0], s1 = sino[iz][a][i0 + 1]   (0 outside 0 .. nu-1)
+ *     w0 = max(1.0f - w*q, 0.0f) * q;   w1 = max(1.0f - (1.0f - w)*q, 0.0f) * q       (one float32 rounding per operation)
+ *     acc = fmaf(w0, s0, acc);  acc = fmaf(w1, s1, acc)                  (angles ascending, tap 0 then tap 1)
+ * (tomo_bp3d: w0 = 1 - w, w1 = w.)  All four take the PLANAR [nz][subset_size][nu] array and return TOMO_E_INVALID on a
+ * context created with TOMO_FLAG_LERP8 (no transpose of the quantised weights is defined) or set to TOMO_RESIDUAL_ZQUAD.
+ * A vertical CoR component needs nothing new: R(-shift) in front, as for tomo_bp3d. */
+/* tomo_bp3d_matched: vol = A_s^T sino with the transposed Joseph weights w0, w1 derived above (vol fully overwritten). */
+int tomo_bp3d_matched(tomo_ctx *ctx, int subset, const float *sino_dev, float *vol_dev, void *stream);
+/* tomo_bp3d_matched_fista: tomo_bp3d_fista (arguments, aliasing, epilogue roundings) with the gradient A_s^T res formed by
+ *   the transposed Joseph weights w0, w1 derived above instead of (1 - w, w). */
+int tomo_bp3d_matched_fista(tomo_ctx *ctx, int subset, const float *res_dev, const float *xt_dev,
+                            float *xout_dev, float l_inv, int nonneg, void *stream);
+/* tomo_bp3d_matched_fista_momentum: tomo_bp3d_fista_momentum (arguments, aliasing, epilogue roundings) with the gradient
+ *   formed by the transposed Joseph weights w0, w1 derived above. */
+int tomo_bp3d_matched_fista_momentum(tomo_ctx *ctx, int subset, const float *res_dev, float *xt_dev,
+                                     float *xold_x_dev, float l_inv, float beta, int nonneg, void *stream);
+/* tomo_bp3d_matched_admm: tomo_bp3d_admm (arguments, aliasing, epilogue roundings) with g = A_s^T res formed by the
+ *   transposed Joseph weights w0, w1 derived above. */
+int tomo_bp3d_matched_admm(tomo_ctx *ctx, int subset, const float *res_dev, float *z_dev, const float *x_dev,
+                           const float *u_dev, float *zu_out_dev, float tau, float rho, int relax_on,
+                           float one_minus_alpha, float alpha, int nonneg, void *stream);
+
 /* Private layout of the residual BETWEEN tomo_fp3d_residual and its consumer tomo_bp3d_fista / _fista_momentum / _admm on
  * the same context (round 5).  The reference materialises the residual as a [detY, angles, detX] CuPy array between
  * grad_data_term's forward and back projection (data_fidelities.py:28-40); nobody else reads it on the plain LS / PWLS /

@@ -68,6 +68,10 @@ SIGNATURES = {
     "tomo_bp3d_fista": (_i, [_vp, _i, _vp, _vp, _vp, _f, _i, _vp]),
     "tomo_bp3d_fista_momentum": (_i, [_vp, _i, _vp, _vp, _vp, _f, _f, _i, _vp]),
     "tomo_bp3d_admm": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _f, _f, _i, _vp]),
+    "tomo_bp3d_matched": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "tomo_bp3d_matched_fista": (_i, [_vp, _i, _vp, _vp, _vp, _f, _i, _vp]),
+    "tomo_bp3d_matched_fista_momentum": (_i, [_vp, _i, _vp, _vp, _vp, _f, _f, _i, _vp]),
+    "tomo_bp3d_matched_admm": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _f, _f, _i, _vp]),
     "tomo_ctx_set_residual_layout": (_i, [_vp, _i]),
     "tomo_ctx_residual_layout": (_i, [_vp]),
     "tomo_ctx_residual_elems": (_sz, [_vp, _i]),

@@ -24,7 +24,7 @@ class RecToolsDIRCuPy:
     when the detector is padded (methodsDIR.py:44-69)."""
 
     def __init__(self, DetectorsDimH: int, DetectorsDimH_pad: int, DetectorsDimV, CenterRotOffset, AnglesVec,
-                 ObjSize: int, projector: str = "astra", device_projector: int = 0):
+                 ObjSize: int, projector: str = "astra", device_projector: int = 0, adjoint: str = "unmatched"):
         if CenterRotOffset is None:
             CenterRotOffset = 0.0
         # 2D geometry (the reference's RecToolsDIR with DetectorsDimV=None, methodsDIR.py:44-69,322-371): one slice
@@ -39,7 +39,19 @@ class RecToolsDIRCuPy:
         self.projector = projector
         self.geom = "2D" if self.is2d else "3D"
         self.Atools = HipTools3D(DetectorsDimH, DetectorsDimH_pad, DetectorsDimV, AnglesVec, CenterRotOffset,
-                                 ObjSize, "gpu", device_projector, None)
+                                 ObjSize, "gpu", device_projector, None,
+                                 **({} if adjoint == "unmatched" else {"adjoint": adjoint}))
+
+    @property
+    def adjoint(self) -> str:
+        """Which back projector ``BACKPROJ`` applies (no reference counterpart): "unmatched" (default), ASTRA's
+        voxel-driven one, or "matched", the exact transpose of ``FORWPROJ`` (docs/kernels/bp_matched.md).  ``FBP`` keeps
+        the voxel-driven one whatever this says.  Forwards to ``Atools.adjoint``."""
+        return self.Atools.adjoint
+
+    @adjoint.setter
+    def adjoint(self, value):
+        self.Atools.adjoint = value
 
     def _swap(self, data, labels, required):
         data = ops.to_device(data, self.Atools.device_index)
@@ -91,7 +103,10 @@ class RecToolsDIRCuPy:
         """Filtered back projection with the sinc-ramp filter (reference: methodsDIR_CuPy.py:114-150).
 
         Keyword Args: ``data_axes_labels_order`` (the data are brought to ["angles", "detY", "detX"]),
-        ``recon_mask_radius``, ``cutoff_freq`` (default 0.35)."""
+        ``recon_mask_radius``, ``cutoff_freq`` (default 0.35).
+
+        Always back projects with the voxel-driven (unmatched) projector, whatever ``adjoint`` says: filtered back
+        projection is defined with it, and the result must not depend on a switch meant for the iterative drivers."""
         cutoff = kwargs.get("cutoff_freq")
         cutoff = 0.35 if cutoff is None else cutoff
         given = data
@@ -109,7 +124,7 @@ class RecToolsDIRCuPy:
                                             float(1.0 / na / nu), ops.stream_ptr(data)))
         sino = ops.contiguous(data.transpose(0, 1))  # [detY, angles, detX]
         del data
-        rec = self.Atools._backprojCuPy(sino)
+        rec = self.Atools.backward(sino, None, adjoint="unmatched")
         rec = check_kwargs(rec, cupyrun=True, recon_mask_radius=kwargs.get("recon_mask_radius"))
         return ops.like(rec.squeeze(0) if flat else rec, given)
 

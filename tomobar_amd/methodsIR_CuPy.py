@@ -89,7 +89,7 @@ class RecToolsIRCuPy:
 
     def __init__(self, DetectorsDimH: int, DetectorsDimH_pad: int, DetectorsDimV: Union[int, None],
                  CenterRotOffset: Union[float, np.ndarray], AnglesVec: np.ndarray, ObjSize: int,
-                 device_projector: int = 0, OS_number: Optional[int] = None):
+                 device_projector: int = 0, OS_number: Optional[int] = None, adjoint: str = "unmatched"):
         self.OS_number = OS_number
         # padding the detector enlarges the reconstruction grid; the result is cropped back (methodsIR_CuPy.py:72-79)
         self.objsize_user_given = ObjSize if DetectorsDimH_pad != 0 else None
@@ -98,8 +98,10 @@ class RecToolsIRCuPy:
         if DetectorsDimV == 0 or DetectorsDimV is None:
             DetectorsDimV = 1  # 2D is one slice of the 3D geometry (:81-82)
         self.geom = "3D"
+        # (the keyword travels only when it is not the default: projector classes with the reference's constructor still fit)
         self.Atools = HipTools3D(DetectorsDimH, DetectorsDimH_pad, DetectorsDimV, AnglesVec, CenterRotOffset,
-                                 ObjSize, "gpu", device_projector, OS_number)
+                                 ObjSize, "gpu", device_projector, OS_number,
+                                 **({} if adjoint == "unmatched" else {"adjoint": adjoint}))
         self.power_seed = None  # set to an int for a reproducible power-method start vector
         self.last_run = None    # record of the most recent driver call (see _RunMonitor): iterations run, relative changes
         self.slab = None        # tomobar_amd.slab.SlabComm when this object reconstructs one z-slab of a larger volume
@@ -112,6 +114,17 @@ class RecToolsIRCuPy:
     def slab(self, comm):
         self._slab = comm
         self.Atools.slab = comm   # the projector exchanges ghost detector rows itself when a vertical CoR component is set
+
+    @property
+    def adjoint(self) -> str:
+        """Which back projector the drivers use (no reference counterpart): "unmatched" (default), ASTRA's voxel-driven
+        one, or "matched", the exact transpose of the forward projector -- what CGLS, SIRT, Landweber and the power
+        method assume (docs/kernels/bp_matched.md).  Forwards to ``Atools.adjoint``."""
+        return self.Atools.adjoint
+
+    @adjoint.setter
+    def adjoint(self, value):
+        self.Atools.adjoint = value
 
     @property
     def OS_number(self) -> int:

@@ -50,7 +50,8 @@ class HipTools3D:
 
     def __init__(self, detectors_x: int, detectors_x_pad: int, detectors_y: int, angles_vec: np.ndarray,
                  centre_of_rotation: Union[float, np.ndarray], recon_size: int, processing_arch: str = "gpu",
-                 device_index: int = 0, ordsub_number: Optional[int] = None, lerp8: bool = False):
+                 device_index: int = 0, ordsub_number: Optional[int] = None, lerp8: bool = False,
+                 adjoint: str = "unmatched"):
         # ---- validation with the reference's messages (astra_base.py:74-193)
         if detectors_x <= 0:
             raise ValueError("The size of the horizontal detector cannot be negative or zero")
@@ -80,6 +81,8 @@ class HipTools3D:
             raise ValueError("The number of ordered subsets cannot be negative or zero")
         if detectors_y is not None and detectors_y <= 0:
             raise ValueError("The size of the vertical detector cannot be negative or zero")
+        self.lerp8 = bool(lerp8)
+        self._adjoint = self._check_adjoint(adjoint)   # before the native context exists: a refused pair creates nothing
 
         self.detectors_x = int(detectors_x)
         self.detectors_x_pad = int(detectors_x_pad)
@@ -174,6 +177,34 @@ class HipTools3D:
             raise ValueError(f"projection data has shape {tuple(b.shape)}, expected {self.sino_shape(os_index)}")
         return b
 
+    # ------------------------------------------------------------------ which back projector
+    def _check_adjoint(self, value):
+        if value not in ("unmatched", "matched"):
+            raise ValueError(f"adjoint should be 'unmatched' or 'matched', not {value!r}")
+        if value == "matched" and self.lerp8:
+            raise ValueError("adjoint='matched' is the transpose of the unquantised forward projector: "
+                             "it is not available with lerp8=True")
+        return value
+
+    @property
+    def adjoint(self) -> str:
+        """"unmatched" (default): the reference's pair -- ASTRA's voxel-driven bilinear back projector, which is not the
+        transpose of the ray-driven forward projector.  "matched": the exact transpose of the forward projector
+        (include/tomo_mi355x.h, tomo_bp3d_matched; docs/kernels/bp_matched.md) in ``backward``, ``_backproj[OS]CuPy``,
+        ``grad_step``, ``grad_step_momentum`` and ``admm_z_update``, hence in every driver built on them.  Settable."""
+        return self._adjoint
+
+    @adjoint.setter
+    def adjoint(self, value):
+        self._adjoint = self._check_adjoint(value)
+        if value == "matched" and self.residual_layout() != "planar":   # the matched kernels read the planar layout only
+            self.set_residual_layout("planar")
+
+    def _bp_name(self, name, adjoint=None):
+        """The entry point behind ``name`` for the back projector in force (``adjoint`` overrides the object's)."""
+        matched = self._check_adjoint(adjoint or self._adjoint) == "matched"
+        return getattr(self._lib, name.replace("tomo_bp3d", "tomo_bp3d_matched") if matched else name)
+
     # ------------------------------------------------------------------ AstraTools3D interface
     def _forwprojCuPy(self, object3D):
         return self.forward(object3D, None)
@@ -243,12 +274,14 @@ class HipTools3D:
             self._chk(self._lib.tomo_fp3d(self._ctx, self._sub(os_index), ops.ptr(vol), ops.ptr(out), ops.stream_ptr(vol)))
         return out
 
-    def backward(self, sino, os_index=None, out=None):
+    def backward(self, sino, os_index=None, out=None, adjoint=None):
+        """Back projection with the object's back projector (``adjoint`` property); ``adjoint="unmatched"`` /
+        ``"matched"`` picks one for this call alone (FBP is defined with the voxel-driven one)."""
         sino = self._adjoint_in(self._sino_in(sino, os_index), os_index)
         if out is None:
             out = torch.empty(self.vol_shape(), dtype=torch.float32, device=self._device)
         with torch.cuda.device(self._device):
-            self._chk(self._lib.tomo_bp3d(self._ctx, self._sub(os_index), ops.ptr(sino), ops.ptr(out), ops.stream_ptr(sino)))
+            self._chk(self._bp_name("tomo_bp3d", adjoint)(self._ctx, self._sub(os_index), ops.ptr(sino), ops.ptr(out), ops.stream_ptr(sino)))
         return out
 
     # ---- private residual layout between `residual` and `grad_step` / `grad_step_momentum` / `admm_z_update`
@@ -257,7 +290,13 @@ class HipTools3D:
         forward projector leaves the four slices of a quad interleaved, which the back projector stages with one 16-byte
         load instead of four gathers (include/tomo_mi355x.h, TOMO_RESIDUAL_ZQUAD).  Same values, bit for bit; only the
         fused calls above follow it, and only buffers from ``residual_buffer`` may be handed between them.  The drivers
-        switch it on around their loops and back off before they return."""
+        switch it on around their loops and back off before they return.
+
+        With ``adjoint == "matched"`` a request for "zquad" KEEPS the planar layout: the matched back projector reads the
+        planar array only.  ``residual_buffer`` and ``residual`` follow the layout the context reports, so the drivers
+        need no change for it."""
+        if layout == "zquad" and self._adjoint == "matched":
+            layout = "planar"
         if layout == "zquad" and self._vshift is not None:
             raise ValueError("the quad-interleaved residual is not available with a vertical CoR component")
         self._chk(self._lib.tomo_ctx_set_residual_layout(self._ctx, L.RESIDUAL_LAYOUT[layout]))
@@ -267,7 +306,9 @@ class HipTools3D:
         return {v: k for k, v in L.RESIDUAL_LAYOUT.items()}[code]
 
     def residual_buffer(self, os_index=None) -> torch.Tensor:
-        """Uninitialised buffer for the residual of a subset in the context's CURRENT residual layout."""
+        """Uninitialised buffer for the residual of a subset in the context's CURRENT residual layout: the layout the
+        context REPORTS, not the one last asked for -- with ``adjoint == "matched"`` that stays planar whatever
+        ``set_residual_layout`` was given, which is why the drivers need no change for the matched back projector."""
         if self.residual_layout() == "planar":
             return torch.empty(self.sino_shape(os_index), dtype=torch.float32, device=self._device)
         n = int(self._lib.tomo_ctx_residual_elems(self._ctx, self._sub(os_index)))
@@ -386,7 +427,7 @@ class HipTools3D:
             self._check_residual(res, os_index)
         res = self._adjoint_in(res, os_index)
         with torch.cuda.device(self._device):
-            self._chk(self._lib.tomo_bp3d_fista(self._ctx, self._sub(os_index), ops.ptr(res), ops.ptr(x_t), ops.ptr(x_out),
+            self._chk(self._bp_name("tomo_bp3d_fista")(self._ctx, self._sub(os_index), ops.ptr(res), ops.ptr(x_t), ops.ptr(x_out),
                                             float(l_inv), int(bool(nonneg)), ops.stream_ptr(x_t)))
 
     def grad_step_momentum(self, res, x_t, x_old_then_x, l_inv, beta, nonneg, os_index):
@@ -394,7 +435,7 @@ class HipTools3D:
             self._check_residual(res, os_index)
         res = self._adjoint_in(res, os_index)
         with torch.cuda.device(self._device):
-            self._chk(self._lib.tomo_bp3d_fista_momentum(self._ctx, self._sub(os_index), ops.ptr(res), ops.ptr(x_t),
+            self._chk(self._bp_name("tomo_bp3d_fista_momentum")(self._ctx, self._sub(os_index), ops.ptr(res), ops.ptr(x_t),
                                                      ops.ptr(x_old_then_x), float(l_inv), float(beta),
                                                      int(bool(nonneg)), ops.stream_ptr(x_t)))
 
@@ -403,7 +444,7 @@ class HipTools3D:
             self._check_residual(res, os_index)
         res = self._adjoint_in(res, os_index)
         with torch.cuda.device(self._device):
-            self._chk(self._lib.tomo_bp3d_admm(self._ctx, self._sub(os_index), ops.ptr(res), ops.ptr(z), ops.ptr(x),
+            self._chk(self._bp_name("tomo_bp3d_admm")(self._ctx, self._sub(os_index), ops.ptr(res), ops.ptr(z), ops.ptr(x),
                                            ops.ptr(u), ops.ptr(zu_out), float(tau), float(rho), int(bool(relax_on)),
                                            float(one_minus_alpha), float(alpha), int(bool(nonneg)), ops.stream_ptr(z)))
 
@@ -414,7 +455,8 @@ class HipTools3D:
         return tab, n
 
     def kernel_path(self, op: str = "fp") -> str:
-        """Which kernel form the last forward ("fp") / back ("bp") projection of this object took (diagnostics)."""
+        """Which kernel form the last forward ("fp") / back ("bp") projection of this object took (diagnostics); a "bp"
+        text that starts with "matched" names the matched back projector."""
         return self._lib.tomo_ctx_kernel_path(self._ctx, op.encode()).decode()
 
     def _chk(self, rc):

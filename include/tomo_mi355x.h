@@ -31,7 +31,8 @@ extern "C" {
  * tomo_diff4th* entry points joined version 10 without a raise: tests/test_ndf_oracle.py pins the number 10, and _lib.py
  * binds every symbol by name at load, so a library without them is refused all the same.  The three tomo_llt_rof* entry
  * points joined it the same way, for the same reason.  So did the four tomo_wavelet_* entry points, and tomo_halo_pack2 /
- * tomo_halo_pull2 with the four tomo_ipc_region_* entry points. */
+ * tomo_halo_pull2 with the four tomo_ipc_region_* entry points, and tomo_nltv_scratch_bytes, tomo_patch_select and
+ * tomo_nltv. */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -452,6 +453,35 @@ int tomo_wavelet_forward(int device, const float *in_dev, float *pyramid_dev, in
                          float threshold, void *stream);
 int tomo_wavelet_inverse(int device, float *pyramid_dev, float *out_dev, const float *mix_dev, int dx, int dy, int dz,
                          int nd, void *stream);
+/* Non-local total variation (NLTV): PatchSelect builds the neighbour tables, the NLTV iteration uses them.  The
+ * reference's legacy demo (Demos/methods_IR_legacy/DemoFISTA_NLTV_2D.py) passes such tables under NLTV_H_i, NLTV_H_j and
+ * NLTV_Weights, but both halves lived in the regularisation toolkit it no longer depends on: the algorithm, with its order
+ * of operations and its own exponential, is stated in docs/kernels/nltv.md and restated in numpy by tests/_nltv_oracle.py
+ * -- formula-level parity, unpinned; the float32 results (indices included) equal that restatement bit for bit.
+ *   dims as for tomo_pdtv (a dimension of 1 is valid), except that dx and dy may not exceed 65535 (the index tables are
+ *   16-bit).  nd = 3 is a stack of dz independent (y, x) slices: search, patches and iteration never leave a slice.
+ *   The tables are laid out [neighbours][dz][dy][dx]: hi_dev the x index and hj_dev the y index of the k-th neighbour of
+ *   every pixel (uint16), w_dev its weight (float32) -- 8 * neighbours bytes per voxel in all.
+ *   tomo_patch_select: for every pixel the `neighbours` (1..32) offsets of [-search, search]^2 without (0, 0) (search
+ *   1..15) that lie inside the slice and have the smallest patch distance d -- a separable Gaussian-weighted sum of squared
+ *   differences over a (2 patch + 1)^2 patch (patch 1..4), terms outside the slice dropped --, ties to the earlier offset
+ *   (row-major order), stored in ascending order of d with the weight exp(-d / h^2); a pixel with fewer candidates than
+ *   `neighbours` fills the rest with its own index and the weight 0.  One launch (per 65535 slices), no scratch.
+ *   tomo_nltv: u^0 = in, `iters` Jacobi iterations of
+ *       u' = (f / lambda + c sum_k w_k u_k) / (1 / lambda + c sum_k w_k),   c = 2 / sqrt(sum_k w_k (u_k - u)^2 + 1e-12),
+ *   with u_k = u[hj_k, hi_k] inside the pixel's slice.  Every index is clamped into the slice before use (a valid table is
+ *   not changed by that; a corrupt one gives a wrong answer, never an access outside the array).  The iterations ping-pong
+ *   between out_dev and one work array of the TV arena (tomo_nltv_scratch_bytes), so out_dev must not alias in_dev; in_dev
+ *   and the tables are never written.  iters = 0 copies the input.  One launch per iteration, 8 * neighbours + 12 B per voxel.
+ *   tol, *iters_done, *last_rel_change: the early-stopping rule above (tol = 0: off).
+ *   TOMO_E_INVALID: search, patch or neighbours outside their ranges, dx or dy above 65535, a dimension < 1, nd outside
+ *   {2, 3}, a NULL array, a non-positive h or lambda, negative iters, a negative or non-finite tol, out_dev == in_dev. */
+size_t tomo_nltv_scratch_bytes(int dx, int dy, int dz, int nd);
+int tomo_patch_select(int device, const float *in_dev, uint16_t *hi_dev, uint16_t *hj_dev, float *w_dev,
+                      int dx, int dy, int dz, int nd, int search, int patch, int neighbours, float h, void *stream);
+int tomo_nltv(int device, const float *in_dev, float *out_dev, const uint16_t *hi_dev, const uint16_t *hj_dev,
+              const float *w_dev, int dx, int dy, int dz, int nd, int neighbours, float lambda, int iters,
+              double tol, int *iters_done, double *last_rel_change, void *stream);
 /* scratch bytes the TV drivers hold for a given problem (informational; a tolerance adds one float volume, see above) and
  * arena release.  tomo_tgv_scratch_bytes: 16 (nd = 3: U-bar, V, V-bar, P, six Q) or 10 (nd = 2) float arrays, each rounded
  * up to 256 bytes and followed by the 69888-byte array skew.  tomo_ndf_scratch_bytes, tomo_diff4th_scratch_bytes and

@@ -119,6 +119,9 @@ SIGNATURES = {
     "tomo_wavelet_shrink": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "tomo_wavelet_forward": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "tomo_wavelet_inverse": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "tomo_nltv_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_patch_select": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    "tomo_nltv": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
     "tomo_release_scratch": (_i, [_i]),
     "tomo_reserve_scratch": (_i, [_i, _sz, _vp]),
     "tomo_set_placement_tries": (_i, [_i]),

@@ -394,6 +394,62 @@ def wavelet_inverse(pyramid, shape, out=None, mix=None):
     return out
 
 
+def _nltv_tables(data, tables):
+    """the three tables of an array `data`, checked: (K, *data.shape), uint16 / uint16 / float32, contiguous, on its device"""
+    hi, hj, w = tables
+    for name, t, dtype in (("H_i", hi, torch.uint16), ("H_j", hj, torch.uint16), ("Weights", w, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise ValueError(f"{name} must be a {str(dtype).replace('torch.', '')} array")
+        if not t.is_contiguous() or t.device != data.device:
+            raise ValueError(f"{name} must be C-contiguous and live on the device of the data")
+        if t.dim() != data.dim() + 1 or tuple(t.shape[1:]) != tuple(data.shape) or t.shape[0] != w.shape[0]:
+            raise ValueError(f"{name} must have the shape (neighbours, *data.shape) = ({int(w.shape[0])}, "
+                             f"{', '.join(map(str, data.shape))}), got {tuple(t.shape)}")
+    return int(w.shape[0])
+
+
+def patch_select(data, searchwindow, patchwindow, neighbours, edge_parameter):
+    """The neighbour tables of non-local TV (tomo_patch_select; the algorithm: docs/kernels/nltv.md): for every pixel of every
+    (y, x) slice of `data` (2D, or 3D = a stack of slices along axis 0) the `neighbours` most similar pixels inside the search
+    window.  Returns (H_i, H_j, Weights) of shape (neighbours, *data.shape): the x and y indices (uint16) and the weights
+    (float32), 8 * neighbours bytes per voxel."""
+    _chk_f32(data, "data")
+    if data.dim() not in (2, 3):
+        raise ValueError("2D or 3D arrays must be provided only")
+    dx, dy, dz, nd = _tv_dims(data)
+    K = int(neighbours)
+    if not 1 <= K <= 32:
+        raise ValueError("PatchSelect: the number of neighbours must lie in [1, 32]")
+    shape = (K, *data.shape)
+    hi = torch.empty(shape, dtype=torch.uint16, device=data.device)
+    hj = torch.empty(shape, dtype=torch.uint16, device=data.device)
+    w = torch.empty(shape, dtype=torch.float32, device=data.device)
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_patch_select(data.device.index, ptr(data), ptr(hi), ptr(hj), ptr(w), dx, dy, dz, nd,
+                                          int(searchwindow), int(patchwindow), K, float(edge_parameter), stream_ptr(data)))
+    return hi, hj, w
+
+
+def nltv(data, out, H_i, H_j, Weights, lam, iterations, tolerance=0.0):
+    """Non-local TV (tomo_nltv; the algorithm: docs/kernels/nltv.md): `iterations` Jacobi iterations of `data` into `out` (a
+    different array: the iterations ping-pong through it; `data` and the tables are never written) over the tables of
+    `patch_select`, shape (neighbours, *data.shape).  `lam` is a float32 scalar.  Returns (out, iterations_done, rel_change)
+    -- the last relative change the stopping rule evaluated, NaN if none (tolerance 0 = off)."""
+    _chk_f32(data, "data")
+    _chk_f32(out, "out")
+    if data.dim() not in (2, 3):
+        raise ValueError("2D or 3D arrays must be provided only")
+    if tuple(out.shape) != tuple(data.shape) or out.device != data.device:
+        raise ValueError("out must have the shape and the device of the data")
+    K = _nltv_tables(data, (H_i, H_j, Weights))
+    dx, dy, dz, nd = _tv_dims(data)
+    done, last = C.c_int(0), C.c_double(float("nan"))
+    with torch.cuda.device(data.device):
+        L.check(L.lib().tomo_nltv(data.device.index, ptr(data), ptr(out), ptr(H_i), ptr(H_j), ptr(Weights), dx, dy, dz, nd, K,
+                                  float(lam), int(iterations), float(tolerance), C.byref(done), C.byref(last), stream_ptr(data)))
+    return out, int(done.value), float(last.value)
+
+
 _variant_state = threading.local()   # mirror of the library's per-thread switches, per flavour: lets `variant()` restore
 
 
@@ -494,6 +550,18 @@ def reserve_wavelet_scratch(shape, device):
     with torch.cuda.device(device):
         L.check(L.lib().tomo_reserve_scratch(device.index or 0, 4 * wavelet_pyramid_floats(tuple(shape)),
                                              C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+
+
+def reserve_nltv_scratch(shape, device):
+    """`reserve_tv_scratch` for the one work array of the NLTV iterations on arrays of `shape` (tomo_nltv_scratch_bytes; a 3D
+    shape is a stack of slices, singleton axes included)."""
+    device = torch.device(device)
+    nd = len(shape)
+    dz, dy, dx = (1, *shape) if nd == 2 else shape
+    lib = L.lib()
+    with torch.cuda.device(device):
+        L.check(lib.tomo_reserve_scratch(device.index or 0, lib.tomo_nltv_scratch_bytes(dx, dy, dz, nd),
+                                         C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
 
 
 def set_placement_tries(tries: int):

@@ -6,6 +6,8 @@ variation), ``NDF_cupy`` (nonlinear diffusion with the Huber, Perona-Malik and T
 counterpart in this reference version: formula-level parity, unpinned (docs/kernels/tgv.md, docs/kernels/ndf.md,
 docs/kernels/diff4th.md, docs/kernels/llt_rof.md).  ``WAVELETS_cupy`` (db5 wavelet shrinkage, docs/kernels/wavelets.md) is the
 step behind the ``_WAVELETS`` suffix of a method: the reference's tutorials use it, its tree no longer implements it.
+``PatchSelect_cupy`` and ``NLTV_cupy`` (non-local TV over neighbour tables, docs/kernels/nltv.md) are the two halves behind
+the method "NLTV" of the reference's legacy demo, likewise implemented nowhere in its tree.
 
 The iteration loops run inside ``libtomo_mi355x.so`` (``tomo_pdtv`` / ``tomo_roftv``): one fused HIP kernel per
 iteration, launched back to back on the caller's stream, scratch taken from the library's arena
@@ -22,7 +24,8 @@ import torch
 
 from . import ops
 from .convergence import check_tolerance
-from .supp.regularisers import SLICEWISE_KINDS, WAVELETS_REFUSED, has_wavelets, kind_of, slicewise_of, wavelet_threshold
+from .supp.regularisers import (NLTV_CUPY, SLICEWISE_KINDS, WAVELETS_REFUSED, has_wavelets, is_nltv, kind_of, nltv_check,
+                                nltv_iterations, nltv_tables, slicewise_of, wavelet_threshold)
 
 _last = threading.local()
 
@@ -60,7 +63,12 @@ def prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torch
     meaning.  The result does not depend on how z is cut into chunks or slabs: a slab rank runs its own slices through the
     same whole-volume function and never touches the communicator (no ghost planes, no reduction), which is why a
     tolerance > 0 is refused there -- the ranks would stop at different iterations.  A 2D input or a singleton axis already
-    runs the 2D kernels: the key changes nothing there.  The other kinds refuse the key."""
+    runs the 2D kernels: the key changes nothing there.  The other kinds refuse the key.
+
+    A method that contains ``NLTV`` and names no kind (the reference's legacy demo: "NLTV") runs ``NLTV_cupy`` over the tables
+    under ``NLTV_H_i``, ``NLTV_H_j`` and ``NLTV_Weights`` (built beforehand with ``PatchSelect_cupy``) with lambda =
+    ``regul_param`` and ``IterNumb`` (else ``iterations``) iterations (docs/kernels/nltv.md).  It is per slice by definition:
+    a slab rank runs its own slices over its own tables without communication, and refuses a tolerance > 0 as above."""
     if _regularisation_.get("exact_roundings") and "PD_TV" in _regularisation_["method"] and ops.get_variant("pdtv") == 0:
         with ops.variant("pdtv", 22):
             return _prox_regul(self, X, _regularisation_, out)
@@ -73,6 +81,10 @@ def _prox_regul(self, X: torch.Tensor, _regularisation_: dict, out=None) -> torc
     slab = getattr(self, "slab", None)
     check_prox_available(self, X.shape, _regularisation_)
     tol = check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']")
+    if is_nltv(method):
+        # per slice by definition: a slab rank runs its own slices over its own tables, no communication
+        return globals()[NLTV_CUPY](X, *nltv_tables(_regularisation_), _regularisation_["regul_param"], nltv_iterations(_regularisation_),
+                                    self.Atools.device_index, out=out, tolerance=tol)
     if kind is None:
         raise ValueError(f"unknown regularisation method {method!r}: ROF_TV, PD_TV and TGV are supported, as are NDF, Diff4th "
                          "and LLT_ROF")
@@ -103,7 +115,16 @@ def check_prox_available(self, vol_shape, _regularisation_: dict) -> None:
     storage either (they do run in z-slab mode).  The ``WAVELETS`` suffix does not combine with LLT_ROF (``regul_param2`` is
     already that kind's LLT weight).  ``slicewise=True`` exists for ROF_TV and PD_TV only, and on a slab rank with a real 3D
     volume it does not combine with a tolerance > 0 (no communication: the ranks would stop at different iterations and the
-    result would depend on the split).  The other methods pass."""
+    result would depend on the split).  NLTV (docs/kernels/nltv.md) combines with no kind, not with ``WAVELETS`` and not with
+    ``half_precision=True``; a slab rank runs it on its own slices, so there it refuses a tolerance > 0 for the same reason
+    as ``slicewise`` (the key itself is not consulted: NLTV is per slice by definition).  The other methods pass."""
+    nltv_check(_regularisation_)
+    if is_nltv(_regularisation_.get("method")):
+        if getattr(self, "slab", None) is not None and _true_3d(vol_shape) \
+                and check_tolerance(_regularisation_.get("tolerance"), "_regularisation_['tolerance']") > 0.0:
+            raise ValueError("NLTV does not take a tolerance in z-slab mode: every rank would stop on its own slices and "
+                             "the result would depend on the split")
+        return
     kind = kind_of(_regularisation_.get("method"))
     if kind is None:
         return
@@ -135,6 +156,9 @@ def reserve_prox_scratch(self, vol_shape, _regularisation_: dict) -> None:
     arrays inside every call, regularisersCuPy.py:220-232).  Nothing to do without a TV method, and in z-slab mode the
     slab drivers take their own placed block (slab.py)."""
     check_prox_available(self, vol_shape, _regularisation_)
+    if is_nltv(_regularisation_.get("method")):   # one work array, on a slab rank as well (its prox is the whole-volume call)
+        ops.reserve_nltv_scratch(tuple(int(v) for v in vol_shape), f"cuda:{self.Atools.device_index}")
+        return
     kind = kind_of(_regularisation_.get("method"))
     if kind is None or getattr(self, "slab", None) is not None:
         return
@@ -334,6 +358,76 @@ def WAVELETS_cupy(data, regularisation_parameter: float = 0.001, gpu_device: int
     res = torch.empty_like(d) if out is None else out.view(d.shape)
     ops.wavelet_shrink(d, np.float32(regularisation_parameter), out=res, mix=None if mix is None else mix.view(d.shape))
     return _finish(res, is2d, axis, orig_shape, out, data)
+
+
+def PatchSelect_cupy(data, searchwindow: int = 7, patchwindow: int = 2, neighbours: int = 15, edge_parameter: float = 0.9,
+                     gpu_id: int = 0):
+    """The neighbour tables of ``NLTV_cupy``: for every pixel the ``neighbours`` (1..32) pixels of its search window
+    ``[-searchwindow, searchwindow]^2`` (1..15) whose ``(2 patchwindow + 1)^2`` patch (1..4) is most similar to its own, with
+    the weights ``exp(-d / edge_parameter^2)`` of their Gaussian-weighted patch distances ``d``.  A 3D array is a stack of
+    independent (y, x) slices along axis 0 (singleton axes included): search and patches never leave a slice.  Returns
+    ``(H_i, H_j, Weights)`` of shape ``(neighbours, *data.shape)`` on the device: the x and the y index of each neighbour
+    (uint16) and its weight (float32), most similar first; a pixel with fewer candidates than ``neighbours`` fills the rest
+    with its own index and the weight 0.  The tables take ``8 * neighbours`` bytes per voxel.
+
+    The defaults are those of the reference's legacy demo (Demos/methods_IR_legacy/DemoFISTA_NLTV_2D.py), whose
+    ``PatchSelect`` lived in the regularisation toolkit the reference no longer depends on: the algorithm is the one stated
+    in docs/kernels/nltv.md -- formula-level parity, unpinned; indices and weights equal the numpy restatement
+    tests/_nltv_oracle.py bit for bit."""
+    d = _prepare_stack(data, gpu_id)
+    return tuple(ops.like(t, data) for t in ops.patch_select(d, searchwindow, patchwindow, neighbours, np.float32(edge_parameter)))
+
+
+def NLTV_cupy(data, H_i, H_j, Weights, regularisation_parameter: float = 1e-05, iterations: int = 3, gpu_id: int = 0,
+              out=None, tolerance: float = 0.0) -> torch.Tensor:
+    """Non-local total variation over the tables of ``PatchSelect_cupy``: ``iterations`` Jacobi iterations, from ``u = data``,
+    of ``u' = (data / lambda + c sum_k W_k u_k) / (1 / lambda + c sum_k W_k)`` with ``u_k`` the k-th neighbour of the pixel
+    and ``c = 2 / sqrt(sum_k W_k (u_k - u)^2 + 1e-12)``.  A 3D array is a stack of independent (y, x) slices along axis 0
+    (singleton axes included).  The tables hold ``Weights.shape[0]`` neighbours per voxel; any shape with that many
+    elements per neighbour is accepted (of the squeezed or the unsqueezed array).  Tables that are not on the device are
+    copied there on every call: keep them there.  An index beyond the slice is clamped into it.  Like every ``*_cupy``
+    function here (and the reference's), a 2D input comes back with a leading singleton axis unless ``out`` is given.
+
+    There is no reference implementation of it in this reference version (its legacy demo still passes the tables; the
+    function lived in the regularisation toolkit it no longer depends on): the algorithm is the one stated in
+    docs/kernels/nltv.md -- formula-level parity, unpinned; the float32 result equals the numpy restatement
+    tests/_nltv_oracle.py bit for bit.  ``tolerance`` > 0 stops the iterations early by the rule of
+    tomobar_amd/convergence.py; ``last_prox()`` tells after which iteration.  There is no non-negativity switch (the drivers
+    clamp before the prox) and no binary16 storage."""
+    if gpu_id < 0:
+        raise ValueError("The gpu_device must be a positive integer or zero")
+    shape = tuple(int(v) for v in data.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("2D or 3D arrays must be provided only")
+    tables = []
+    for name, t, dtype in (("H_i", H_i, torch.uint16), ("H_j", H_j, torch.uint16), ("Weights", Weights, torch.float32)):
+        t = ops.to_device(t, gpu_id)
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be a {str(dtype).replace('torch.', '')} array")
+        if t.dim() < 2 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a C-contiguous array of shape (neighbours, *data.shape)")
+        tables.append(t)
+    neighbours = int(tables[2].shape[0])
+    for name, t in zip(("H_i", "H_j", "Weights"), tables):
+        if t.shape[0] != neighbours or t.numel() != neighbours * int(np.prod(shape)):
+            raise ValueError(f"{name} has the shape {tuple(t.shape)}: ({neighbours}, {', '.join(map(str, shape))}) is expected")
+    tables = [t.view((neighbours,) + shape) for t in tables]
+    # _marched squeezes a singleton axis; the kernels take the stack as it is
+    return _marched(lambda d, res, tol: ops.nltv(d.view(shape), res.view(shape), *tables, np.float32(regularisation_parameter),
+                                                 iterations, tol),
+                    data, gpu_id, out, tolerance)
+
+
+def _prepare_stack(data, gpu_id: int) -> torch.Tensor:
+    """the array of PatchSelect_cupy on the device: 2D, or 3D = a stack of slices along axis 0, nothing squeezed"""
+    if gpu_id < 0:
+        raise ValueError("The gpu_device must be a positive integer or zero")
+    data = ops.to_device(data, gpu_id)
+    if data.dtype != torch.float32:
+        raise ValueError("The input data should be float32 data type")
+    if data.ndim not in (2, 3):
+        raise ValueError("2D or 3D arrays must be provided only")
+    return ops.contiguous(data)
 
 
 def _check_if_input_2d_or_3d(data) -> Tuple[torch.Tensor, bool, int]:

@@ -13,7 +13,8 @@ from typing import Optional
 from .. import ops
 from ..convergence import check_tolerance
 from .funcs import _data_dims_swapper
-from .regularisers import WAVELETS_DEFAULTS, has_wavelets, kind_of, slicewise_of
+from .regularisers import (NLTV_ITERATIONS, NLTV_NEIGHBOURS, NLTV_TABLES, WAVELETS_DEFAULTS, has_wavelets, is_nltv, kind_of,
+                           nltv_check, nltv_iterations, nltv_tables, slicewise_of)
 
 LABELS_3D = ["detY", "angles", "detX"]
 LABELS_2D = ["angles", "detX"]
@@ -31,6 +32,40 @@ _ALGORITHM_DEFAULTS = (("initialise", None), ("nonnegativity", False), ("recon_m
 _REGULARISATION_DEFAULTS = (("regul_param", 0.001), ("iterations", 150), ("tolerance", 0.0),
                             ("time_marching_step", 0.005), ("PD_LipschitzConstant", 12.0), ("methodTV", 0),
                             ("device_regulariser", 0))
+
+
+def _nltv_keys(self, reg: dict) -> None:
+    """The keys of the NLTV method (supp/regularisers.py; those of the reference's legacy demo): the three tables are
+    required and checked -- dtype, one shape (K, ...) for all three, K times the voxels of the volume --, ``NumNeighb`` is
+    filled with K and must equal it, and the iteration count ``IterNumb`` (the demo's key) becomes ``iterations``."""
+    nltv_tables(reg)
+    for key, want in zip(NLTV_TABLES, ("uint16", "uint16", "float32")):
+        got = str(getattr(reg[key], "dtype", None)).split(".")[-1]
+        if got != want:
+            raise ValueError(f"_regularisation_['{key}'] must be a {want} array, got {got}")
+    shapes = [tuple(int(v) for v in reg[key].shape) for key in NLTV_TABLES]
+    if len(shapes[2]) not in (3, 4) or shapes[0] != shapes[2] or shapes[1] != shapes[2]:
+        raise ValueError(f"the NLTV tables must share one shape (neighbours, *volume), got {shapes[0]}, {shapes[1]} and {shapes[2]}")
+    neighbours = shapes[2][0]
+    vol_shape = getattr(self.Atools, "vol_shape", None)
+    if callable(vol_shape):
+        vol = tuple(int(v) for v in vol_shape())
+        nvox = 1
+        for v in vol:
+            nvox *= v
+        per_neighbour = 1
+        for v in shapes[2][1:]:
+            per_neighbour *= v
+        if per_neighbour != nvox:
+            raise ValueError(f"the NLTV tables have the shape {shapes[2]}: (neighbours, *volume) with the volume {vol} is expected")
+    if reg.get(NLTV_NEIGHBOURS) is None:
+        reg[NLTV_NEIGHBOURS] = neighbours
+    if int(reg[NLTV_NEIGHBOURS]) != neighbours:
+        raise ValueError(f"_regularisation_['{NLTV_NEIGHBOURS}'] = {reg[NLTV_NEIGHBOURS]}, the tables hold {neighbours} neighbours")
+    if reg.get(NLTV_ITERATIONS) is not None:
+        reg["iterations"] = nltv_iterations(reg)
+        if reg["iterations"] < 0:
+            raise ValueError(f"_regularisation_['{NLTV_ITERATIONS}'] must not be negative")
 
 
 def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regularisation_: Optional[dict] = None,
@@ -115,6 +150,9 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
         _regularisation_ = {}
     if not _regularisation_:
         _regularisation_["method"] = None
+    nltv_check(_regularisation_)
+    if is_nltv(_regularisation_.get("method")):   # before the defaults: "iterations" must still be the caller's own
+        _nltv_keys(self, _regularisation_)
     if method_run in {"FISTA", "ADMM", "OSEM"}:
         for key, value in _REGULARISATION_DEFAULTS:
             _regularisation_.setdefault(key, value)

@@ -103,6 +103,60 @@ def wavelet_threshold(reg):
     return _opt(reg, "regul_param2")
 
 
+# ---- NLTV stands beside the table as well: non-local TV over neighbour tables the caller builds beforehand with
+# ``PatchSelect_cupy`` (docs/kernels/nltv.md).  The keys are those of the reference's legacy demo
+# (Demos/methods_IR_legacy/DemoFISTA_NLTV_2D.py), which notes that "NLTV method is quite different to the generic structure
+# of other regularisers": no record of KINDS fits it (three arrays among its arguments, per slice by definition, no z-slab
+# driver and no placed slot).  The call sites branch on ``is_nltv`` before ``kind_of``.
+NLTV = "NLTV"
+NLTV_CUPY = "NLTV_cupy"                            # the whole-volume function in regularisersCuPy (a slab rank runs it too)
+NLTV_SELECT_CUPY = "PatchSelect_cupy"              # what builds the tables
+NLTV_TABLES = ("NLTV_H_i", "NLTV_H_j", "NLTV_Weights")   # required keys: (K, *volume) arrays, uint16 / uint16 / float32
+NLTV_NEIGHBOURS = "NumNeighb"                      # optional: must equal the tables' first extent
+NLTV_ITERATIONS = "IterNumb"                       # the demo's key for the iteration count; absent: "iterations"
+
+
+def is_nltv(method) -> bool:
+    """``method`` is a string that contains ``NLTV`` and names no kind (one that names both is refused: ``nltv_check``)."""
+    return isinstance(method, str) and NLTV in method and kind_of(method) is None
+
+
+def nltv_check(reg) -> None:
+    """The method strings and keys NLTV refuses, as a ValueError: a string that names a kind as well, the ``WAVELETS``
+    suffix, ``half_precision=True``.  Nothing to do for any other method."""
+    method = reg.get("method")
+    if not isinstance(method, str) or NLTV not in method:
+        return
+    kind = kind_of(method)
+    if kind is not None:
+        raise ValueError(f"the regularisation method {method!r} names both {kind.name} and NLTV")
+    if WAVELETS in method:
+        raise ValueError("NLTV does not combine with WAVELETS")
+    if reg.get("half_precision", False):
+        raise ValueError("NLTV does not support half_precision=True")
+
+
+def nltv_tables(reg) -> tuple:
+    """The three tables of ``reg`` in the order ``NLTV_cupy`` takes them.  A missing one is a ValueError that names the key --
+    and the methods that run without tables, which is what a caller who wrote "NLTV" without building any needs to know."""
+    for key in NLTV_TABLES:
+        if reg.get(key) is None:
+            raise ValueError(f"_regularisation_['{key}'] is required by the NLTV method: it takes the tables {NLTV_SELECT_CUPY} "
+                             f"returns as {', '.join(NLTV_TABLES)}; without tables ROF_TV, PD_TV and TGV are supported, as are "
+                             "NDF, Diff4th and LLT_ROF")
+    return tuple(reg[key] for key in NLTV_TABLES)
+
+
+def nltv_iterations(reg) -> int:
+    """``IterNumb`` where present, else ``iterations``; both present and different is a ValueError."""
+    if reg.get(NLTV_ITERATIONS) is None:
+        return reg["iterations"]
+    if reg.get("iterations") is not None and int(reg["iterations"]) != int(reg[NLTV_ITERATIONS]):
+        raise ValueError(f"_regularisation_['{NLTV_ITERATIONS}'] = {reg[NLTV_ITERATIONS]} and _regularisation_['iterations'] = "
+                         f"{reg['iterations']} differ: give one of them")
+    return int(reg[NLTV_ITERATIONS])
+
+
 # ---- the key "slicewise": True runs the 2D form of the kind on every (y, x) slice of a 3D volume instead of coupling the
 # slices along z (docs/kernels/slicewise.md).  Absent = False; dicts_check does not fill it.
 SLICEWISE = "slicewise"

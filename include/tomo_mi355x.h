@@ -32,7 +32,7 @@ extern "C" {
  * binds every symbol by name at load, so a library without them is refused all the same.  The three tomo_llt_rof* entry
  * points joined it the same way, for the same reason.  So did the four tomo_wavelet_* entry points, and tomo_halo_pack2 /
  * tomo_halo_pull2 with the four tomo_ipc_region_* entry points, and tomo_nltv_scratch_bytes, tomo_patch_select and
- * tomo_nltv. */
+ * tomo_nltv, and the five entry points of the private volume layout (TOMO_VOLUME_ZQUAD below). */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -239,6 +239,35 @@ enum { TOMO_RESIDUAL_PLANAR = 0, TOMO_RESIDUAL_ZQUAD = 1 };
 int tomo_ctx_set_residual_layout(tomo_ctx *ctx, int layout);
 int tomo_ctx_residual_layout(const tomo_ctx *ctx);
 size_t tomo_ctx_residual_elems(const tomo_ctx *ctx, int subset);
+
+/* Private layout of X_t inside the FISTA loop with a proximal step (round 7).  X_t has ONE producer there, the momentum
+ * (tomo_momentum_transposed, which already writes it twice: as is and in-plane transposed), and TWO consumers:
+ * tomo_fp3d_residual and the gradient-step epilogue of tomo_bp3d_fista.  The reference holds it as a [Z, Y, X] CuPy array
+ * (methodsIR_CuPy.py:447-475) that nothing else reads, so the three may agree on the layout the forward projector stages
+ * fastest:
+ *   TOMO_VOLUME_PLANAR (default): [nz][n][n], what every entry point documents.
+ *   TOMO_VOLUME_ZQUAD           : "volume zquad", [ceil(nz/4)][n][n][4] float32 -- the four slices of a quad interleaved per
+ *       voxel, slices >= nz of the last quad are zeros.  The forward projector's whole-row form stages one 16-byte word per
+ *       (row, column) straight into LDS (`buffer_load_dwordx4 ... lds`) where the planar layout costs four dword gathers, four
+ *       prefetch registers and a ds_write_b128; the back projector reads its eight words per thread before its LDS hand-over.
+ *       Same arithmetic, bit for bit.  The array must be 16-byte aligned and hold tomo_ctx_volume_elems(ctx) floats; n % 4 == 0.
+ * While ZQUAD is set: tomo_momentum_transposed writes xt_dev (and the transposed token) in that layout from PLANAR x_dev /
+ * xold_dev; tomo_fp3d_residual[_robust] reads vol_dev and tomo_bp3d_fista reads xt_dev in it (xout_dev stays planar).
+ * tomo_volume_to_zquad converts a planar volume into the same pair (X_t = x0, once per FISTA call).  A quad-interleaved
+ * volume can only be forward projected as the very next call after its producer on the same stream -- the transposed twin is
+ * the one-shot token below, and nothing re-creates it -- and only where tomo_ctx_volume_zquad_ok(ctx, subset) returned 1:
+ * every launch of the subset takes the whole-row double-buffered form (docs/kernels/fp.md), the back projector's brick
+ * kernel serves it, and tomo_set_variant("fp", 5) -- the A/B switch of both flavours that keeps a driver on the planar
+ * volume -- is not in force.  Anything else is TOMO_E_INVALID, never a quiet conversion.  tomo_fp3d, tomo_bp3d,
+ * tomo_fp3d_residual_ring, tomo_bp3d_fista_momentum, tomo_bp3d_admm and the matched back projector take planar volumes
+ * only (tomo_fp3d_residual_ring, tomo_bp3d_fista_momentum and tomo_bp3d_admm refuse to run while ZQUAD is set).  These five entry points joined version 10 without a raise, like
+ * the ones listed at TOMO_ABI_VERSION: the tests pin the number, _lib.py binds every symbol by name. */
+enum { TOMO_VOLUME_PLANAR = 0, TOMO_VOLUME_ZQUAD = 1 };
+int tomo_ctx_set_volume_layout(tomo_ctx *ctx, int layout);
+int tomo_ctx_volume_layout(const tomo_ctx *ctx);
+size_t tomo_ctx_volume_elems(const tomo_ctx *ctx);
+int tomo_ctx_volume_zquad_ok(const tomo_ctx *ctx, int subset);
+int tomo_volume_to_zquad(tomo_ctx *ctx, const float *x_dev, float *xq_dev, void *stream);
 
 /* ---------------------------------------------------------------- element-wise glue
  * tomo_momentum : x_t = x + beta*(x - x_old)                         methodsIR_CuPy.py:475
@@ -642,7 +671,8 @@ int tomo_fourier_inv(int device, const float *data_dev, float *out_dev, int nz, 
                      int m, float mu, int center_size, void *stream);
 
 /* kernel-variant selector (per calling host thread): name in {"bp","fp","pdtv","roftv"}; variant 0 = the default of every
- * class.  The shipped library accepts exactly one other value: "pdtv" 22 = float32 duals with the rounding sequence of the
+ * class.  The shipped library accepts two other values: "fp" 5 = the default kernels, but tomo_ctx_volume_zquad_ok answers no,
+ * so a driver keeps the planar X_t (the A/B switch of TOMO_VOLUME_ZQUAD: one process runs both ways), and "pdtv" 22 = float32 duals with the rounding sequence of the
  * reference's kernels reproduced bit for bit (primal_dual_for_total_variation.cu:66-123; FMA-corrected 1 / sqrtf and
  * quotient), +5 ... +16 % per launch depending on the box.  The default runs float32 duals with relaxed arithmetic (v_rsq_f32 instead of 1 / sqrtf, a
  * host-computed 1 / (1 + lt) instead of the divide: within 1e-5 of the reference, typically 3e-7); binary16 duals

@@ -21,6 +21,7 @@ FLAG_LERP8 = 1
 FID = {"LS": 0, "PWLS": 1, "KL": 2, "RATIO": 3}
 ROBUST = {None: 0, "huber": 1, "studentst": 2}   # TOMO_ROBUST_* of include/tomo_mi355x.h
 RESIDUAL_LAYOUT = {"planar": 0, "zquad": 1}   # TOMO_RESIDUAL_* of include/tomo_mi355x.h
+VOLUME_LAYOUT = {"planar": 0, "zquad": 1}     # TOMO_VOLUME_* of include/tomo_mi355x.h
 NDF_PENALTY = {"Huber": 0, "PM": 1, "Tukey": 2}   # TOMO_NDF_* of include/tomo_mi355x.h
 
 
@@ -75,6 +76,11 @@ SIGNATURES = {
     "tomo_ctx_set_residual_layout": (_i, [_vp, _i]),
     "tomo_ctx_residual_layout": (_i, [_vp]),
     "tomo_ctx_residual_elems": (_sz, [_vp, _i]),
+    "tomo_ctx_set_volume_layout": (_i, [_vp, _i]),
+    "tomo_ctx_volume_layout": (_i, [_vp]),
+    "tomo_ctx_volume_elems": (_sz, [_vp]),
+    "tomo_ctx_volume_zquad_ok": (_i, [_vp, _i]),
+    "tomo_volume_to_zquad": (_i, [_vp, _vp, _vp, _vp]),
     "tomo_momentum": (_i, [_vp, _vp, _vp, _f, _sz, _vp]),
     "tomo_momentum_transposed": (_i, [_vp, _vp, _vp, _vp, _f, _vp]),
     "tomo_ctx_invalidate": (_i, [_vp]),

@@ -242,6 +242,36 @@ __global__ __launch_bounds__(256) void bp_brick_kernel(BpArgs a)
             for (int aa = 0; aa < nb; ++aa) sample(aa);
         }
     }
+    // ---- quad-interleaved X_t (round 7; TOMO_VOLUME_ZQUAD, a.xt_zquad): the gradient step X = P+(X_t - g/L) is applied HERE, in the
+    // ownership the sampling had -- one x, rows iy0 and iy0 + 4, the four quads of the z-brick: eight dwordx4 loads per thread,
+    // a 16-lane row of the wave reading one 256-byte run -- and the hand-over below carries finished values that are only
+    // stored.  Read from the post-hand-over ownership (four consecutive x of ONE slice per lane) the layout would cost four
+    // 16-byte-strided dword loads per float4: the access pattern the hand-over was introduced to remove.  Same arithmetic per
+    // voxel as bp_epilogue; edge bricks read the same way and store through the scalar path.
+    [[maybe_unused]] const bool xtq = EPI == EPI_FISTA && a.xt_zquad;  // uniform
+    if constexpr (EPI == EPI_FISTA) {
+        if (xtq) {
+            const v4f *xq = reinterpret_cast<const v4f *>(a.xt);
+            v4f t4[2][BB_ZQ];
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int zq = 0; zq < BB_ZQ; ++zq) {
+                    const int iy = iy0 + 4 * r;
+                    t4[r][zq] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+                    if (ix < a.n && iy < a.n && z0 + 4 * zq < a.nz)  // (the last quad of the volume is whole in this layout)
+                        t4[r][zq] = __builtin_nontemporal_load(xq + ((size_t)((z0 >> 2) + zq) * a.n + iy) * a.n + ix);
+                }
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int j = 0; j < 4 * BB_ZQ; ++j) {
+                    float x = t4[r][j >> 2][j & 3] - a.s0 * acc[r][j >> 1][j & 1];
+                    if (a.nonneg) x = x < 0.0f ? 0.0f : x;
+                    acc[r][j >> 1][j & 1] = x;
+                }
+        }
+    }
     // ---- epilogue.  A brick that lies inside the volume hands its 32 x 16 x 16 accumulators over through LDS (the tile
     // buffers are free now) so that a lane owns four consecutive voxels of a row: 8 dwordx4 accesses per thread and array
     // in whole 128-byte lines instead of 32 dword accesses in 64-byte row pieces (the fused FISTA epilogue cost +1.9 ms
@@ -262,7 +292,9 @@ __global__ __launch_bounds__(256) void bp_brick_kernel(BpArgs a)
             const int item = tid + 256 * m;  // float4 index = (z * 16 + y) * 8 + x4
             const int x4 = item & (BB_TX / 4 - 1), yy = (item / (BB_TX / 4)) & (BB_TY - 1), zz = item / (BB_TX / 4 * BB_TY);
             const float4 g = reinterpret_cast<const float4 *>(stg)[item];
-            bp_epilogue4<EPI>(a, ((size_t)(z0 + zz) * a.n + (ty0 + yy)) * a.n + tx0 + 4 * x4, g);
+            const size_t idx = ((size_t)(z0 + zz) * a.n + (ty0 + yy)) * a.n + tx0 + 4 * x4;
+            if (xtq) __builtin_nontemporal_store(v4f{g.x, g.y, g.z, g.w}, reinterpret_cast<v4f *>(a.xout + idx));  // finished above
+            else bp_epilogue4<EPI>(a, idx, g);
         }
         return;
     }
@@ -273,7 +305,11 @@ __global__ __launch_bounds__(256) void bp_brick_kernel(BpArgs a)
             if (iy < a.n) {
 #pragma unroll
                 for (int j = 0; j < 4 * BB_ZQ; ++j)
-                    if (z0 + j < a.nz) bp_epilogue<EPI>(a, ((size_t)(z0 + j) * a.n + iy) * a.n + ix, acc[r][j >> 1][j & 1]);
+                    if (z0 + j < a.nz) {
+                        const size_t idx = ((size_t)(z0 + j) * a.n + iy) * a.n + ix;
+                        if (xtq) a.xout[idx] = acc[r][j >> 1][j & 1];  // finished above
+                        else bp_epilogue<EPI>(a, idx, acc[r][j >> 1][j & 1]);
+                    }
             }
         }
     }

@@ -59,9 +59,14 @@ __device__ __forceinline__ int fp_lane_pixel(int lane)
 
 // A = angles per workgroup: 8 (FP_A) everywhere except the dense-angle form of round 4 (256 pixels x 16 angles: half the
 // stagings per sample for angle sets whose neighbours in the slope order are a fraction of a degree apart, BASELINE configs[3])
-template <bool LERP8, bool RESID, int PASSES, int M, bool DB, int BT, int A = 8>
+// QV (round 7, whole-row double-buffered form only): `src` is the private QUAD-INTERLEAVED volume [nz/4][row][column][4]
+// (TOMO_VOLUME_ZQUAD, tomo_mi355x.h) and a staged item goes from memory straight into the LDS tile -- one
+// buffer_load_dwordx4 ... lds per item (bb_dma16 of bp_brick.inl): no prefetch registers, no ds_write_b128.  The
+// descriptor's range check clips exactly as in the planar gather; slices past nz are zeros in the layout itself.
+template <bool LERP8, bool RESID, int PASSES, int M, bool DB, int BT, int A = 8, bool QV = false>
 __global__ __launch_bounds__(BT) void fp_tiled_kernel(FpTiledArgs a)
 {
+    static_assert(!QV || (DB && BT == 1024), "the LDS-DMA staging is built for the whole-row double-buffered form");
     constexpr int KC = M / PASSES;
     extern __shared__ __attribute__((aligned(16))) unsigned char fp_smem[];
     const int tile_items = KC * a.wpitch;
@@ -154,12 +159,41 @@ __global__ __launch_bounds__(BT) void fp_tiled_kernel(FpTiledArgs a)
     const int rowbytes = n * 4;
     const int nb1 = z0 + 1 < a.nz ? rowbytes : 0, nb2 = z0 + 2 < a.nz ? rowbytes : 0, nb3 = z0 + 3 < a.nz ? rowbytes : 0;
 
-    float4 pre[M];
+    // QV: chunk k0 -> LDS tile `dst` directly.  Item (row k0+r, column tid + bt p) lands at dst[r * wpitch + tid + bt p]: the
+    // LDS address of an LDS-DMA is wave-uniform base + 16 * lane, and the tile is lane-linear in the column.  Zeros come from
+    // the range check: a column left of the volume (negative offset = huge unsigned), right of it, beyond the window (offset
+    // forced out of range) or a row past the march (zero-length descriptor).
+    [[maybe_unused]] const float4 *qsrc = reinterpret_cast<const float4 *>(a.src) + (size_t)zb * zstride;
+    [[maybe_unused]] const int wave_j0 = __builtin_amdgcn_readfirstlane(tid & ~63);
+    [[maybe_unused]] auto dma = [&](int k0, float4 *dst) {
+#pragma unroll
+        for (int r = 0; r < KC; ++r) {
+            const int k = __builtin_amdgcn_readfirstlane(min(k0 + r, n - 1));
+            const int lo = __builtin_amdgcn_readfirstlane(win_lo[k]);
+            const int wid = (k0 + r < n) ? __builtin_amdgcn_readfirstlane(win_wid[k]) : 0;
+            // (the row address is wave-uniform; say so, or the descriptor may land in VGPRs, which the instruction cannot take)
+            const uintptr_t ra = (uintptr_t)(qsrc + (size_t)k * (size_t)n);
+            const uintptr_t rau = ((uintptr_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(ra >> 32)) << 32) |
+                                  (uintptr_t)(unsigned)__builtin_amdgcn_readfirstlane((int)ra);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)rau, 0, (k0 + r < n) ? n * 16 : 0, 0x00020000);
+#pragma unroll
+            for (int p = 0; p < PASSES; ++p) {
+                const int j = tid + bt * p;
+                const int off = (j < wid) ? ((j + lo) << 4) : (int)0x80000000;
+                // a wave whose 64 columns all lie beyond the tile row skips the pass; lanes beyond it are masked off (they
+                // would write into the next row of the tile)
+                if ((p == 0 || wave_j0 + bt * p < a.wpitch) && j < a.wpitch)
+                    bb_dma16(rs, (unsigned)(uintptr_t)(bb_lds_ptr)(dst + r * a.wpitch + wave_j0 + bt * p), off);
+            }
+        }
+    };
+    [[maybe_unused]] float4 pre[QV ? 1 : M];
     // Gather of the chunk starting at row k0 into registers: pre[r * PASSES + p] <- (row k0+r, column tid + BT p).
     // One buffer descriptor per (row, slice) -- base = the row, num_records = n floats, built by scalar instructions --
     // lets the hardware's range check do what used to be 12 VALU per item: a column left of the volume (negative offset =
     // huge unsigned), right of it, beyond the window (offset forced out of range) or a row past the march loads 0.
     auto prefetch = [&](int k0) {
+        if constexpr (!QV) {
 #pragma unroll
         for (int r = 0; r < KC; ++r) {
             // readfirstlane: the row index is wave-uniform, but in the 16-angle instantiation the compiler carries the chunk
@@ -190,19 +224,26 @@ __global__ __launch_bounds__(BT) void fp_tiled_kernel(FpTiledArgs a)
                 pre[r * PASSES + p] = v;
             }
         }
+        }
     };
 
     const int nchunks = (n + KC - 1) / KC;
-    const bool stage = !(a.probe & 16);  // uniform; false only in the staging-cost measurement (results are garbage then)
-    if (!stage) {
+    const bool stage = QV || !(a.probe & 16);  // uniform; false only in the staging-cost measurement (results are garbage then)
+    if constexpr (!QV) {
+        if (!stage) {
 #pragma unroll
-        for (int i = 0; i < M; ++i) pre[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            for (int i = 0; i < M; ++i) pre[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
     }
-    if (stage) prefetch(0);
+    if constexpr (QV) dma(0, tile0);
+    else if (stage) prefetch(0);
     for (int c = 0; c < nchunks; ++c) {
         float4 *tile = (c & 1) ? tile1 : tile0;
         if (!DB) __syncthreads();  // every wave is past the sampling of chunk c-1 (same buffer)
-        if (stage && !(a.probe & 32)) {
+        if constexpr (QV) {
+            // hand-over order: this thread's pieces of chunk c have landed in LDS, then the chunk barrier below
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else if (stage && !(a.probe & 32)) {
 #pragma unroll
             for (int r = 0; r < KC; ++r)
 #pragma unroll
@@ -219,7 +260,9 @@ __global__ __launch_bounds__(BT) void fp_tiled_kernel(FpTiledArgs a)
         // readfirstlane: (float)row below is a VALU conversion, and from it some instantiations pull the whole chain of wave-uniform
         // row / chunk counters into vector registers (then every use of them costs v_min / v_add / v_readfirstlane instead of SALU)
         const int k0 = __builtin_amdgcn_readfirstlane(c * KC);
-        if (stage && c + 1 < nchunks) prefetch(k0 + KC);  // in flight while chunk c is sampled
+        if constexpr (QV) {
+            if (c + 1 < nchunks) dma(k0 + KC, (c & 1) ? tile0 : tile1);  // in flight while chunk c is sampled
+        } else if (stage && c + 1 < nchunks) prefetch(k0 + KC);  // in flight while chunk c is sampled
 #pragma unroll
         for (int r = 0; r < KC; ++r) {
             // rows past the end of the march are staged as zeros and sampled with the last row's (valid) coordinates,

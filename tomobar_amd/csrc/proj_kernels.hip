@@ -64,6 +64,7 @@ struct BpArgs {
     float *vol;              // EPI_PLAIN: output volume
     // fused epilogues
     const float *xt;         // FISTA: X_t (in)         ADMM: x
+    int xt_zquad;            // EPI_FISTA, brick kernel only: xt is [ceil(nz/4)][n][n][4] (TOMO_VOLUME_ZQUAD, see tomo_mi355x.h)
     float *xout;             // FISTA: X (out)          ADMM: z (in/out)
     float *xt_out;           // FISTA_MOM: new X_t      ADMM: zu (out)
     const float *xold;       // FISTA_MOM: X_old (==xout buffer)   ADMM: u
@@ -360,6 +361,12 @@ int bp_launch(BpArgs a, bool lerp8, hipStream_t st)
     // the brick kernel addresses a 16-slice sinogram slab with 32-bit element offsets
     // (the quad layout is read through one buffer descriptor per z-brick and batch: 4 quads x 16 bytes < 2^31)
     if (EPI == EPI_PLAIN) a.zquad = 0;  // tomo_bp3d always takes the public layout
+    if (EPI != EPI_FISTA) a.xt_zquad = 0;
+    if (a.xt_zquad) {  // only the brick kernel's epilogue reads the quad-interleaved X_t (tomo_ctx_volume_zquad_ok says so beforehand)
+        TOMO_REQUIRE((((uintptr_t)a.xt) & 15) == 0, "the quad-interleaved volume must be 16-byte aligned");
+        TOMO_REQUIRE((g_variant_bp == 0 || g_variant_bp == 3) && (long)a.na * a.nu < (1L << 25),
+                     "this back projection does not read the quad-interleaved volume");
+    }
     if (a.zquad && (((uintptr_t)a.sino) & 15) != 0)
         return tomo_fail(TOMO_E_INVALID, "the quad-interleaved residual must be 16-byte aligned");
     // A PLANAR sinogram (tomo_bp3d: FBP, SIRT, CGLS, OSEM, the power method; the fused epilogues of the ring-term and
@@ -575,6 +582,72 @@ __global__ __launch_bounds__(256) void transpose64_kernel(const float *__restric
     }
 }
 
+// The producers of the private volume layout TOMO_VOLUME_ZQUAD (round 7; tomo_mi355x.h): X_t = X + beta (X - X_old) (MOMENTUM;
+// the same mul-then-add) or X_t = X, written QUAD-INTERLEAVED twice -- xq [nz/4][y][x][4] and, in-plane transposed,
+// xq_T [nz/4][x][y][4] -- for the forward projector's LDS-DMA staging and the back projector's gradient-step epilogue.  No
+// planar X_t exists, so this moves what transpose64_kernel<true> moves: two reads, two writes per voxel.  One workgroup
+// takes a 64 x 64 tile of the FOUR slices of a quad, so every store is a whole float4; the padding slices of the last quad
+// are written as zeros.  LDS tile [4][64][64] floats (the 64 KiB a static array may have), column rotated by the row: the
+// planar float4 writes, the row-wise reads (bank = lane + row) and the transposed reads (bank = lane + column) are all
+// conflict-free.  Needs n % 4 == 0 and 16-byte aligned arrays.
+template <bool MOMENTUM>
+__global__ __launch_bounds__(256) void zquad64_kernel(const float *__restrict__ x, const float *__restrict__ xold,
+                                                      float *__restrict__ xq, float *__restrict__ xq_T, float beta, int n, int nz)
+{
+    __shared__ float t[4][64][64];
+    const size_t plane = (size_t)n * n;
+    const int z0 = 4 * (int)blockIdx.z;
+    const int bx = blockIdx.x * 64, by = blockIdx.y * 64;
+    const int c4 = (threadIdx.x & 15) * 4, r0 = threadIdx.x >> 4;  // 16 float4 columns x 16 rows per pass
+    // all 16 (32 with X_old) loads of the thread are issued before the first value is used: two workgroups share a CU (LDS), so
+    // the bytes in flight have to come from each wave
+    float4 av[4][4], ov[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int zz = 0; zz < 4; ++zz) {
+            const int xx = bx + c4, yy = by + r0 + 16 * k;
+            av[k][zz] = ov[k][zz] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (xx < n && yy < n && z0 + zz < nz) {
+                const size_t i = (size_t)(z0 + zz) * plane + (size_t)yy * n + xx;
+                av[k][zz] = nt_ld4(x + i);
+                if (MOMENTUM) ov[k][zz] = nt_ld4(xold + i);
+            }
+        }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int r = r0 + 16 * k;
+#pragma unroll
+        for (int zz = 0; zz < 4; ++zz) {
+            const float4 a = av[k][zz], o = ov[k][zz];
+            float4 v = a;   // (outside the volume a = o = 0 and the momentum of zeros is +0)
+            if (MOMENTUM) {
+                v.x = a.x + beta * (a.x - o.x); v.y = a.y + beta * (a.y - o.y);
+                v.z = a.z + beta * (a.z - o.z); v.w = a.w + beta * (a.w - o.w);
+            }
+            t[zz][r][(c4 + r) & 63] = v.x; t[zz][r][(c4 + 1 + r) & 63] = v.y;
+            t[zz][r][(c4 + 2 + r) & 63] = v.z; t[zz][r][(c4 + 3 + r) & 63] = v.w;
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const size_t qoff = (size_t)blockIdx.z * plane;  // float4 units
+#pragma unroll 4
+    for (int m = 0; m < 16; ++m) {
+        const int r = w + 4 * m;  // a wave stores one 1 KiB run of a row per instruction
+        const int s = (lane + r) & 63;
+        if (bx + lane < n && by + r < n)
+            nt_st4(xq + 4 * (qoff + (size_t)(by + r) * n + bx + lane), make_float4(t[0][r][s], t[1][r][s], t[2][r][s], t[3][r][s]));
+    }
+#pragma unroll 4
+    for (int m = 0; m < 16; ++m) {
+        const int r = w + 4 * m;  // column of the tile = row of the transposed copy
+        const int s = (r + lane) & 63;
+        if (bx + r < n && by + lane < n)
+            nt_st4(xq_T + 4 * (qoff + (size_t)(bx + r) * n + by + lane), make_float4(t[0][lane][s], t[1][lane][s], t[2][lane][s], t[3][lane][s]));
+    }
+}
+
 static inline bool aligned16(const void *a, const void *b, const void *c, const void *d)
 {
 #ifdef TOMO_GLUE32   // A/B builds only (tools/run_ab.sh): the 32 x 32 dword kernels everywhere
@@ -767,10 +840,13 @@ struct FpLaunch {
     size_t lds;           // dynamic LDS bytes
     long blocks;
     bool mult;            // per-angle lane -> pixel multipliers (whole-row form)
+    bool qv;              // whole-row double-buffered form staged by LDS-DMA from the quad-interleaved volume (TOMO_VOLUME_ZQUAD)
+    int group;            // qv: angles per workgroup when not the form's own (0), see fp_plan_group13
 };
 
 struct FpPlan {
     bool march = false;   // the un-tiled march kernel over the whole subset instead
+    bool qv = false;      // a quad-interleaved volume was asked for and EVERY launch reads it (fp_plan's `volq`)
     int count = 0;
     FpLaunch l[4];
 };
@@ -856,9 +932,35 @@ static FpLaunch fp_plan_tiled(const tomo_ctx *ctx, const tomo_subset &s, int var
     return {FP_TILED, cls, false, off, nc, wp, 256, passes, kc, nut, ngroups, lds, blocks, false};
 }
 
+// Angle groups sized to the class (round 7, qv launches only: the LDS-DMA staging leaves the registers for 13 x 4 accumulators
+// under the 128 of a 1024-thread workgroup).  37 or 38 angles per axis (BASELINE configs[2]) make 3 groups of 13 -- 39 slots,
+// 3 stagings of the volume -- instead of 5 groups of 8 -- 40 slots, 5 stagings.  Taken when 13-angle groups pad to no more
+// slots than 8-angle groups do and the (wider) window still runs double-buffered.
+constexpr int FP_A13 = 13;
+static bool fp_plan_group13(const tomo_ctx *ctx, const tomo_subset &s, FpLaunch &l)
+{
+    if (ceil_div(l.n_angles, FP_A13) * FP_A13 > ceil_div(l.n_angles, FP_A) * FP_A) return false;
+    const int wp = s.wbound_wide13[l.cls], passes = ceil_div(wp, l.threads);
+    if (wp <= 0 || passes > 2) return false;
+    const size_t tab = (size_t)ctx->n * 8;
+    int kc = 4;
+    size_t lds = (size_t)2 * kc * wp * 16 + tab;
+    if (lds > 160 * 1024) { kc = 2; lds = (size_t)2 * kc * wp * 16 + tab; }
+    if (lds > 160 * 1024) return false;
+    l.wpitch = wp; l.passes = passes; l.kc = kc; l.lds = lds;
+    l.ngroups = ceil_div(l.n_angles, FP_A13);
+    l.blocks = fp_blocks(ctx->nz, l.nut, l.ngroups);
+    l.mult = l.mult && (size_t)2 * l.threads * 16 <= lds - tab;
+    l.group = FP_A13;
+    return true;
+}
+
 // The forward projector's kernels for one subset (no HIP calls): per stepping axis the dense form or the whole-row form
 // where they pay, 256-pixel tiles for every class left over, or the march when a class's window does not fit in LDS.
-static int fp_plan(const tomo_ctx *ctx, const tomo_subset &s, int variant, FpPlan &plan)
+// `volq`: the caller holds the volume quad-interleaved (TOMO_VOLUME_ZQUAD).  Only the whole-row double-buffered form reads
+// that layout, so the plan is marked `qv` when every launch takes it (BASELINE configs[2] and [4] do) and left planar --
+// plan.qv false, for the caller to refuse -- otherwise.  Which forms are chosen does not depend on `volq`.
+static int fp_plan(const tomo_ctx *ctx, const tomo_subset &s, int variant, FpPlan &plan, bool volq = false)
 {
     // dense form taken when it stages <= 0.75x what whole rows x 8 angles would
     constexpr double FP_DENSE16_PAYS = 0.75;
@@ -927,6 +1029,12 @@ static int fp_plan(const tomo_ctx *ctx, const tomo_subset &s, int variant, FpPla
         TOMO_REQUIRE(plan.l[i].form != FP_TILED_SYNC || plan.l[i].lds <= 64 * 1024,
                      "forward-projection window does not fit in LDS");
     }
+    if (volq && ctx->n % 4 == 0) {
+        plan.qv = plan.count > 0;
+        for (int i = 0; i < plan.count; ++i) plan.qv &= plan.l[i].form == FP_WHOLE_ROW && plan.l[i].passes <= 2;
+        for (int i = 0; i < plan.count; ++i) plan.l[i].qv = plan.qv;
+        for (int i = 0; i < plan.count && plan.qv; ++i) (void)fp_plan_group13(ctx, s, plan.l[i]);
+    }
     return TOMO_OK;
 }
 
@@ -937,7 +1045,9 @@ static std::string fp_path_text(const FpLaunch &l)
     switch (l.form) {
     case FP_WHOLE_ROW:
         return std::string(l.cls >> 1 ? "x" : "y") + (l.merged ? "" : (l.cls & 1) ? "-" : "+") + ":whole-row(" +
-               std::to_string(l.threads) + " threads, " + passes + ", " + std::to_string(l.kc) + " rows/chunk) ";
+               std::to_string(l.threads) + " threads, " + passes + ", " + std::to_string(l.kc) + " rows/chunk" +
+               (l.qv ? ", quad-interleaved volume, LDS-DMA staging" + std::string(l.group ? ", " + std::to_string(l.group) + " angles) " : ") ")
+                     : ") ");
     case FP_DENSE16: return cls + "dense(256 pixels x 16 angles, " + passes + ") ";
     case FP_TILED: return cls + "tiled-pipelined(256 threads, " + passes + ") ";
     default: return cls + "tiled-sync(window " + std::to_string(l.wpitch) + ") ";
@@ -957,7 +1067,13 @@ static void fp_launch(const FpLaunch &l, const FpTiledArgs &t, hipStream_t st)
         fp_tiled_sync_kernel<L8, RES, 256, FP_A><<<(unsigned)l.blocks, 256, l.lds, st>>>(t, l.kc);
         return;
     case FP_WHOLE_ROW:   // the 1024-thread instantiations, launched with l.threads <= 1024
-        if (l.passes == 1) k = fp_tiled_kernel<L8, RES, 1, 4, true, 1024>;
+        if (l.qv && l.group == FP_A13 && l.passes == 1) k = fp_tiled_kernel<L8, RES, 1, 4, true, 1024, FP_A13, true>;
+        else if (l.qv && l.group == FP_A13 && m == 8) k = fp_tiled_kernel<L8, RES, 2, 8, true, 1024, FP_A13, true>;
+        else if (l.qv && l.group == FP_A13) k = fp_tiled_kernel<L8, RES, 2, 4, true, 1024, FP_A13, true>;
+        else if (l.qv && l.passes == 1) k = fp_tiled_kernel<L8, RES, 1, 4, true, 1024, FP_A, true>;
+        else if (l.qv && m == 8) k = fp_tiled_kernel<L8, RES, 2, 8, true, 1024, FP_A, true>;
+        else if (l.qv) k = fp_tiled_kernel<L8, RES, 2, 4, true, 1024, FP_A, true>;
+        else if (l.passes == 1) k = fp_tiled_kernel<L8, RES, 1, 4, true, 1024>;
         else if (l.passes == 2 && m == 8) k = fp_tiled_kernel<L8, RES, 2, 8, true, 1024>;
         else if (l.passes == 2) k = fp_tiled_kernel<L8, RES, 2, 4, true, 1024>;
         else if (l.passes == 3 && m == 6) k = fp_tiled_kernel<L8, RES, 3, 6, false, 1024>;
@@ -982,7 +1098,7 @@ static void fp_launch(const FpLaunch &l, const FpTiledArgs &t, hipStream_t st)
 
 int fp_run(tomo_ctx *ctx, int subset, const float *vol, const float *b, const float *w, int gathered, int fidelity,
            float *out, void *stream, const float *ring = nullptr, float ring_scale = 0.0f, int zquad = 0,
-           int robust = TOMO_ROBUST_NONE, float rdelta = 0.0f)
+           int robust = TOMO_ROBUST_NONE, float rdelta = 0.0f, int volq = 0)
 {
     TOMO_REQUIRE(ctx != nullptr, "ctx is NULL");
     TOMO_REQUIRE(vol != nullptr && out != nullptr, "NULL data pointer");
@@ -991,15 +1107,25 @@ int fp_run(tomo_ctx *ctx, int subset, const float *vol, const float *b, const fl
     hipStream_t st = as_stream(stream);
     // the transposed copy tomo_momentum_transposed left behind is a ONE-SHOT token: whatever this call does with it
     // (use it, find it belongs to another volume / stream, return early), it is spent before anything else happens
-    const bool ready = ctx->volT_valid && ctx->volT_of == vol && ctx->volT_stream == st && ctx->scratch != nullptr;
+    const bool ready = ctx->volT_valid && ctx->volT_of == vol && ctx->volT_stream == st && ctx->scratch != nullptr &&
+                       ctx->volT_quad == (volq != 0);
     ctx->volT_valid = false;
     ctx->volT_of = nullptr;
     if (s.size == 0) return TOMO_OK;
     TOMO_ON_DEVICE(ctx->device);
+    // fp variant 5 (both flavours) only makes tomo_ctx_volume_zquad_ok say no, so that a driver keeps the planar volume (A/B)
+    const int variant = g_variant_fp == 5 ? 0 : g_variant_fp;
     FpArgs a;
     a.vol = vol;
     a.volT = nullptr;
-    if (s.n_dirx > 0) {
+    if (volq) {
+        // `vol` is the quad-interleaved volume; its in-plane transposed twin is the token the producer (tomo_momentum_transposed
+        // or tomo_volume_to_zquad) has just left in the context.  Nothing here converts: the layout exists to spare that pass.
+        TOMO_REQUIRE((((uintptr_t)vol) & 15) == 0, "the quad-interleaved volume must be 16-byte aligned");
+        TOMO_REQUIRE(s.n_dirx == 0 || ready, "a quad-interleaved volume is forward projected once, right after tomo_momentum_transposed / "
+                                             "tomo_volume_to_zquad wrote it on the same stream");
+        a.volT = (const float *)ctx->scratch;
+    } else if (s.n_dirx > 0) {
         int rc = fp_scratch(ctx);
         if (rc != TOMO_OK) return rc;
         // tomo_momentum_transposed has just written this volume's transposed copy: use it once, skip the pass
@@ -1027,11 +1153,13 @@ int fp_run(tomo_ctx *ctx, int subset, const float *vol, const float *b, const fl
     ctx->last_fp_path.clear();
     const bool l8 = (ctx->flags & TOMO_FLAG_LERP8) != 0;
     FpPlan plan;
-    const int rc = fp_plan(ctx, s, g_variant_fp, plan);
+    const int rc = fp_plan(ctx, s, variant, plan, volq != 0);
     if (rc != TOMO_OK) return rc;
+    TOMO_REQUIRE(!volq || plan.qv, "this subset's forward projection does not read the quad-interleaved volume "
+                                   "(tomo_ctx_volume_zquad_ok says so beforehand)");
     if (plan.march) {
         ctx->last_fp_path = "march(no LDS)";
-        if (g_variant_fp != 1) tomo_warn_once("fp_march", "forward projection: a staged row window exceeds 64 KiB of LDS, "
+        if (variant != 1) tomo_warn_once("fp_march", "forward projection: a staged row window exceeds 64 KiB of LDS, "
                                               "falling back to the un-tiled march kernel (about 4x slower)");
         dim3 grid(ceil_div(ctx->nu, 256), s.size, ceil_div(ctx->nz, 4));
         if (b) {
@@ -1100,8 +1228,10 @@ int fp_tables(tomo_ctx *ctx)
                 s.wbound[c] = fp_window_bound(tab, order + o, nc, n, nu);
                 s.wbound16[c] = fp_window_bound(tab, order + o, nc, n, nu, 256, FP_A16);
                 if (nu > 1024) s.wbound_wide[c] = fp_window_bound(tab, order + o, nc, n, nu, bt);
+                if (nu > 1024) s.wbound_wide13[c] = fp_window_bound(tab, order + o, nc, n, nu, bt, FP_A13);
             }
             if (nu <= 1024 && nc0 + nc1 > 0) s.wbound_wide[2 * d] = fp_window_bound(tab, order + off, nc0 + nc1, n, nu, bt);
+            if (nu <= 1024 && nc0 + nc1 > 0) s.wbound_wide13[2 * d] = fp_window_bound(tab, order + off, nc0 + nc1, n, nu, bt, FP_A13);
             off += nc0 + nc1;
         }
     }
@@ -1139,7 +1269,8 @@ extern "C" int tomo_fp3d_residual(tomo_ctx *ctx, int subset, const float *vol_de
                  "data_fidelity should be LS, PWLS or KL");
     TOMO_REQUIRE(fidelity != TOMO_FID_PWLS || w_full_dev != nullptr, "PWLS needs the weights");
     return fp_run(ctx, subset, vol_dev, b_full_dev, fidelity == TOMO_FID_PWLS ? w_full_dev : nullptr, gathered,
-                  fidelity, res_dev, stream, nullptr, 0.0f, ctx ? ctx->res_layout : 0);
+                  fidelity, res_dev, stream, nullptr, 0.0f, ctx ? ctx->res_layout : 0, TOMO_ROBUST_NONE, 0.0f,
+                  ctx ? ctx->vol_layout : 0);
 }
 
 extern "C" int tomo_fp3d_residual_robust(tomo_ctx *ctx, int subset, const float *vol_dev, const float *b_full_dev,
@@ -1152,7 +1283,7 @@ extern "C" int tomo_fp3d_residual_robust(tomo_ctx *ctx, int subset, const float 
     TOMO_REQUIRE(robust == TOMO_ROBUST_NONE || robust == TOMO_ROBUST_HUBER || robust == TOMO_ROBUST_STUDENTST, "unknown robust mode %d", robust);
     TOMO_REQUIRE(robust == TOMO_ROBUST_NONE || delta > 0.0f, "the Huber / Student's-t threshold must be positive");
     return fp_run(ctx, subset, vol_dev, b_full_dev, fidelity == TOMO_FID_PWLS ? w_full_dev : nullptr, gathered,
-                  fidelity, res_dev, stream, nullptr, 0.0f, ctx ? ctx->res_layout : 0, robust, delta);
+                  fidelity, res_dev, stream, nullptr, 0.0f, ctx ? ctx->res_layout : 0, robust, delta, ctx ? ctx->vol_layout : 0);
 }
 
 extern "C" int tomo_ctx_set_residual_layout(tomo_ctx *ctx, int layout)
@@ -1173,10 +1304,86 @@ extern "C" size_t tomo_ctx_residual_elems(const tomo_ctx *ctx, int subset)
     return nzr * (size_t)s.size * (size_t)ctx->nu;
 }
 
+// ---- private volume layout (TOMO_VOLUME_ZQUAD, tomo_mi355x.h)
+extern "C" int tomo_ctx_set_volume_layout(tomo_ctx *ctx, int layout)
+{
+    TOMO_REQUIRE(ctx != nullptr, "ctx is NULL");
+    TOMO_REQUIRE(layout == TOMO_VOLUME_PLANAR || layout == TOMO_VOLUME_ZQUAD, "unknown volume layout %d", layout);
+    TOMO_REQUIRE(layout == TOMO_VOLUME_PLANAR || ctx->n % 4 == 0, "the quad-interleaved volume needs a slice size that is a multiple of 4");
+    ctx->vol_layout = layout;
+    ctx->volT_valid = false;   // a token of the other layout is worth nothing
+    ctx->volT_of = nullptr;
+    return TOMO_OK;
+}
+
+extern "C" int tomo_ctx_volume_layout(const tomo_ctx *ctx) { return ctx ? ctx->vol_layout : -1; }
+
+extern "C" size_t tomo_ctx_volume_elems(const tomo_ctx *ctx)
+{
+    if (!ctx) return 0;
+    const size_t nzv = ctx->vol_layout == TOMO_VOLUME_ZQUAD ? (size_t)ceil_div(ctx->nz, 4) * 4 : (size_t)ctx->nz;
+    return nzv * (size_t)ctx->n * (size_t)ctx->n;
+}
+
+// Would subset `subset` run on a quad-interleaved X_t?  Host arithmetic only.  Yes when the forward projector plans the
+// whole-row double-buffered form for every launch and the back projector's brick kernel (whose epilogue reads the layout)
+// serves the subset; no under fp variant 5, the A/B switch that keeps a driver on the planar volume.
+extern "C" int tomo_ctx_volume_zquad_ok(const tomo_ctx *ctx, int subset)
+{
+    if (!ctx || subset >= ctx->os || ctx->n % 4 != 0 || ceil_div(ctx->nz, 4) > 65535) return 0;
+    if (g_variant_fp != 0 || (g_variant_bp != 0 && g_variant_bp != 3)) return 0;
+    const tomo_subset &s = (subset < 0 || ctx->os == 1) ? ctx->subsets[0] : ctx->subsets[1 + subset];
+    if (s.size == 0 || (long)s.size * ctx->nu >= (1L << 25)) return 0;
+    FpPlan plan;
+    if (fp_plan(ctx, s, 0, plan, true) != TOMO_OK) return 0;
+    return plan.qv ? 1 : 0;
+}
+
+// the in-plane transposed quad-interleaved copy lives in the context's scratch like the planar one (whole quads)
+static int fp_scratch_zquad(tomo_ctx *ctx)
+{
+    const size_t need = (size_t)ceil_div(ctx->nz, 4) * 4 * ctx->n * ctx->n * sizeof(float);
+    if (ctx->scratch_bytes < need) {
+        ctx->volT_valid = false;
+        if (ctx->scratch) { TOMO_HIP(hipDeviceSynchronize()); TOMO_HIP(hipFree(ctx->scratch)); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
+        TOMO_HIP(hipMalloc(&ctx->scratch, need));
+        ctx->scratch_bytes = need;
+    }
+    return TOMO_OK;
+}
+
+// x (planar), optionally with the momentum of xold, -> xq and the transposed token in the context's scratch
+static int volume_zquad_produce(tomo_ctx *ctx, const float *x_dev, const float *xold_dev, float *xq_dev, float beta, void *stream)
+{
+    TOMO_REQUIRE(ctx->n % 4 == 0 && aligned16(x_dev, xold_dev, xq_dev, nullptr),
+                 "the quad-interleaved volume needs a slice size that is a multiple of 4 and 16-byte aligned arrays");
+    const int nq = ceil_div(ctx->nz, 4);
+    TOMO_REQUIRE(nq <= 65535, "too many slices for one launch");
+    TOMO_ON_DEVICE(ctx->device);
+    int rc = fp_scratch_zquad(ctx);
+    if (rc != TOMO_OK) return rc;
+    dim3 tg(ceil_div(ctx->n, 64), ceil_div(ctx->n, 64), nq);
+    if (xold_dev) zquad64_kernel<true><<<tg, 256, 0, as_stream(stream)>>>(x_dev, xold_dev, xq_dev, (float *)ctx->scratch, beta, ctx->n, ctx->nz);
+    else zquad64_kernel<false><<<tg, 256, 0, as_stream(stream)>>>(x_dev, nullptr, xq_dev, (float *)ctx->scratch, 0.0f, ctx->n, ctx->nz);
+    TOMO_LAUNCH_CHECK();
+    ctx->volT_of = xq_dev;
+    ctx->volT_stream = as_stream(stream);
+    ctx->volT_quad = true;
+    ctx->volT_valid = true;
+    return TOMO_OK;
+}
+
+extern "C" int tomo_volume_to_zquad(tomo_ctx *ctx, const float *x_dev, float *xq_dev, void *stream)
+{
+    TOMO_REQUIRE(ctx != nullptr && x_dev && xq_dev, "NULL argument");
+    return volume_zquad_produce(ctx, x_dev, nullptr, xq_dev, 0.0f, stream);
+}
+
 extern "C" int tomo_momentum_transposed(tomo_ctx *ctx, const float *x_dev, const float *xold_dev, float *xt_dev, float beta,
                                         void *stream)
 {
     TOMO_REQUIRE(ctx != nullptr && x_dev && xold_dev && xt_dev, "NULL argument");
+    if (ctx->vol_layout == TOMO_VOLUME_ZQUAD) return volume_zquad_produce(ctx, x_dev, xold_dev, xt_dev, beta, stream);
     TOMO_ON_DEVICE(ctx->device);
     int rc = fp_scratch(ctx);
     if (rc != TOMO_OK) return rc;
@@ -1190,6 +1397,7 @@ extern "C" int tomo_momentum_transposed(tomo_ctx *ctx, const float *x_dev, const
     TOMO_LAUNCH_CHECK();
     ctx->volT_of = xt_dev;
     ctx->volT_stream = as_stream(stream);
+    ctx->volT_quad = false;
     ctx->volT_valid = true;
     return TOMO_OK;
 }
@@ -1208,6 +1416,7 @@ extern "C" int tomo_fp3d_residual_ring(tomo_ctx *ctx, int subset, const float *v
     TOMO_REQUIRE(b_full_dev != nullptr && ring_dev != nullptr, "projection data / ring offset pointer is NULL");
     TOMO_REQUIRE(ctx == nullptr || ctx->res_layout == TOMO_RESIDUAL_PLANAR,
                  "the ring-term residual is read by tomo_ring_gh_reduce in the planar layout: set TOMO_RESIDUAL_PLANAR first");
+    TOMO_REQUIRE(ctx == nullptr || ctx->vol_layout == TOMO_VOLUME_PLANAR, "the ring-term residual takes the planar volume: set TOMO_VOLUME_PLANAR first");
     return fp_run(ctx, subset, vol_dev, b_full_dev, nullptr, 0, TOMO_FID_LS, res_dev, stream, ring_dev, ring_scale);
 }
 
@@ -1230,6 +1439,7 @@ extern "C" int tomo_bp3d_fista(tomo_ctx *ctx, int subset, const float *res_dev, 
     TOMO_REQUIRE(xt_dev && xout_dev, "NULL volume pointer");
     a.xt = xt_dev; a.xout = xout_dev; a.s0 = l_inv; a.nonneg = nonneg;
     a.zquad = ctx->res_layout == TOMO_RESIDUAL_ZQUAD;
+    a.xt_zquad = ctx->vol_layout == TOMO_VOLUME_ZQUAD;
     return bp_launch<EPI_FISTA>(a, (ctx->flags & TOMO_FLAG_LERP8) != 0, as_stream(stream));
 }
 
@@ -1240,6 +1450,7 @@ extern "C" int tomo_bp3d_fista_momentum(tomo_ctx *ctx, int subset, const float *
     int rc = bp_prepare(ctx, subset, res_dev, a);
     if (rc != TOMO_OK) return rc;
     TOMO_REQUIRE(xt_dev && xold_x_dev, "NULL volume pointer");
+    TOMO_REQUIRE(ctx->vol_layout == TOMO_VOLUME_PLANAR, "the fused gradient step + momentum takes the planar volume: set TOMO_VOLUME_PLANAR first");
     a.xt = xt_dev; a.xt_out = xt_dev; a.xold = xold_x_dev; a.xout = xold_x_dev;
     a.s0 = l_inv; a.s1 = beta; a.nonneg = nonneg;
     a.zquad = ctx->res_layout == TOMO_RESIDUAL_ZQUAD;
@@ -1254,6 +1465,7 @@ extern "C" int tomo_bp3d_admm(tomo_ctx *ctx, int subset, const float *res_dev, f
     int rc = bp_prepare(ctx, subset, res_dev, a);
     if (rc != TOMO_OK) return rc;
     TOMO_REQUIRE(z_dev && x_dev && u_dev && zu_out_dev, "NULL volume pointer");
+    TOMO_REQUIRE(ctx->vol_layout == TOMO_VOLUME_PLANAR, "the ADMM z-update takes the planar volume: set TOMO_VOLUME_PLANAR first");
     a.xt = x_dev; a.xout = z_dev; a.xt_out = zu_out_dev; a.xold = u_dev;
     a.s0 = tau; a.s1 = rho; a.s2 = one_minus_alpha; a.s3 = alpha;
     a.nonneg = nonneg; a.relax_on = relax_on;

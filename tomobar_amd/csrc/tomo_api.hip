@@ -61,7 +61,7 @@ extern "C" int tomo_set_variant(const char *kernel, int variant)
     int *slot = nullptr;
     bool ok = false;
     if (k == "bp") { slot = &g_variant_bp; ok = allowed({0}, {1, 2, 3}); }
-    else if (k == "fp") { slot = &g_variant_fp; ok = allowed({0}, {1, 2, 3, 4}); }   // 4 = whole-row form without the per-angle lane multipliers (A/B)
+    else if (k == "fp") { slot = &g_variant_fp; ok = allowed({0, 5}, {1, 2, 3, 4}); }   // 4 = whole-row form without the per-angle lane multipliers (A/B); 5 = default kernels, but tomo_ctx_volume_zquad_ok says no: the drivers keep the planar X_t (A/B)
     else if (k == "pdtv") { slot = &g_variant_pdtv; ok = allowed({0, 22}, {1, 2, 3, 21, 31, 32}); }
     else if (k == "roftv") { slot = &g_variant_roftv; ok = allowed({0}, {1, 2, 3, 4}); }
 #if TOMO_DEV

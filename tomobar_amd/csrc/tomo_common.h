@@ -48,6 +48,7 @@ struct tomo_subset {
     int wbound[4] = {0, 0, 0, 0};       // per class, 256-pixel tiles x 8 angles
     int wbound_wide[4] = {0, 0, 0, 0};  // whole-row tiles x 8 angles: per axis in [2 * axis] up to 1024 pixels, else per class
     int wbound16[4] = {0, 0, 0, 0};     // per class, 256-pixel tiles x 16 angles (dense angle sets)
+    int wbound_wide13[4] = {0, 0, 0, 0};  // wbound_wide for groups of 13 angles (quad-interleaved volume, fp_plan_group13)
 };
 
 struct tomo_ctx {
@@ -68,6 +69,8 @@ struct tomo_ctx {
     bool volT_valid = false;                  // ... valid for exactly the next forward projection of that volume
     hipStream_t volT_stream = nullptr;        // ... on the stream the copy was written on (another stream would race it)
     std::string last_fp_path, last_bp_path;   // which kernels the last FP / BP call ran (tomo_ctx_kernel_path)
+    bool volT_quad = false;                   // ... quad-interleaved (written for a TOMO_VOLUME_ZQUAD X_t)
+    int vol_layout = 0;                       // TOMO_VOLUME_*: layout of X_t between tomo_momentum_transposed, tomo_fp3d_residual and tomo_bp3d_fista
     int res_layout = 0;                       // TOMO_RESIDUAL_*: layout of the residual between tomo_fp3d_residual and tomo_bp3d_fista* / _admm
 };
 
@@ -107,7 +110,8 @@ void tomo_fbp_cache_release(int device);      // cached hipFFT plans / filter ta
 // kernel-variant switches (tomo_set_variant).  Two flavours of the library are built from these sources:
 //   libtomo_mi355x.so      (shipped): every kernel class runs its default (variant 0); "pdtv" additionally accepts 22 =
 //                          the reference's roundings for float32 duals (bit-identical to the oracle; the default is within
-//                          1e-5).  No measurement switches are compiled in: g_probe is the constant 0 and every
+//                          1e-5), "fp" 5 = default kernels with tomo_ctx_volume_zquad_ok answering no (the drivers keep the
+//                          planar X_t: same-process A/B).  No measurement switches are compiled in: g_probe is the constant 0 and every
 //                          `probe &` test folds away.
 //   libtomo_mi355x_dev.so  (-DTOMO_DEV_VARIANTS; tests and tools/ only): the independent implementations and A/B builds
 //                          (bp 1/2, fp 1/2/3/4, pdtv 1/2/3/21, roftv 1/2/3/4) and the "probe" bits of tools/*_probe.py.

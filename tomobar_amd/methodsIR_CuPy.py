@@ -268,7 +268,6 @@ class RecToolsIRCuPy:
 
         t = float32(1.0)
         X = x0                      # doubles as X_old at the start of every sub-iteration
-        X_t = x0.clone()
         res = {}
         X_grad = self._new_vol() if has_prox else None
         X_prox = self._new_vol() if has_prox else None
@@ -281,9 +280,21 @@ class RecToolsIRCuPy:
         # as [detY, angles, detX] and keep the planar one
         zquad = not (use_ring or use_swls) and not getattr(A, "has_vertical_shift", False)
         A.set_residual_layout("zquad" if zquad else "planar")
+        # with a prox between gradient step and momentum X_t has one producer (A.momentum) and two consumers (A.residual,
+        # A.grad_step): where the residual runs quad-interleaved and every subset's kernels read it, X_t is held
+        # quad-interleaved as well (HipTools3D.set_volume_layout) and x0 is converted once.  Without a prox
+        # (grad_step_momentum), on a z-slab and with a projector object that does not know the layout it stays planar.
+        vquad = (has_prox and zquad and self.slab is None and hasattr(A, "volume_zquad_ok")
+                 and A.residual_layout() == "zquad"   # (the matched back projector keeps the planar residual)
+                 and all(A.volume_zquad_ok(s if use_os else None) for s in range(self.OS_number)))
         n_sub_total = a["iterations"] * self.OS_number
         mon = _RunMonitor(self, "FISTA", a, x0, r)
         try:
+            if vquad:
+                A.set_volume_layout("zquad")
+                X_t = A.volume_to_zquad(x0)
+            else:
+                X_t = x0.clone()
             for it_no in range(a["iterations"]):
                 for sub_ind in range(self.OS_number):
                     sub = sub_ind if use_os else None
@@ -325,6 +336,8 @@ class RecToolsIRCuPy:
                     break
         finally:
             A.set_residual_layout("planar")
+            if vquad:
+                A.set_volume_layout("planar")
             A.invalidate()
         return self._finalise(X, a)
 

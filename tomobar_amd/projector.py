@@ -96,6 +96,7 @@ class HipTools3D:
 
         self.nz, self.n = self.detectors_y, self.recon_size
         self._vshift = None
+        self._vol_zquad = False   # mirrors the context's volume layout (set_volume_layout)
         self.slab = None   # tomobar_amd.slab.SlabComm when this object projects ONE z-slab of a larger volume (RecToolsIRCuPy.slab sets it)
         self.nu = self.detectors_x + 2 * self.detectors_x_pad
         self.na = self.angles_vec.size
@@ -332,6 +333,67 @@ class HipTools3D:
             return res
         return res.permute(0, 3, 1, 2).reshape(-1, res.shape[1], res.shape[2])[: self.nz].contiguous()
 
+    # ---- private layout of X_t between `momentum` / `volume_to_zquad`, `residual` and `grad_step`
+    def volume_zquad_ok(self, os_index=None) -> bool:
+        """Would this subset's fused pair run on a quad-interleaved X_t (include/tomo_mi355x.h, tomo_ctx_volume_zquad_ok)?
+        Host arithmetic only.  False with a vertical CoR component, with the matched back projector and under
+        ``ops.set_variant("fp", 5)``, the A/B switch that keeps the drivers on the planar volume."""
+        if self._vshift is not None or self._adjoint == "matched":
+            return False
+        return bool(self._lib.tomo_ctx_volume_zquad_ok(self._ctx, self._sub(os_index)))
+
+    def set_volume_layout(self, layout: str, require_ok: bool = True):
+        """"planar" (default: X_t is the [detY, N, N] array every entry point documents) or "zquad": ``momentum`` writes X_t
+        with the four slices of a quad interleaved per voxel, ``residual`` stages it straight into LDS and ``grad_step``
+        reads it before its hand-over (include/tomo_mi355x.h, TOMO_VOLUME_ZQUAD).  Same values, bit for bit; only those
+        three calls and ``volume_to_zquad`` follow it, only buffers from ``volume_buffer`` may be handed between them, and
+        "zquad" is refused unless ``volume_zquad_ok`` holds for every subset (``require_ok=False``: the tests of ``momentum``
+        and ``grad_step`` alone, which read the layout on any geometry; ``residual`` still refuses a subset that cannot).  The
+        FISTA driver switches it on around its loop and back off before it returns."""
+        if layout == "zquad" and require_ok:
+            subs = [None] if self.ordsub_number == 1 else range(self.ordsub_number)
+            if not all(self.volume_zquad_ok(s) for s in subs):
+                raise ValueError("the quad-interleaved volume is not available for this geometry (volume_zquad_ok)")
+        self._chk(self._lib.tomo_ctx_set_volume_layout(self._ctx, L.VOLUME_LAYOUT[layout]))
+        self._vol_zquad = layout == "zquad"
+
+    def volume_layout(self) -> str:
+        code = self._lib.tomo_ctx_volume_layout(self._ctx)
+        return {v: k for k, v in L.VOLUME_LAYOUT.items()}[code]
+
+    def volume_buffer(self) -> torch.Tensor:
+        """Uninitialised X_t buffer in the context's CURRENT volume layout."""
+        if self.volume_layout() == "planar":
+            return torch.empty(self.vol_shape(), dtype=torch.float32, device=self._device)
+        return torch.empty(((self.nz + 3) // 4, self.n, self.n, 4), dtype=torch.float32, device=self._device)
+
+    def _check_volume(self, vol, what="volume"):
+        """Same reason as ``_check_residual``: the C-ABI cannot see buffer sizes and the layout is context state."""
+        want = int(self._lib.tomo_ctx_volume_elems(self._ctx))
+        quad = self.volume_layout() == "zquad"
+        if vol.numel() != want or (vol.dim() == 4) != quad or vol.dtype != torch.float32 or not vol.is_contiguous():
+            raise ValueError(f"{what} of {vol.numel()} elements / rank {vol.dim()} does not match the context's current "
+                             f"'{self.volume_layout()}' volume layout ({want} floats): take it from volume_buffer() after "
+                             "set_volume_layout()")
+
+    def volume_to_zquad(self, x, out=None) -> torch.Tensor:
+        """Planar ``x`` -> the quad-interleaved X_t buffer (and its transposed twin in the context, as ``momentum`` leaves it)."""
+        if self.volume_layout() != "zquad":
+            raise ValueError("volume_to_zquad needs set_volume_layout('zquad')")
+        x = self._vol_in(x)
+        if out is None:
+            out = self.volume_buffer()
+        self._check_volume(out)
+        with torch.cuda.device(self._device):
+            self._chk(self._lib.tomo_volume_to_zquad(self._ctx, ops.ptr(x), ops.ptr(out), ops.stream_ptr(x)))
+        return out
+
+    def volume_as_planar(self, vol) -> torch.Tensor:
+        """A [detY, N, N] copy of an X_t buffer whatever layout it was written in (diagnostics / tests)."""
+        if vol.dim() == 3:
+            return vol
+        return vol.permute(0, 3, 1, 2).reshape(-1, self.n, self.n)[: self.nz].contiguous()
+
     # fused forms used by the FISTA / ADMM drivers (buffers validated by the drivers)
     def residual(self, vol, b, w, fidelity: str, os_index, out, gathered: int = 0, robust=None):
         """out = w_s*(A_s vol - b_s) (LS/PWLS) or 1 - b_s/max(A_s vol, 1e-8) (KL); ``gathered`` bit0/bit1: b / w is
@@ -339,6 +401,8 @@ class HipTools3D:
         the Huber / Student's-t re-weighting of the residual in the same epilogue (include/tomo_mi355x.h)."""
         if self._vshift is None:
             self._check_residual(out, os_index)
+        if self._vol_zquad:
+            self._check_volume(vol)
         if robust is not None:
             mode, delta = robust
             if self._vshift is not None:
@@ -413,7 +477,10 @@ class HipTools3D:
 
     def momentum(self, x, x_old, x_t, beta):
         """x_t = x + beta (x - x_old), leaving the in-plane transposed x_t in the context for the next forward
-        projection of x_t (which then skips its transpose pass)."""
+        projection of x_t (which then skips its transpose pass).  Under ``set_volume_layout("zquad")`` x_t (from
+        ``volume_buffer``) and the transposed copy are written quad-interleaved; x and x_old stay planar."""
+        if self._vol_zquad:
+            self._check_volume(x_t, "x_t")
         with torch.cuda.device(self._device):
             self._chk(self._lib.tomo_momentum_transposed(self._ctx, ops.ptr(x), ops.ptr(x_old), ops.ptr(x_t), float(beta),
                                                      ops.stream_ptr(x)))
@@ -425,6 +492,8 @@ class HipTools3D:
     def grad_step(self, res, x_t, x_out, l_inv, nonneg, os_index):
         if self._vshift is None:
             self._check_residual(res, os_index)
+        if self._vol_zquad:
+            self._check_volume(x_t, "x_t")
         res = self._adjoint_in(res, os_index)
         with torch.cuda.device(self._device):
             self._chk(self._bp_name("tomo_bp3d_fista")(self._ctx, self._sub(os_index), ops.ptr(res), ops.ptr(x_t), ops.ptr(x_out),

@@ -1,5 +1,5 @@
 """Small fixed workloads for rocprofv3 --pmc passes (one kernel class per invocation, few launches).
-usage: python tools/pmc_probe.py <what> [N] [NZ] [NA]   what in {pdtv0,pdtv1,pdtv0h,roftv,bp0,bp1,bp3,bpp,bpq,fp,fp4,fpq,momentum,fourier}"""
+usage: python tools/pmc_probe.py <what> [N] [NZ] [NA]   what in {pdtv0,pdtv1,pdtv0h,roftv,bp0,bp1,bp3,bpp,bpq,bpv,fp,fp4,fpq,fpv,momentum,fourier}"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -59,6 +59,16 @@ else:
             H.residual(vol, sino, None, "LS", None, res)
         for _ in range(3 if what == "bpq" else 0):
             H.grad_step(res, vol, out, 1e-4, True, None)
+    elif what in ("bpv", "fpv"):   # the fused pair as the FISTA loop with a prox runs it: X_t AND the residual quad-interleaved (round 7)
+        H.set_residual_layout("zquad")
+        H.set_volume_layout("zquad")
+        res = H.residual_buffer(None)
+        xq = H.volume_buffer()
+        for _ in range(2 if what == "fpv" else 1):
+            H.momentum(vol, out, xq, 0.5)   # the producer: X_t and its transposed twin (zquad64_kernel)
+            H.residual(xq, sino, None, "LS", None, res)
+        for _ in range(3 if what == "bpv" else 0):
+            H.grad_step(res, xq, out, 1e-4, True, None)
     elif what.startswith("bp"):
         ops.set_variant("bp", int(what[2]))
         for _ in range(3):

@@ -14,8 +14,6 @@
 //   * staging latency was exposed (stage, barrier, sample, barrier): here the loads of batch b+1 are in flight (held
 //     in registers) while batch b is sampled.
 // Accumulation order (angles ascending, tap 0 then tap 1, fmaf) is that of the oracle: results are bit-identical.
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int BB_TX = 32, BB_TY = 16, BB_ZQ = 4, BB_AB = 8;
 // columns per (angle, z-quad) row of the tile.  A brick sees at most 31|cos| + 15|sin| <= 34.5 detector pixels plus the
 // second tap and the floor: 37 columns.  Planar staging: 40 (5 items per thread exactly).  Quad-interleaved staging (LDS-DMA,
@@ -246,8 +244,8 @@ __global__ __launch_bounds__(256) void bp_brick_kernel(BpArgs a)
     // ownership the sampling had -- one x, rows iy0 and iy0 + 4, the four quads of the z-brick: eight dwordx4 loads per thread,
     // a 16-lane row of the wave reading one 256-byte run -- and the hand-over below carries finished values that are only
     // stored.  Read from the post-hand-over ownership (four consecutive x of ONE slice per lane) the layout would cost four
-    // 16-byte-strided dword loads per float4: the access pattern the hand-over was introduced to remove.  Same arithmetic per
-    // voxel as bp_epilogue; edge bricks read the same way and store through the scalar path.
+    // 16-byte-strided dword loads per float4: the access pattern the hand-over was introduced to remove.  The arithmetic per
+    // voxel is bp_value's, as in bp_epilogue; edge bricks read the same way and store through the scalar path.
     [[maybe_unused]] const bool xtq = EPI == EPI_FISTA && a.xt_zquad;  // uniform
     if constexpr (EPI == EPI_FISTA) {
         if (xtq) {
@@ -266,8 +264,8 @@ __global__ __launch_bounds__(256) void bp_brick_kernel(BpArgs a)
             for (int r = 0; r < 2; ++r)
 #pragma unroll
                 for (int j = 0; j < 4 * BB_ZQ; ++j) {
-                    float x = t4[r][j >> 2][j & 3] - a.s0 * acc[r][j >> 1][j & 1];
-                    if (a.nonneg) x = x < 0.0f ? 0.0f : x;
+                    float x = 0.0f, unused = 0.0f;
+                    bp_value<EPI_FISTA>(a, acc[r][j >> 1][j & 1], t4[r][j >> 2][j & 3], 0.0f, 0.0f, x, unused);
                     acc[r][j >> 1][j & 1] = x;
                 }
         }

@@ -16,18 +16,14 @@
 // registers into LDS as float4 over z (the loads of batch b + 1 are in flight while batch b is sampled), every tap is one
 // ds_read_b128 serving four slices.  New per (voxel column, angle): q from the angle record and six VALU operations that
 // turn w into (w0, w1), shared by the 16 slices of the column.
-// The argument struct and the epilogue arithmetic live in the anonymous namespace of proj_kernels.hip, whose text is pinned
-// to the measured traffic profiles; they are restated here (MbArgs, mb_value) rather than moved.
-#include "tomo_common.h"
+// The argument struct, the epilogue arithmetic (bp_value) and the host front end are those of the shipped back projector:
+// bp_common.h.
+#include "bp_common.h"
 
 #include <string>
 
 namespace {
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-enum { MB_PLAIN = 0, MB_FISTA = 1, MB_FISTA_MOM = 2, MB_ADMM = 3 };
 constexpr int MB_TX = 32, MB_TY = 16, MB_ZQ = 4, MB_AB = 8;
 // columns per (angle, z-quad) row of the tile: a brick sees at most 31|cos| + 15|sin| <= 34.5 detector pixels plus the
 // second tap and the floor = 37; 40 makes the staging 5 items per thread exactly
@@ -36,61 +32,22 @@ constexpr int MB_NITEMS = MB_AB * MB_ZQ * MB_PITCH;
 constexpr int MB_ITEMS = MB_NITEMS / 256;
 static_assert(MB_NITEMS == 256 * MB_ITEMS, "staging items must divide evenly");
 
-struct MbArgs {
-    const float *sino;       // [nz][na][nu]
-    const tomo_angle_t *tab; // na records
-    int nz, n, nu, na;
-    float *vol;              // MB_PLAIN: output volume
-    const float *xt;         // FISTA: X_t (in)         ADMM: x
-    float *xout;             // FISTA: X (out)          ADMM: z (in/out)
-    float *xt_out;           // FISTA_MOM: new X_t      ADMM: zu (out)
-    const float *xold;       // FISTA_MOM: X_old (== xout buffer)   ADMM: u
-    float s0, s1, s2, s3;    // FISTA: l_inv, beta ; ADMM: tau, rho, (1 - alpha), alpha
-    int nonneg, relax_on;
-    int ntx, nty, nzb;
-    int epi_aligned;         // every array the epilogue touches is 16-byte aligned
-};
-
-// One voxel of an epilogue: gradient g and the values read -> the (up to) two values written.  No contraction: these are
-// the separate roundings of the shipped epilogues (bp_epilogue of proj_kernels.hip, methodsIR_CuPy.py:463-475,545-557).
-//   FISTA      i0 = X_t                       -> o0 = X
-//   FISTA_MOM  i0 = X_t, i1 = X_old           -> o0 = X, o1 = new X_t
-//   ADMM       i0 = z, i1 = u, i2 = x         -> o0 = z, o1 = z + u
+// The epilogues: the loads and stores around bp_value.
 template <int EPI>
-__device__ __forceinline__ void mb_value(const MbArgs &a, float g, float i0, float i1, float i2, float &o0, float &o1)
-{
-    if (EPI == MB_PLAIN) {
-        o0 = g;
-    } else if (EPI == MB_FISTA || EPI == MB_FISTA_MOM) {
-        float x = i0 - a.s0 * g;
-        if (a.nonneg) x = x < 0.0f ? 0.0f : x;
-        o0 = x;
-        if (EPI == MB_FISTA_MOM) o1 = x + a.s1 * (x - i1);
-    } else {
-        const float ga = a.s1 * ((i0 - i2) + i1);
-        float z = i0 - a.s0 * (g + ga);
-        if (a.nonneg) z = z < 0.0f ? 0.0f : z;
-        if (a.relax_on) z = a.s2 * i0 + a.s3 * z;
-        o0 = z;
-        o1 = z + i1;
-    }
-}
-
-template <int EPI>
-__device__ __forceinline__ void mb_epilogue(const MbArgs &a, size_t idx, float g)
+__device__ __forceinline__ void mb_epilogue(const BpArgs &a, size_t idx, float g)
 {
     float o0 = 0.0f, o1 = 0.0f;
-    if (EPI == MB_PLAIN) {
+    if (EPI == EPI_PLAIN) {
         a.vol[idx] = g;
-    } else if (EPI == MB_FISTA) {
-        mb_value<EPI>(a, g, a.xt[idx], 0.0f, 0.0f, o0, o1);
+    } else if (EPI == EPI_FISTA) {
+        bp_value<EPI>(a, g, a.xt[idx], 0.0f, 0.0f, o0, o1);
         a.xout[idx] = o0;
-    } else if (EPI == MB_FISTA_MOM) {
-        mb_value<EPI>(a, g, a.xt[idx], a.xold[idx], 0.0f, o0, o1);
+    } else if (EPI == EPI_FISTA_MOM) {
+        bp_value<EPI>(a, g, a.xt[idx], a.xold[idx], 0.0f, o0, o1);
         a.xout[idx] = o0;
         a.xt_out[idx] = o1;
     } else {
-        mb_value<EPI>(a, g, a.xout[idx], a.xold[idx], a.xt[idx], o0, o1);
+        bp_value<EPI>(a, g, a.xout[idx], a.xold[idx], a.xt[idx], o0, o1);
         a.xout[idx] = o0;
         a.xt_out[idx] = o1;
     }
@@ -100,32 +57,32 @@ __device__ __forceinline__ void mb_epilogue(const MbArgs &a, size_t idx, float g
 // array.  Non-temporal, like the shipped epilogue: the volume streams are touched once and must not evict the sinogram
 // windows that every brick of the XCD re-reads from L2.  Fused forms only: plain stores gain nothing from the hand-over.
 template <int EPI>
-__device__ __forceinline__ void mb_epilogue4(const MbArgs &a, size_t idx, v4f g)
+__device__ __forceinline__ void mb_epilogue4(const BpArgs &a, size_t idx, v4f g)
 {
-    static_assert(EPI != MB_PLAIN, "the plain epilogue stores its accumulators directly");
+    static_assert(EPI != EPI_PLAIN, "the plain epilogue stores its accumulators directly");
     auto ld4 = [&](const float *p) { return __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p + idx)); };
     auto st4 = [&](float *p, v4f v) { __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(p + idx)); };
     const v4f zero = v4f{0.0f, 0.0f, 0.0f, 0.0f};
     v4f i0 = zero, i1 = zero, i2 = zero, o0 = zero, o1 = zero;
-    if (EPI == MB_FISTA) {
+    if (EPI == EPI_FISTA) {
         i0 = ld4(a.xt);
-    } else if (EPI == MB_FISTA_MOM) {
+    } else if (EPI == EPI_FISTA_MOM) {
         i0 = ld4(a.xt); i1 = ld4(a.xold);
-    } else if (EPI == MB_ADMM) {
+    } else if (EPI == EPI_ADMM) {
         i0 = ld4(a.xout); i1 = ld4(a.xold); i2 = ld4(a.xt);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         float p = 0.0f, r = 0.0f;
-        mb_value<EPI>(a, g[k], i0[k], i1[k], i2[k], p, r);
+        bp_value<EPI>(a, g[k], i0[k], i1[k], i2[k], p, r);
         o0[k] = p; o1[k] = r;
     }
     st4(a.xout, o0);
-    if (EPI != MB_FISTA) st4(a.xt_out, o1);
+    if (EPI != EPI_FISTA) st4(a.xt_out, o1);
 }
 
 template <int EPI>
-__global__ __launch_bounds__(256) void bp_matched_kernel(MbArgs a)
+__global__ __launch_bounds__(256) void bp_matched_kernel(BpArgs a)
 {
     // the double-buffered tile [2][angle][z-quad][u] (2 x 20 KiB), then the window table (three slots: a slow wave may
     // still sample batch b - 1 while the window of batch b + 1 is written)
@@ -248,7 +205,7 @@ __global__ __launch_bounds__(256) void bp_matched_kernel(MbArgs a)
             for (int r = 0; r < 2; ++r) {
                 const float f = fmaf(xw, t.cs, fmaf(r ? yw1 : yw0, t.sn, off));
                 const float fl = floorf(f);
-                const float w = f - fl;
+                const float w = lerp_w<false>(f, fl);
                 // the transposed Joseph weights (one rounding per operation, in this order)
                 const float w0 = fmaxf(1.0f - w * q, 0.0f) * q;
                 const float w1 = fmaxf(1.0f - (1.0f - w) * q, 0.0f) * q;
@@ -273,7 +230,7 @@ __global__ __launch_bounds__(256) void bp_matched_kernel(MbArgs a)
     }
     // ---- epilogue.  A brick that lies inside the volume hands its accumulators over through LDS (the tile buffers are
     // free now) so that a lane owns four consecutive voxels of a row: dwordx4 accesses in whole 128-byte lines.
-    if constexpr (EPI != MB_PLAIN) {  // (plain stores gain nothing from the hand-over)
+    if constexpr (EPI != EPI_PLAIN) {  // (plain stores gain nothing from the hand-over)
         if ((tx0 + MB_TX <= a.n) && (ty0 + MB_TY <= a.n) && (z0 + 4 * MB_ZQ <= a.nz) && ((a.n & 3) == 0) && a.epi_aligned) {  // uniform for the workgroup
             float *stg = reinterpret_cast<float *>(&tile2[0][0]);  // [16 z][16 y][32 x] floats = 32 KiB of the 40
             __syncthreads();  // every wave is past the sampling of the last batch
@@ -306,36 +263,25 @@ __global__ __launch_bounds__(256) void bp_matched_kernel(MbArgs a)
     }
 }
 
-int mb_prepare(tomo_ctx *ctx, int subset, const float *sino, MbArgs &a)
+// what the matched kernel refuses beyond bp_prepare
+int mb_check(const tomo_ctx *ctx, const BpArgs &a)
 {
-    TOMO_REQUIRE(ctx != nullptr, "ctx is NULL");
-    TOMO_REQUIRE(subset < ctx->os, "subset %d out of range (OS_number %d)", subset, ctx->os);
     TOMO_REQUIRE((ctx->flags & TOMO_FLAG_LERP8) == 0,
                  "the matched back projector is the transpose of the unquantised forward projector: no transpose is defined "
                  "for a context created with TOMO_FLAG_LERP8");
     TOMO_REQUIRE(ctx->res_layout == TOMO_RESIDUAL_PLANAR,
                  "the matched back projector reads the planar [nz][subset_size][nu] layout only: set TOMO_RESIDUAL_PLANAR first");
-    const tomo_subset &s = (subset < 0 || ctx->os == 1) ? ctx->subsets[0] : ctx->subsets[1 + subset];
-    TOMO_REQUIRE(sino != nullptr || s.size == 0, "NULL sinogram pointer");
     // the kernel addresses a 16-slice sinogram slab with 32-bit element offsets
-    TOMO_REQUIRE((long)s.size * ctx->nu < (1L << 27), "matched back projection: angles x detector >= 2^27 samples per slice");
-    a = MbArgs();
-    a.sino = sino;
-    a.tab = ctx->dev_table + s.table_offset;
-    a.nz = ctx->nz; a.n = ctx->n; a.nu = ctx->nu; a.na = s.size;
+    TOMO_REQUIRE((long)a.na * a.nu < (1L << 27), "matched back projection: angles x detector >= 2^27 samples per slice");
     return TOMO_OK;
 }
 
 template <int EPI>
-int mb_launch(tomo_ctx *ctx, MbArgs a, hipStream_t st)
+int mb_launch(tomo_ctx *ctx, BpArgs a, hipStream_t st)
 {
     TOMO_ON_DEVICE(ctx->device);
     tomo_prof_scope prof(PROF_BP, st, 1);
-    uintptr_t bits = 0;
-    if (EPI == MB_PLAIN) bits |= (uintptr_t)a.vol;
-    else bits |= (uintptr_t)a.xt | (uintptr_t)a.xout;
-    if (EPI == MB_FISTA_MOM || EPI == MB_ADMM) bits |= (uintptr_t)a.xt_out | (uintptr_t)a.xold;
-    a.epi_aligned = (bits & 15) == 0;
+    a.epi_aligned = bp_epi_aligned<EPI>(a);
     a.ntx = ceil_div(a.n, MB_TX);
     a.nty = ceil_div(a.n, MB_TY);
     a.nzb = ceil_div(a.nz, 4 * MB_ZQ);
@@ -349,49 +295,47 @@ int mb_launch(tomo_ctx *ctx, MbArgs a, hipStream_t st)
 
 }  // namespace
 
+// ---- entry points: bp_prepare, the form's filler (bp_common.h), mb_check, mb_launch
 extern "C" int tomo_bp3d_matched(tomo_ctx *ctx, int subset, const float *sino_dev, float *vol_dev, void *stream)
 {
-    MbArgs a;
-    int rc = mb_prepare(ctx, subset, sino_dev, a);
+    BpArgs a;
+    int rc = bp_prepare(ctx, subset, sino_dev, a);
+    if (rc == TOMO_OK) rc = bp_fill_plain(a, vol_dev);
+    if (rc == TOMO_OK) rc = mb_check(ctx, a);
     if (rc != TOMO_OK) return rc;
-    TOMO_REQUIRE(vol_dev != nullptr, "NULL volume pointer");
-    a.vol = vol_dev;
-    return mb_launch<MB_PLAIN>(ctx, a, as_stream(stream));
+    return mb_launch<EPI_PLAIN>(ctx, a, as_stream(stream));
 }
 
 extern "C" int tomo_bp3d_matched_fista(tomo_ctx *ctx, int subset, const float *res_dev, const float *xt_dev,
                                        float *xout_dev, float l_inv, int nonneg, void *stream)
 {
-    MbArgs a;
-    int rc = mb_prepare(ctx, subset, res_dev, a);
+    BpArgs a;
+    int rc = bp_prepare(ctx, subset, res_dev, a);
+    if (rc == TOMO_OK) rc = bp_fill_fista(a, xt_dev, xout_dev, l_inv, nonneg);
+    if (rc == TOMO_OK) rc = mb_check(ctx, a);
     if (rc != TOMO_OK) return rc;
-    TOMO_REQUIRE(xt_dev && xout_dev, "NULL volume pointer");
-    a.xt = xt_dev; a.xout = xout_dev; a.s0 = l_inv; a.nonneg = nonneg;
-    return mb_launch<MB_FISTA>(ctx, a, as_stream(stream));
+    return mb_launch<EPI_FISTA>(ctx, a, as_stream(stream));
 }
 
 extern "C" int tomo_bp3d_matched_fista_momentum(tomo_ctx *ctx, int subset, const float *res_dev, float *xt_dev,
                                                 float *xold_x_dev, float l_inv, float beta, int nonneg, void *stream)
 {
-    MbArgs a;
-    int rc = mb_prepare(ctx, subset, res_dev, a);
+    BpArgs a;
+    int rc = bp_prepare(ctx, subset, res_dev, a);
+    if (rc == TOMO_OK) rc = bp_fill_fista_momentum(a, xt_dev, xold_x_dev, l_inv, beta, nonneg);
+    if (rc == TOMO_OK) rc = mb_check(ctx, a);
     if (rc != TOMO_OK) return rc;
-    TOMO_REQUIRE(xt_dev && xold_x_dev, "NULL volume pointer");
-    a.xt = xt_dev; a.xt_out = xt_dev; a.xold = xold_x_dev; a.xout = xold_x_dev;
-    a.s0 = l_inv; a.s1 = beta; a.nonneg = nonneg;
-    return mb_launch<MB_FISTA_MOM>(ctx, a, as_stream(stream));
+    return mb_launch<EPI_FISTA_MOM>(ctx, a, as_stream(stream));
 }
 
 extern "C" int tomo_bp3d_matched_admm(tomo_ctx *ctx, int subset, const float *res_dev, float *z_dev, const float *x_dev,
                                       const float *u_dev, float *zu_out_dev, float tau, float rho, int relax_on,
                                       float one_minus_alpha, float alpha, int nonneg, void *stream)
 {
-    MbArgs a;
-    int rc = mb_prepare(ctx, subset, res_dev, a);
+    BpArgs a;
+    int rc = bp_prepare(ctx, subset, res_dev, a);
+    if (rc == TOMO_OK) rc = bp_fill_admm(a, z_dev, x_dev, u_dev, zu_out_dev, tau, rho, relax_on, one_minus_alpha, alpha, nonneg);
+    if (rc == TOMO_OK) rc = mb_check(ctx, a);
     if (rc != TOMO_OK) return rc;
-    TOMO_REQUIRE(z_dev && x_dev && u_dev && zu_out_dev, "NULL volume pointer");
-    a.xt = x_dev; a.xout = z_dev; a.xt_out = zu_out_dev; a.xold = u_dev;
-    a.s0 = tau; a.s1 = rho; a.s2 = one_minus_alpha; a.s3 = alpha;
-    a.nonneg = nonneg; a.relax_on = relax_on;
-    return mb_launch<MB_ADMM>(ctx, a, as_stream(stream));
+    return mb_launch<EPI_ADMM>(ctx, a, as_stream(stream));
 }

@@ -18,7 +18,7 @@
 //     copy of the volume so that the interpolation axis is always the contiguous one.  Variant 1: no LDS.
 //   * epilogues: plain / residual (FP) and plain / FISTA step / FISTA step+momentum / ADMM z-update (BP).
 // No MFMA: there is no dense contraction on this path.
-#include "tomo_common.h"
+#include "bp_common.h"
 
 #include <algorithm>
 #include <atomic>
@@ -32,14 +32,6 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------ shared pieces
-template <bool LERP8>
-__device__ __forceinline__ float lerp_w(float f, float fl)
-{
-    float w = f - fl;
-    if (LERP8) w = rintf(w * 256.0f) * (1.0f / 256.0f);
-    return w;
-}
-
 // Robust re-weighting of a data residual (the Huber and Student's-t data terms of the reference's removed RecToolsIR class:
 // _data_["huber_threshold"], _data_["studentst_threshold"], Demos/methods_IR_legacy/DemoFISTA_artifacts2D.py:197,348;
 // formula-level, see include/tomo_mi355x.h): Huber  r <- (delta/|r|) r where |r| > delta;  Student's t  r <- (2/(delta^2 + r^2)) r
@@ -54,118 +46,59 @@ __device__ __forceinline__ float robust_weight(float r, int mode, float delta)
     return r;
 }
 
-enum { EPI_PLAIN = 0, EPI_FISTA = 1, EPI_FISTA_MOM = 2, EPI_ADMM = 3 };
-
-struct BpArgs {
-    const float *sino;       // [nz][na][nu]; zquad: [ceil(nz/4)][na][nu][4] (TOMO_RESIDUAL_ZQUAD, fused epilogues only)
-    int zquad;
-    const tomo_angle_t *tab; // na records
-    int nz, n, nu, na;
-    float *vol;              // EPI_PLAIN: output volume
-    // fused epilogues
-    const float *xt;         // FISTA: X_t (in)         ADMM: x
-    int xt_zquad;            // EPI_FISTA, brick kernel only: xt is [ceil(nz/4)][n][n][4] (TOMO_VOLUME_ZQUAD, see tomo_mi355x.h)
-    float *xout;             // FISTA: X (out)          ADMM: z (in/out)
-    float *xt_out;           // FISTA_MOM: new X_t      ADMM: zu (out)
-    const float *xold;       // FISTA_MOM: X_old (==xout buffer)   ADMM: u
-    float s0, s1, s2, s3;    // FISTA: l_inv, beta ; ADMM: tau, rho, (1-alpha), alpha
-    int nonneg, relax_on;
-    int ntx, nty, nzb;       // tiled variant: tile counts
-    int epi_aligned;         // every array the epilogue touches is 16-byte aligned (dwordx4 epilogue of the brick kernel)
-    int device;              // host side only: the context's device (made current around the launch)
-    std::string *path;       // host side only: receives the name of the kernel that ran
-};
-
-// No contraction here: these are the separate CuPy ufunc roundings of methodsIR_CuPy.py:463-475,545-557.
+// The epilogues of the voxel-driven kernels: the loads and stores around bp_value (bp_common.h), which holds the arithmetic.
 template <int EPI>
 __device__ __forceinline__ void bp_epilogue(const BpArgs &a, size_t idx, float g)
 {
+    float o0 = 0.0f, o1 = 0.0f;
     if (EPI == EPI_PLAIN) {
         a.vol[idx] = g;
     } else if (EPI == EPI_FISTA) {
-        float x = a.xt[idx] - a.s0 * g;
-        if (a.nonneg) x = x < 0.0f ? 0.0f : x;
-        a.xout[idx] = x;
+        bp_value<EPI>(a, g, a.xt[idx], 0.0f, 0.0f, o0, o1);
+        a.xout[idx] = o0;
     } else if (EPI == EPI_FISTA_MOM) {
-        float x = a.xt[idx] - a.s0 * g;
-        if (a.nonneg) x = x < 0.0f ? 0.0f : x;
-        const float xo = a.xold[idx];
-        a.xout[idx] = x;
-        a.xt_out[idx] = x + a.s1 * (x - xo);
+        bp_value<EPI>(a, g, a.xt[idx], a.xold[idx], 0.0f, o0, o1);
+        a.xout[idx] = o0;
+        a.xt_out[idx] = o1;
     } else {
-        const float z0 = a.xout[idx], u = a.xold[idx];
-        const float ga = a.s1 * ((z0 - a.xt[idx]) + u);
-        float z = z0 - a.s0 * (g + ga);
-        if (a.nonneg) z = z < 0.0f ? 0.0f : z;
-        if (a.relax_on) z = a.s2 * z0 + a.s3 * z;
-        a.xout[idx] = z;
-        a.xt_out[idx] = z + u;
+        bp_value<EPI>(a, g, a.xout[idx], a.xold[idx], a.xt[idx], o0, o1);
+        a.xout[idx] = o0;
+        a.xt_out[idx] = o1;
     }
 }
 
 // the same epilogues on four consecutive voxels of a row (idx a multiple of 4, 16-byte aligned arrays): one dwordx4 access
-// per array instead of four dword accesses; the arithmetic per voxel is that of bp_epilogue
+// per array instead of four dword accesses
 template <int EPI>
-__device__ __forceinline__ void bp_epilogue4(const BpArgs &a, size_t idx, float4 g)
+__device__ __forceinline__ void bp_epilogue4(const BpArgs &a, size_t idx, float4 g4)
 {
     // The epilogue's volume streams are touched once (X_t read, X written: 8.6 GB through a 4 MB L2 per 1024^3 call) while the
     // sinogram windows of a z-brick (4.9 MB) are re-read by every brick of the XCD: with ordinary loads / stores the streams
     // evict the windows and the L2 re-fetches them ~33 x from the fabric (14.6 GB per call); marked NON-TEMPORAL they leave the
     // windows resident -- fetch 14.6 -> 4.9 GB (X_t + 1.8 x the subset), call 7.09 -> 6.90 ms (profiles/r5i_bp_epilogue_nontemporal_ab.txt).
-#ifndef TOMO_BP_EPI_TEMPORAL   // (A/B builds only: tools/run_ab.sh)
-    typedef float v4 __attribute__((ext_vector_type(4)));
-    auto ld4 = [&](const float *p) {
-        const v4 t = __builtin_nontemporal_load(reinterpret_cast<const v4 *>(p + idx));
-        return make_float4(t.x, t.y, t.z, t.w);
-    };
-    auto st4 = [&](float *p, float4 v) { __builtin_nontemporal_store(v4{v.x, v.y, v.z, v.w}, reinterpret_cast<v4 *>(p + idx)); };
-#else
-    auto ld4 = [&](const float *p) { return *reinterpret_cast<const float4 *>(p + idx); };
-    auto st4 = [&](float *p, float4 v) { *reinterpret_cast<float4 *>(p + idx) = v; };
-#endif
-    const float gv[4] = {g.x, g.y, g.z, g.w};
+    auto ld4 = [&](const float *p) { return __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p + idx)); };
+    auto st4 = [&](float *p, v4f v) { __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(p + idx)); };
+    const v4f g = v4f{g4.x, g4.y, g4.z, g4.w}, zero = v4f{0.0f, 0.0f, 0.0f, 0.0f};
     if (EPI == EPI_PLAIN) {
         st4(a.vol, g);
-    } else if (EPI == EPI_FISTA) {
-        const float4 t4 = ld4(a.xt);
-        const float tv[4] = {t4.x, t4.y, t4.z, t4.w};
-        float o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float x = tv[k] - a.s0 * gv[k];
-            if (a.nonneg) x = x < 0.0f ? 0.0f : x;
-            o[k] = x;
-        }
-        st4(a.xout, make_float4(o[0], o[1], o[2], o[3]));
-    } else if (EPI == EPI_FISTA_MOM) {
-        const float4 t4 = ld4(a.xt), o4 = ld4(a.xold);
-        const float tv[4] = {t4.x, t4.y, t4.z, t4.w}, ov[4] = {o4.x, o4.y, o4.z, o4.w};
-        float o[4], m[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float x = tv[k] - a.s0 * gv[k];
-            if (a.nonneg) x = x < 0.0f ? 0.0f : x;
-            o[k] = x;
-            m[k] = x + a.s1 * (x - ov[k]);
-        }
-        st4(a.xout, make_float4(o[0], o[1], o[2], o[3]));
-        st4(a.xt_out, make_float4(m[0], m[1], m[2], m[3]));
-    } else {
-        const float4 z4 = ld4(a.xout), u4 = ld4(a.xold), t4 = ld4(a.xt);
-        const float zv[4] = {z4.x, z4.y, z4.z, z4.w}, uv[4] = {u4.x, u4.y, u4.z, u4.w}, tv[4] = {t4.x, t4.y, t4.z, t4.w};
-        float o[4], m[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float ga = a.s1 * ((zv[k] - tv[k]) + uv[k]);
-            float z = zv[k] - a.s0 * (gv[k] + ga);
-            if (a.nonneg) z = z < 0.0f ? 0.0f : z;
-            if (a.relax_on) z = a.s2 * zv[k] + a.s3 * z;
-            o[k] = z;
-            m[k] = z + uv[k];
-        }
-        st4(a.xout, make_float4(o[0], o[1], o[2], o[3]));
-        st4(a.xt_out, make_float4(m[0], m[1], m[2], m[3]));
+        return;
     }
+    v4f i0 = zero, i1 = zero, i2 = zero, o0 = zero, o1 = zero;
+    if (EPI == EPI_FISTA) {
+        i0 = ld4(a.xt);
+    } else if (EPI == EPI_FISTA_MOM) {
+        i0 = ld4(a.xt); i1 = ld4(a.xold);
+    } else {
+        i0 = ld4(a.xout); i1 = ld4(a.xold); i2 = ld4(a.xt);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float p = 0.0f, r = 0.0f;
+        bp_value<EPI>(a, g[k], i0[k], i1[k], i2[k], p, r);
+        o0[k] = p; o1[k] = r;
+    }
+    st4(a.xout, o0);
+    if (EPI != EPI_FISTA) st4(a.xt_out, o1);
 }
 
 // ------------------------------------------------------------------------------------------ BP variant 1
@@ -351,13 +284,7 @@ int bp_launch(BpArgs a, bool lerp8, hipStream_t st)
 {
     TOMO_ON_DEVICE(a.device);
     tomo_prof_scope prof(PROF_BP, st, 1);
-    {
-        uintptr_t bits = 0;
-        if (EPI == EPI_PLAIN) bits |= (uintptr_t)a.vol;
-        else bits |= (uintptr_t)a.xt | (uintptr_t)a.xout;
-        if (EPI == EPI_FISTA_MOM || EPI == EPI_ADMM) bits |= (uintptr_t)a.xt_out | (uintptr_t)a.xold;
-        a.epi_aligned = (bits & 15) == 0;
-    }
+    a.epi_aligned = bp_epi_aligned<EPI>(a);
     // the brick kernel addresses a 16-slice sinogram slab with 32-bit element offsets
     // (the quad layout is read through one buffer descriptor per z-brick and batch: 4 quads x 16 bytes < 2^31)
     if (EPI == EPI_PLAIN) a.zquad = 0;  // tomo_bp3d always takes the public layout
@@ -484,26 +411,11 @@ __device__ __forceinline__ float fp_residual_value(const Args &a, float val, int
     return robust_weight(val, a.robust, a.rdelta);
 }
 
-__global__ __launch_bounds__(256) void transpose_inplane_kernel(const float *__restrict__ in, float *__restrict__ out, int n)
-{
-    __shared__ float t[32][33];
-    const size_t zoff = (size_t)blockIdx.z * n * n;
-    const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
-    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;  // 32 x 8
-    for (int r = ly; r < 32; r += 8) {
-        const int x = bx + lx, y = by + r;
-        t[r][lx] = (x < n && y < n) ? in[zoff + (size_t)y * n + x] : 0.0f;
-    }
-    __syncthreads();
-    for (int r = ly; r < 32; r += 8) {
-        const int y = by + lx, x = bx + r;
-        if (x < n && y < n) out[zoff + (size_t)x * n + y] = t[lx][r];
-    }
-}
-
 // X_t = X + beta (X - X_old) (the momentum step of methodsIR_CuPy.py:475: mul then add, no fma) written twice: as is,
 // and in-plane transposed into the forward projector's scratch copy -- the next forward projection of X_t then needs no
-// transpose pass of its own (one read of X_t saved per sub-iteration)
+// transpose pass of its own (one read of X_t saved per sub-iteration).  MOMENTUM = false: the plain in-plane transpose of x
+// into xt_T (xold, xt and beta unused).
+template <bool MOMENTUM>
 __global__ __launch_bounds__(256) void momentum_transpose_kernel(const float *__restrict__ x, const float *__restrict__ xold,
                                                                 float *__restrict__ xt, float *__restrict__ xt_T, float beta, int n)
 {
@@ -516,9 +428,11 @@ __global__ __launch_bounds__(256) void momentum_transpose_kernel(const float *__
         float v = 0.0f;
         if (xx < n && yy < n) {
             const size_t i = zoff + (size_t)yy * n + xx;
-            const float a = x[i];
-            v = a + beta * (a - xold[i]);
-            xt[i] = v;
+            v = x[i];
+            if (MOMENTUM) {
+                v = v + beta * (v - xold[i]);
+                xt[i] = v;
+            }
         }
         t[r][lx] = v;
     }
@@ -529,7 +443,7 @@ __global__ __launch_bounds__(256) void momentum_transpose_kernel(const float *__
     }
 }
 
-// The same two kernels on 64 x 64 tiles with 16-byte accesses (round 5): a wave reads four whole 256-byte row segments per
+// The same kernel on 64 x 64 tiles with 16-byte accesses (round 5): a wave reads four whole 256-byte row segments per
 // instruction instead of two 128-byte ones, and the transposed tile leaves as float4 along y.  Needs n % 4 == 0 and 16-byte
 // aligned arrays (the launchers fall back to the 32 x 32 dword kernels otherwise).  MOMENTUM = false: plain in-plane transpose.
 // LDS tile [64][65]: the transposed read of lane (c, r) touches bank (4c + j + r) mod 64 -- conflict-free for every j.
@@ -709,12 +623,29 @@ __global__ __launch_bounds__(256) void fp_march_kernel(FpArgs a)
 
 #include "fp_tiled.inl"
 
-// the context's in-plane transposed volume copy (x-stepping angles read it), grow-only
-int fp_scratch(tomo_ctx *ctx)
+// The transposed-copy token: `of`'s in-plane transposed copy (quad-interleaved or planar) is in the context's scratch, good
+// for exactly the next forward projection of `of` on stream `st`.
+void volT_publish(tomo_ctx *ctx, const float *of, hipStream_t st, bool quad)
 {
-    const size_t need = (size_t)ctx->nz * ctx->n * ctx->n * sizeof(float);
+    ctx->volT_of = of;
+    ctx->volT_stream = st;
+    ctx->volT_quad = quad;
+    ctx->volT_valid = true;
+}
+
+void volT_revoke(tomo_ctx *ctx)
+{
+    ctx->volT_valid = false;
+    ctx->volT_of = nullptr;
+}
+
+// the context's in-plane transposed volume copy (x-stepping angles read it), grow-only: `slices` slices of the volume (nz, or
+// whole quads for the quad-interleaved copy)
+int fp_scratch(tomo_ctx *ctx, int slices)
+{
+    const size_t need = (size_t)slices * ctx->n * ctx->n * sizeof(float);
     if (ctx->scratch_bytes < need) {
-        ctx->volT_valid = false;
+        volT_revoke(ctx);
         if (ctx->scratch) { TOMO_HIP(hipDeviceSynchronize()); TOMO_HIP(hipFree(ctx->scratch)); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
         TOMO_HIP(hipMalloc(&ctx->scratch, need));
         ctx->scratch_bytes = need;
@@ -1103,14 +1034,13 @@ int fp_run(tomo_ctx *ctx, int subset, const float *vol, const float *b, const fl
     TOMO_REQUIRE(ctx != nullptr, "ctx is NULL");
     TOMO_REQUIRE(vol != nullptr && out != nullptr, "NULL data pointer");
     TOMO_REQUIRE(subset < ctx->os, "subset %d out of range (OS_number %d)", subset, ctx->os);
-    const tomo_subset &s = (subset < 0 || ctx->os == 1) ? ctx->subsets[0] : ctx->subsets[1 + subset];
+    const tomo_subset &s = *find_subset(ctx, subset);
     hipStream_t st = as_stream(stream);
     // the transposed copy tomo_momentum_transposed left behind is a ONE-SHOT token: whatever this call does with it
     // (use it, find it belongs to another volume / stream, return early), it is spent before anything else happens
     const bool ready = ctx->volT_valid && ctx->volT_of == vol && ctx->volT_stream == st && ctx->scratch != nullptr &&
                        ctx->volT_quad == (volq != 0);
-    ctx->volT_valid = false;
-    ctx->volT_of = nullptr;
+    volT_revoke(ctx);
     if (s.size == 0) return TOMO_OK;
     TOMO_ON_DEVICE(ctx->device);
     // fp variant 5 (both flavours) only makes tomo_ctx_volume_zquad_ok say no, so that a driver keeps the planar volume (A/B)
@@ -1126,7 +1056,7 @@ int fp_run(tomo_ctx *ctx, int subset, const float *vol, const float *b, const fl
                                              "tomo_volume_to_zquad wrote it on the same stream");
         a.volT = (const float *)ctx->scratch;
     } else if (s.n_dirx > 0) {
-        int rc = fp_scratch(ctx);
+        int rc = fp_scratch(ctx, ctx->nz);
         if (rc != TOMO_OK) return rc;
         // tomo_momentum_transposed has just written this volume's transposed copy: use it once, skip the pass
         if (!ready) {
@@ -1135,7 +1065,7 @@ int fp_run(tomo_ctx *ctx, int subset, const float *vol, const float *b, const fl
                 transpose64_kernel<false><<<tg, 256, 0, st>>>(vol, nullptr, nullptr, (float *)ctx->scratch, 0.0f, ctx->n);
             } else {
                 dim3 tg(ceil_div(ctx->n, 32), ceil_div(ctx->n, 32), ctx->nz);
-                transpose_inplane_kernel<<<tg, 256, 0, st>>>(vol, (float *)ctx->scratch, ctx->n);
+                momentum_transpose_kernel<false><<<tg, 256, 0, st>>>(vol, nullptr, nullptr, (float *)ctx->scratch, 0.0f, ctx->n);
             }
             TOMO_LAUNCH_CHECK();
         }
@@ -1192,21 +1122,6 @@ int fp_run(tomo_ctx *ctx, int subset, const float *vol, const float *b, const fl
         TOMO_LAUNCH_CHECK();
         ctx->last_fp_path += fp_path_text(l);
     }
-    return TOMO_OK;
-}
-
-int bp_prepare(tomo_ctx *ctx, int subset, const float *sino, BpArgs &a)
-{
-    TOMO_REQUIRE(ctx != nullptr, "ctx is NULL");
-    TOMO_REQUIRE(subset < ctx->os, "subset %d out of range (OS_number %d)", subset, ctx->os);
-    const tomo_subset &s = (subset < 0 || ctx->os == 1) ? ctx->subsets[0] : ctx->subsets[1 + subset];
-    TOMO_REQUIRE(sino != nullptr || s.size == 0, "NULL sinogram pointer");
-    a = BpArgs();
-    a.device = ctx->device;
-    a.path = &ctx->last_bp_path;
-    a.sino = sino;
-    a.tab = ctx->dev_table + s.table_offset;
-    a.nz = ctx->nz; a.n = ctx->n; a.nu = ctx->nu; a.na = s.size;
     return TOMO_OK;
 }
 
@@ -1299,7 +1214,7 @@ extern "C" int tomo_ctx_residual_layout(const tomo_ctx *ctx) { return ctx ? ctx-
 extern "C" size_t tomo_ctx_residual_elems(const tomo_ctx *ctx, int subset)
 {
     if (!ctx || subset >= ctx->os) return 0;
-    const tomo_subset &s = (subset < 0 || ctx->os == 1) ? ctx->subsets[0] : ctx->subsets[1 + subset];
+    const tomo_subset &s = *find_subset(ctx, subset);
     const size_t nzr = ctx->res_layout == TOMO_RESIDUAL_ZQUAD ? (size_t)ceil_div(ctx->nz, 4) * 4 : (size_t)ctx->nz;
     return nzr * (size_t)s.size * (size_t)ctx->nu;
 }
@@ -1311,8 +1226,7 @@ extern "C" int tomo_ctx_set_volume_layout(tomo_ctx *ctx, int layout)
     TOMO_REQUIRE(layout == TOMO_VOLUME_PLANAR || layout == TOMO_VOLUME_ZQUAD, "unknown volume layout %d", layout);
     TOMO_REQUIRE(layout == TOMO_VOLUME_PLANAR || ctx->n % 4 == 0, "the quad-interleaved volume needs a slice size that is a multiple of 4");
     ctx->vol_layout = layout;
-    ctx->volT_valid = false;   // a token of the other layout is worth nothing
-    ctx->volT_of = nullptr;
+    volT_revoke(ctx);   // a token of the other layout is worth nothing
     return TOMO_OK;
 }
 
@@ -1332,24 +1246,11 @@ extern "C" int tomo_ctx_volume_zquad_ok(const tomo_ctx *ctx, int subset)
 {
     if (!ctx || subset >= ctx->os || ctx->n % 4 != 0 || ceil_div(ctx->nz, 4) > 65535) return 0;
     if (g_variant_fp != 0 || (g_variant_bp != 0 && g_variant_bp != 3)) return 0;
-    const tomo_subset &s = (subset < 0 || ctx->os == 1) ? ctx->subsets[0] : ctx->subsets[1 + subset];
+    const tomo_subset &s = *find_subset(ctx, subset);
     if (s.size == 0 || (long)s.size * ctx->nu >= (1L << 25)) return 0;
     FpPlan plan;
     if (fp_plan(ctx, s, 0, plan, true) != TOMO_OK) return 0;
     return plan.qv ? 1 : 0;
-}
-
-// the in-plane transposed quad-interleaved copy lives in the context's scratch like the planar one (whole quads)
-static int fp_scratch_zquad(tomo_ctx *ctx)
-{
-    const size_t need = (size_t)ceil_div(ctx->nz, 4) * 4 * ctx->n * ctx->n * sizeof(float);
-    if (ctx->scratch_bytes < need) {
-        ctx->volT_valid = false;
-        if (ctx->scratch) { TOMO_HIP(hipDeviceSynchronize()); TOMO_HIP(hipFree(ctx->scratch)); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
-        TOMO_HIP(hipMalloc(&ctx->scratch, need));
-        ctx->scratch_bytes = need;
-    }
-    return TOMO_OK;
 }
 
 // x (planar), optionally with the momentum of xold, -> xq and the transposed token in the context's scratch
@@ -1360,16 +1261,13 @@ static int volume_zquad_produce(tomo_ctx *ctx, const float *x_dev, const float *
     const int nq = ceil_div(ctx->nz, 4);
     TOMO_REQUIRE(nq <= 65535, "too many slices for one launch");
     TOMO_ON_DEVICE(ctx->device);
-    int rc = fp_scratch_zquad(ctx);
+    int rc = fp_scratch(ctx, 4 * nq);  // whole quads
     if (rc != TOMO_OK) return rc;
     dim3 tg(ceil_div(ctx->n, 64), ceil_div(ctx->n, 64), nq);
     if (xold_dev) zquad64_kernel<true><<<tg, 256, 0, as_stream(stream)>>>(x_dev, xold_dev, xq_dev, (float *)ctx->scratch, beta, ctx->n, ctx->nz);
     else zquad64_kernel<false><<<tg, 256, 0, as_stream(stream)>>>(x_dev, nullptr, xq_dev, (float *)ctx->scratch, 0.0f, ctx->n, ctx->nz);
     TOMO_LAUNCH_CHECK();
-    ctx->volT_of = xq_dev;
-    ctx->volT_stream = as_stream(stream);
-    ctx->volT_quad = true;
-    ctx->volT_valid = true;
+    volT_publish(ctx, xq_dev, as_stream(stream), true);
     return TOMO_OK;
 }
 
@@ -1385,28 +1283,24 @@ extern "C" int tomo_momentum_transposed(tomo_ctx *ctx, const float *x_dev, const
     TOMO_REQUIRE(ctx != nullptr && x_dev && xold_dev && xt_dev, "NULL argument");
     if (ctx->vol_layout == TOMO_VOLUME_ZQUAD) return volume_zquad_produce(ctx, x_dev, xold_dev, xt_dev, beta, stream);
     TOMO_ON_DEVICE(ctx->device);
-    int rc = fp_scratch(ctx);
+    int rc = fp_scratch(ctx, ctx->nz);
     if (rc != TOMO_OK) return rc;
     if (ctx->n % 4 == 0 && aligned16(x_dev, xold_dev, xt_dev, ctx->scratch)) {
         dim3 tg(ceil_div(ctx->n, 64), ceil_div(ctx->n, 64), ctx->nz);
         transpose64_kernel<true><<<tg, 256, 0, as_stream(stream)>>>(x_dev, xold_dev, xt_dev, (float *)ctx->scratch, beta, ctx->n);
     } else {
         dim3 tg(ceil_div(ctx->n, 32), ceil_div(ctx->n, 32), ctx->nz);
-        momentum_transpose_kernel<<<tg, 256, 0, as_stream(stream)>>>(x_dev, xold_dev, xt_dev, (float *)ctx->scratch, beta, ctx->n);
+        momentum_transpose_kernel<true><<<tg, 256, 0, as_stream(stream)>>>(x_dev, xold_dev, xt_dev, (float *)ctx->scratch, beta, ctx->n);
     }
     TOMO_LAUNCH_CHECK();
-    ctx->volT_of = xt_dev;
-    ctx->volT_stream = as_stream(stream);
-    ctx->volT_quad = false;
-    ctx->volT_valid = true;
+    volT_publish(ctx, xt_dev, as_stream(stream), false);
     return TOMO_OK;
 }
 
 extern "C" int tomo_ctx_invalidate(tomo_ctx *ctx)
 {
     TOMO_REQUIRE(ctx != nullptr, "ctx is NULL");
-    ctx->volT_valid = false;
-    ctx->volT_of = nullptr;
+    volT_revoke(ctx);
     return TOMO_OK;
 }
 
@@ -1420,13 +1314,13 @@ extern "C" int tomo_fp3d_residual_ring(tomo_ctx *ctx, int subset, const float *v
     return fp_run(ctx, subset, vol_dev, b_full_dev, nullptr, 0, TOMO_FID_LS, res_dev, stream, ring_dev, ring_scale);
 }
 
+// ---- the voxel-driven back projector's entry points: bp_prepare, the form's filler (bp_common.h), the layout flags, bp_launch
 extern "C" int tomo_bp3d(tomo_ctx *ctx, int subset, const float *sino_dev, float *vol_dev, void *stream)
 {
     BpArgs a;
     int rc = bp_prepare(ctx, subset, sino_dev, a);
+    if (rc == TOMO_OK) rc = bp_fill_plain(a, vol_dev);
     if (rc != TOMO_OK) return rc;
-    TOMO_REQUIRE(vol_dev != nullptr, "NULL volume pointer");
-    a.vol = vol_dev;
     return bp_launch<EPI_PLAIN>(a, (ctx->flags & TOMO_FLAG_LERP8) != 0, as_stream(stream));
 }
 
@@ -1435,9 +1329,8 @@ extern "C" int tomo_bp3d_fista(tomo_ctx *ctx, int subset, const float *res_dev, 
 {
     BpArgs a;
     int rc = bp_prepare(ctx, subset, res_dev, a);
+    if (rc == TOMO_OK) rc = bp_fill_fista(a, xt_dev, xout_dev, l_inv, nonneg);
     if (rc != TOMO_OK) return rc;
-    TOMO_REQUIRE(xt_dev && xout_dev, "NULL volume pointer");
-    a.xt = xt_dev; a.xout = xout_dev; a.s0 = l_inv; a.nonneg = nonneg;
     a.zquad = ctx->res_layout == TOMO_RESIDUAL_ZQUAD;
     a.xt_zquad = ctx->vol_layout == TOMO_VOLUME_ZQUAD;
     return bp_launch<EPI_FISTA>(a, (ctx->flags & TOMO_FLAG_LERP8) != 0, as_stream(stream));
@@ -1448,11 +1341,9 @@ extern "C" int tomo_bp3d_fista_momentum(tomo_ctx *ctx, int subset, const float *
 {
     BpArgs a;
     int rc = bp_prepare(ctx, subset, res_dev, a);
+    if (rc == TOMO_OK) rc = bp_fill_fista_momentum(a, xt_dev, xold_x_dev, l_inv, beta, nonneg);
     if (rc != TOMO_OK) return rc;
-    TOMO_REQUIRE(xt_dev && xold_x_dev, "NULL volume pointer");
     TOMO_REQUIRE(ctx->vol_layout == TOMO_VOLUME_PLANAR, "the fused gradient step + momentum takes the planar volume: set TOMO_VOLUME_PLANAR first");
-    a.xt = xt_dev; a.xt_out = xt_dev; a.xold = xold_x_dev; a.xout = xold_x_dev;
-    a.s0 = l_inv; a.s1 = beta; a.nonneg = nonneg;
     a.zquad = ctx->res_layout == TOMO_RESIDUAL_ZQUAD;
     return bp_launch<EPI_FISTA_MOM>(a, (ctx->flags & TOMO_FLAG_LERP8) != 0, as_stream(stream));
 }
@@ -1463,12 +1354,9 @@ extern "C" int tomo_bp3d_admm(tomo_ctx *ctx, int subset, const float *res_dev, f
 {
     BpArgs a;
     int rc = bp_prepare(ctx, subset, res_dev, a);
+    if (rc == TOMO_OK) rc = bp_fill_admm(a, z_dev, x_dev, u_dev, zu_out_dev, tau, rho, relax_on, one_minus_alpha, alpha, nonneg);
     if (rc != TOMO_OK) return rc;
-    TOMO_REQUIRE(z_dev && x_dev && u_dev && zu_out_dev, "NULL volume pointer");
     TOMO_REQUIRE(ctx->vol_layout == TOMO_VOLUME_PLANAR, "the ADMM z-update takes the planar volume: set TOMO_VOLUME_PLANAR first");
-    a.xt = x_dev; a.xout = z_dev; a.xt_out = zu_out_dev; a.xold = u_dev;
-    a.s0 = tau; a.s1 = rho; a.s2 = one_minus_alpha; a.s3 = alpha;
-    a.nonneg = nonneg; a.relax_on = relax_on;
     a.zquad = ctx->res_layout == TOMO_RESIDUAL_ZQUAD;
     return bp_launch<EPI_ADMM>(a, (ctx->flags & TOMO_FLAG_LERP8) != 0, as_stream(stream));
 }

@@ -247,14 +247,6 @@ extern "C" int tomo_ctx_newind_table(const tomo_ctx *ctx, int64_t *out_host)
     return TOMO_OK;
 }
 
-static const tomo_subset *find_subset(const tomo_ctx *ctx, int subset)
-{
-    if (!ctx) return nullptr;
-    if (subset < 0 || ctx->os == 1) return &ctx->subsets[0];
-    if (subset >= ctx->os) return nullptr;
-    return &ctx->subsets[1 + subset];
-}
-
 extern "C" int tomo_ctx_subset_size(const tomo_ctx *ctx, int subset)
 {
     const tomo_subset *s = find_subset(ctx, subset);

@@ -74,6 +74,15 @@ struct tomo_ctx {
     int res_layout = 0;                       // TOMO_RESIDUAL_*: layout of the residual between tomo_fp3d_residual and tomo_bp3d_fista* / _admm
 };
 
+// subset < 0, or a context without ordered subsets: the full angle set; null when there is no such subset
+static inline const tomo_subset *find_subset(const tomo_ctx *ctx, int subset)
+{
+    if (!ctx) return nullptr;
+    if (subset < 0 || ctx->os == 1) return &ctx->subsets[0];
+    if (subset >= ctx->os) return nullptr;
+    return &ctx->subsets[1 + subset];
+}
+
 // one message per process and key on stderr (a slow fallback kernel was taken)
 void tomo_warn_once(const char *key, const char *msg);
 

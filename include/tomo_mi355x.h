@@ -32,7 +32,8 @@ extern "C" {
  * binds every symbol by name at load, so a library without them is refused all the same.  The three tomo_llt_rof* entry
  * points joined it the same way, for the same reason.  So did the four tomo_wavelet_* entry points, and tomo_halo_pack2 /
  * tomo_halo_pull2 with the four tomo_ipc_region_* entry points, and tomo_nltv_scratch_bytes, tomo_patch_select and
- * tomo_nltv, and the five entry points of the private volume layout (TOMO_VOLUME_ZQUAD below). */
+ * tomo_nltv, and the five entry points of the private volume layout (TOMO_VOLUME_ZQUAD below), and the four tomo_pdhg_* entry
+ * points (tests/test_matched_bp_oracle.py pins the number 10 as well). */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -395,6 +396,34 @@ size_t tomo_roftv_slices_scratch_bytes(int dx, int dy, int nslices);
 int tomo_tgv(int device, const float *in_dev, float *out_dev, int dx, int dy, int dz, int nd,
              float lambda, float alpha1, float alpha0, float tau, float sigma, int iters,
              double tol, int *iters_done, double *last_rel_change, void *stream);
+/* The launches of PDHG (primal-dual hybrid gradient, Chambolle-Pock, on min_x F(Ax) + lambda TV(x) itself) beside the
+ * forward projector and the matched back projector: RecToolsIRCuPy.PDHG runs, per iteration, tomo_fp3d on x-bar,
+ * tomo_pdhg_sino_dual, tomo_bp3d_matched, tomo_pdhg_tv_dual, tomo_pdhg_primal.  No reference counterpart: the algorithm is
+ * stated in docs/kernels/pdhg.md and restated in numpy by tests/_pdhg_oracle.py -- formula-level parity, unpinned; the
+ * float32 results equal that restatement bit for bit.  All scalars are float32 values computed by the caller.
+ *   tomo_pdhg_sino_dual: y <- prox of the conjugate of the data term, element-wise over `count` samples, in place; r = A x-bar,
+ *     b = the data.  TOMO_PDHG_LS: (y + sigma (r - b)) / (1 + sigma); TOMO_PDHG_L1: the same ascent clipped to [-1, 1];
+ *     TOMO_PDHG_KL: v = y + sigma r, y = 0.5 ((1 + v) - sqrt((v - 1)^2 + 4 sigma max(b, 0))).  16-byte accesses when the
+ *     three arrays are 16-byte aligned, with a scalar tail.  TOMO_E_INVALID: an unknown term, a non-positive sigma, NULL,
+ *     y aliasing r or b.
+ *   tomo_pdhg_tv_dual: q_d <- q_d + sigma F_d(x-bar) (forward differences, 0 on the last index), then q / max(1, |q| /
+ *     lambda) (methodTV 0) or the clip to [-lambda, lambda] (methodTV 1), in place.  dims as for tomo_pdtv (a dimension of
+ *     1 is valid); nd = 2 ignores dz and q3_dev.
+ *   tomo_pdhg_primal: x' = x - tau (g - div q), div q = (B_1 q1 + B_2 q2) + B_3 q3 (backward differences), clamped at 0
+ *     with nonneg; x-bar <- (x' + x') - x, x <- x', in place.  q1_dev = q2_dev = q3_dev = NULL: no TV block, div q = 0.
+ *   Both marches: TOMO_E_INVALID for nd outside {2, 3}, a dimension below 1, a non-positive step size or lambda, NULL or
+ *     aliasing arrays.  One launch each.
+ *   tomo_pdhg_scratch_bytes: 2 + nd float arrays (x-bar, g, q_1..q_nd), each rounded up to 256 bytes and followed by the
+ *     69888-byte array skew -- the layout of a tomo_placed_scratch block the driver takes them from. */
+enum { TOMO_PDHG_LS = 0, TOMO_PDHG_L1 = 1, TOMO_PDHG_KL = 2 };
+size_t tomo_pdhg_scratch_bytes(int dx, int dy, int dz, int nd);
+int tomo_pdhg_sino_dual(float *y_dev, const float *r_dev, const float *b_dev, size_t count, int fidelity, float sigma,
+                        void *stream);
+int tomo_pdhg_tv_dual(int device, const float *xbar_dev, float *q1_dev, float *q2_dev, float *q3_dev, int dx, int dy,
+                      int dz, int nd, float sigma, float lambda, int methodTV, void *stream);
+int tomo_pdhg_primal(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *q1_dev,
+                     const float *q2_dev, const float *q3_dev, int dx, int dy, int dz, int nd, float tau, int nonneg,
+                     void *stream);
 /* Nonlinear diffusion (NDF) by explicit time marching: U^0 = in, n times
  *     U' = U + tau (lambda S - (U - in)),   S = sum over the axes of g(U[i + e] - U[i]) + g(U[i - e] - U[i]),
  * with zero flux through the faces of the volume and the flux g chosen by `penalty`:

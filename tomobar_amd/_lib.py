@@ -23,6 +23,7 @@ ROBUST = {None: 0, "huber": 1, "studentst": 2}   # TOMO_ROBUST_* of include/tomo
 RESIDUAL_LAYOUT = {"planar": 0, "zquad": 1}   # TOMO_RESIDUAL_* of include/tomo_mi355x.h
 VOLUME_LAYOUT = {"planar": 0, "zquad": 1}     # TOMO_VOLUME_* of include/tomo_mi355x.h
 NDF_PENALTY = {"Huber": 0, "PM": 1, "Tukey": 2}   # TOMO_NDF_* of include/tomo_mi355x.h
+PDHG_FID = {"LS": 0, "L1": 1, "KL": 2}            # TOMO_PDHG_* of include/tomo_mi355x.h
 
 
 def ndf_penalty_id(penalty_type) -> int:
@@ -115,6 +116,10 @@ SIGNATURES = {
     "tomo_roftv_slices_scratch_bytes": (_sz, [_i, _i, _i]),
     "tomo_tgv": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
     "tomo_tgv_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_pdhg_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_pdhg_sino_dual": (_i, [_vp, _vp, _vp, _sz, _i, _f, _vp]),
+    "tomo_pdhg_tv_dual": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "tomo_pdhg_primal": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "tomo_ndf": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
     "tomo_ndf_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_diff4th": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),

@@ -74,7 +74,7 @@ class _RunMonitor:
 
 
 class RecToolsIRCuPy:
-    """Iterative reconstruction algorithms (FISTA, ADMM, OSEM, SIRT, CGLS, Landweber, power method).
+    """Iterative reconstruction algorithms (FISTA, ADMM, PDHG, OSEM, SIRT, CGLS, Landweber, power method).
 
     Args:
         DetectorsDimH (int): Horizontal detector dimension size.
@@ -207,7 +207,9 @@ class RecToolsIRCuPy:
         use_os = self.OS_number > 1
         w = ops.pwls_weights(d["projection_data"], self.slab) if _data_["data_fidelity"] in ["PWLS", "SWLS"] else None
         # the TV operators' scratch arena is allocated and placed here, at set-up, not inside the first proximal step
-        reserve_prox_scratch(self, rec_dim, r)
+        # (PDHG runs no prox: its work arrays are a placed block of its own)
+        if method_run != "PDHG":
+            reserve_prox_scratch(self, rec_dim, r)
         return (d, a, r, x0, w, use_os)
 
     # ------------------------------------------------------------------ power method
@@ -394,6 +396,67 @@ class RecToolsIRCuPy:
                     break
         finally:
             A.set_residual_layout("planar")
+        return self._finalise(x, a)
+
+    # ------------------------------------------------------------------ PDHG
+    def PDHG(self, _data_: dict, _algorithm_: Union[dict, None] = None,
+             _regularisation_: Union[dict, None] = None) -> torch.Tensor:
+        """Primal-dual hybrid gradient (Chambolle-Pock) on  min_x F(Ax) + lambda TV(x)  itself (no reference counterpart in
+        this reference version; the algorithm is stated in docs/kernels/pdhg.md, formula-level parity, unpinned).
+        ``_data_["data_fidelity"]`` is "LS", "KL" or "L1" -- the non-smooth terms exactly, no re-weighting and no clamp of
+        Ax --, ``_regularisation_["method"]`` None or "PD_TV": the TV term sits in the dual of the outer problem, so an
+        iteration is one forward projection, one matched back projection and one stencil pass, with no inner loop.
+        ``_algorithm_["PDHG_ratio"]`` is sigma / tau (default 1).  Needs ``adjoint="matched"``; no ordered subsets, no
+        z-slabs.  Returns the float32 volume ``[detY, N, N]``."""
+        (d, a, r, x, _, _) = self.__common_initialisation(_data_, _algorithm_, _regularisation_, "PDHG")
+        A = self.Atools
+        b = d["projection_data"]
+        fid = self.data_fidelity
+        nonneg = bool(a["nonnegativity"])
+        has_tv = r.get("method") is not None
+        nd = 3 if A.vol_shape()[0] > 1 else 2
+
+        # the step sizes, float32 throughout: sigma tau L_K = 0.95^2 with L_K = |A|^2 + |grad|^2 <= L_A + 4 nd
+        L_K = float32(a["lipschitz_const"])
+        if has_tv:
+            L_K = L_K + float32(4 * nd)
+        s = float32(0.95) / np.sqrt(L_K)
+        rho = float32(a["PDHG_ratio"])
+        sigma, tau = s * rho, s / rho
+        lam = float32(r["regul_param"]) if has_tv else None
+
+        # x-bar, g = A^T y and the TV dual live in a placed block of their own; the projector calls see ordinary tensors
+        xbar, g, q, _ = ops.pdhg_work_arrays(A.vol_shape(), A._device, has_tv)
+        xbar.copy_(x)
+        for field in q:
+            ops.fill(field, 0.0)
+        y = torch.empty_like(b)
+        ops.fill(y, 0.0)
+        proj = torch.empty_like(b)
+
+        planar_volume = getattr(A, "set_volume_layout", None)
+        A.invalidate()
+        A.set_residual_layout("planar")
+        if planar_volume is not None:
+            planar_volume("planar")
+        mon = _RunMonitor(self, "PDHG", a, x)
+        try:
+            for k in range(a["iterations"]):
+                A.forward(xbar, None, out=proj)
+                ops.pdhg_sino_dual(y, proj, b, fid, sigma)
+                A.backward(y, None, out=g)
+                if has_tv:
+                    ops.pdhg_tv_dual(xbar, q, sigma, lam, r["methodTV"])
+                ops.pdhg_primal(x, xbar, g, q, tau, nonneg)
+                if a["verbose"] and np.mod(k, (round)(a["iterations"] / 5) + 1) == 0:
+                    print("PDHG iteration (", k + 1, ") using", r.get("method"), "regularisation")
+                if mon.stop(k + 1, x):
+                    break
+        finally:
+            A.set_residual_layout("planar")
+            if planar_volume is not None:
+                planar_volume("planar")
+            A.invalidate()
         return self._finalise(x, a)
 
     # ------------------------------------------------------------------ simple iterative methods (SURVEY 8f-2)

@@ -334,6 +334,73 @@ def llt_rof(data, out, lam_rof, lam_llt, tau, iterations, tolerance=0.0):
     return _marched("tomo_llt_rof", data, out, (lam_rof, lam_llt, tau), iterations, tolerance)
 
 
+# ----------------------------------------------------------------------------- PDHG (docs/kernels/pdhg.md)
+PDHG_SLOT = 5   # the placed block of the PDHG driver's work arrays (slots 0-4: the slab drivers, supp/regularisers.py)
+
+
+def pdhg_work_arrays(shape, device, tv: bool = True):
+    """The work arrays of one PDHG call on a volume of `shape` ([nz, ny, nx]), uninitialised, from the placed block of
+    ``PDHG_SLOT``: (x-bar, g, [q_1 .. q_nd]) and the lease token of ``placed_empty``; nd = 3 if nz > 1 else 2, no q without
+    the TV block.  With it the block has the size ``tomo_pdhg_scratch_bytes`` states."""
+    nd = 3 if shape[0] > 1 else 2
+    arrays, lease = placed_empty([(tuple(shape), torch.float32)] * (2 + (nd if tv else 0)), device, slot=PDHG_SLOT)
+    return arrays[0], arrays[1], arrays[2:], lease
+
+
+def _pdhg_dims(t):
+    """(dx, dy, dz, nd) of a volume [nz, ny, nx]: nd = 3 if nz > 1 else 2 (a dimension of 1 elsewhere stays 3D)"""
+    _chk_f32(t, "volume")
+    if t.dim() != 3:
+        raise ValueError("PDHG volumes are [nz, ny, nx] arrays")
+    return t.shape[2], t.shape[1], t.shape[0], 3 if t.shape[0] > 1 else 2
+
+
+def pdhg_sino_dual(y, r, b, fidelity: str, sigma):
+    """Step 2 of a PDHG iteration (tomo_pdhg_sino_dual): the sinogram dual `y` <- the prox of the conjugate of the data term
+    `fidelity` ("LS", "L1" or "KL") at y + sigma r, in place; `r` = A x-bar, `b` = the data, `sigma` a float32 scalar."""
+    if fidelity not in L.PDHG_FID:
+        raise ValueError(f"unknown PDHG data term {fidelity!r}: LS, L1 and KL are supported")
+    for name, t in (("y", y), ("r", r), ("b", b)):
+        _chk_f32(t, name)
+        if t.numel() != y.numel() or t.device != y.device:
+            raise ValueError(f"{name} must have the size and the device of y")
+    with _on(y):
+        L.check(L.lib().tomo_pdhg_sino_dual(ptr(y), ptr(r), ptr(b), y.numel(), L.PDHG_FID[fidelity], float(sigma), stream_ptr(y)))
+    return y
+
+
+def _pdhg_fields(x, named):
+    for name, t in named:
+        _chk_f32(t, name)
+        if tuple(t.shape) != tuple(x.shape) or t.device != x.device:
+            raise ValueError(f"{name} must have the shape and the device of the volume")
+
+
+def pdhg_tv_dual(xbar, q, sigma, lam, methodTV=0):
+    """Step 4 of a PDHG iteration (tomo_pdhg_tv_dual): q_d <- q_d + sigma F_d(x-bar), projected (methodTV 0: onto the ball of
+    radius `lam`, 1: onto the box), in place; `q` holds nd fields like `xbar`."""
+    dx, dy, dz, nd = _pdhg_dims(xbar)
+    if len(q) != nd:
+        raise ValueError(f"a volume of {dz} plane{'s' if dz > 1 else ''} takes {nd} dual fields, got {len(q)}")
+    _pdhg_fields(xbar, [(f"q{d + 1}", t) for d, t in enumerate(q)])
+    with _on(xbar):
+        L.check(L.lib().tomo_pdhg_tv_dual(xbar.device.index, ptr(xbar), ptr(q[0]), ptr(q[1]), ptr(q[2] if nd == 3 else None),
+                                          dx, dy, dz, nd, float(sigma), float(lam), int(methodTV), stream_ptr(xbar)))
+
+
+def pdhg_primal(x, xbar, g, q, tau, nonneg=False):
+    """Step 5 of a PDHG iteration (tomo_pdhg_primal): x' = x - tau (g - div q), clamped at 0 with `nonneg`; x-bar <- 2 x' - x,
+    x <- x', in place.  `q`: the nd dual fields, or an empty sequence for no TV block (div q = 0)."""
+    dx, dy, dz, nd = _pdhg_dims(x)
+    if len(q) not in (0, nd):
+        raise ValueError(f"a volume of {dz} plane{'s' if dz > 1 else ''} takes {nd} dual fields or none, got {len(q)}")
+    _pdhg_fields(x, [("xbar", xbar), ("g", g)] + [(f"q{d + 1}", t) for d, t in enumerate(q)])
+    qp = [ptr(t) for t in q] + [ptr(None)] * (3 - len(q))
+    with _on(x):
+        L.check(L.lib().tomo_pdhg_primal(x.device.index, ptr(x), ptr(xbar), ptr(g), qp[0], qp[1], qp[2], dx, dy, dz, nd,
+                                         float(tau), int(bool(nonneg)), stream_ptr(x)))
+
+
 def _wavelet_args(data, out, mix):
     _chk_f32(data, "data")
     if data.dim() not in (2, 3):
@@ -483,7 +550,7 @@ def placed_empty(specs, device, slot: int = 0):
     ``ARRAY_SKEW`` apart; a lease token).  The block belongs to the library (grow-only per (device, stream, slot), freed
     by ``tomo_release_scratch``): the tensors are views for the duration of ONE driver call, not allocations to keep, and
     a second ``placed_empty`` on the same (device, stream, slot) supersedes them -- ``lease_is_current(token)`` tells.
-    Slots in use: the ``slot`` of the records of tomobar_amd/supp/regularisers.py, one per slab driver."""
+    Slots in use: the ``slot`` of the records of tomobar_amd/supp/regularisers.py, one per slab driver, and ``PDHG_SLOT``."""
     device = torch.device(device)
     sizes, total = [], 0
     for shape, dtype in specs:

@@ -22,7 +22,7 @@ LABELS_2D = ["angles", "detX"]
 # default outer-iteration counts: method -> (classical, ordered-subsets)   (dicts.py:101-133)
 _DEFAULT_ITERATIONS = {
     "SIRT": (200, 200), "CGLS": (30, 30), "power": (15, 15), "Landweber": (1500, 1500),
-    "OSEM": (300, 15), "FISTA": (400, 20), "ADMM": (400, 10),
+    "OSEM": (300, 15), "FISTA": (400, 20), "ADMM": (400, 10), "PDHG": (500, 500),
 }
 _NO_OS_METHODS = {"SIRT", "CGLS", "Landweber"}
 _NO_LIPSCHITZ = {"SIRT", "CGLS", "power", "Landweber", "OSEM"}
@@ -68,6 +68,47 @@ def _nltv_keys(self, reg: dict) -> None:
             raise ValueError(f"_regularisation_['{NLTV_ITERATIONS}'] must not be negative")
 
 
+def _pdhg_refusals(self, _data_: dict) -> None:
+    """What PDHG (RecToolsIRCuPy.PDHG; docs/kernels/pdhg.md) cannot run on, as a ValueError before any projector call: an
+    unmatched operator pair (the iteration assumes the exact adjoint), ordered subsets, a z-slab, the weighted data terms,
+    the ring and robust keys."""
+    if getattr(self, "adjoint", None) != "matched":
+        raise ValueError("PDHG needs the exact adjoint of the forward projector: construct with adjoint=\"matched\"")
+    if self.OS_number > 1:
+        raise ValueError("There is no ordered-subsets implementation of PDHG, please set OS_number=None")
+    if getattr(self, "slab", None) is not None:
+        raise ValueError("PDHG is not available in z-slab mode")
+    if _data_["data_fidelity"] not in {"LS", "KL", "L1"}:
+        raise ValueError(f"PDHG supports the 'LS', 'KL' and 'L1' data fidelities, not {_data_['data_fidelity']!r}")
+    for key in ("ringGH_lambda", "huber_threshold", "studentst_threshold"):
+        if _data_.get(key) is not None:
+            raise ValueError(f"_data_['{key}'] is available in FISTA only (PDHG: the 'L1' data fidelity is the robust term)")
+
+
+def _pdhg_keys(_algorithm_: dict, _regularisation_: dict) -> None:
+    """PDHG's own keys: ``PDHG_ratio`` (sigma / tau, default 1.0, positive) and a regulariser that is None or exactly
+    "PD_TV" -- the same TV semi-norm, solved jointly in the dual, so only ``regul_param`` and ``methodTV`` are read (and
+    filled); no prox runs, hence no slice-wise or half-precision form."""
+    _algorithm_.setdefault("PDHG_ratio", 1.0)
+    if not float(_algorithm_["PDHG_ratio"]) > 0.0:
+        raise ValueError("_algorithm_['PDHG_ratio'] (sigma / tau) must be positive")
+    method = _regularisation_.get("method")
+    if method is None:
+        return
+    if method != "PD_TV":
+        raise ValueError(f"PDHG takes _regularisation_['method'] = None or 'PD_TV' (the TV term in its dual), not {method!r}")
+    if _regularisation_.get("slicewise", False) is not False:
+        raise ValueError("PDHG does not support slicewise=True")
+    if _regularisation_.get("half_precision", False):
+        raise ValueError("PDHG does not support half_precision=True")
+    _regularisation_.setdefault("regul_param", 0.001)
+    _regularisation_.setdefault("methodTV", 0)
+    if not float(_regularisation_["regul_param"]) > 0.0:
+        raise ValueError("_regularisation_['regul_param'] must be positive")
+    if _regularisation_["methodTV"] not in (0, 1):
+        raise ValueError("_regularisation_['methodTV'] must be 0 (isotropic) or 1 (anisotropic)")
+
+
 def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regularisation_: Optional[dict] = None,
                 method_run: str = "FISTA") -> tuple:
     """Populate the three dictionaries in place and return them (see module docstring)."""
@@ -92,8 +133,12 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
     # "SWLS" (stripe-weighted least squares) and the Group-Huber keys below are the ring-artefact data terms of the
     # reference's removed RecToolsIR class (docs/source/tutorials/real_data_recon.rst:100-151); the reference's current
     # dicts_check knows LS / PWLS / KL only
-    if _data_["data_fidelity"] not in {"LS", "PWLS", "KL", "SWLS"}:
+    # "L1" is PDHG's alone (docs/kernels/pdhg.md): the other drivers need a differentiable data term
+    if _data_["data_fidelity"] not in {"LS", "PWLS", "KL", "SWLS"} and not (
+            method_run == "PDHG" and _data_["data_fidelity"] == "L1"):
         raise ValueError("_data_['data_fidelity'] should be provided as 'LS', 'PWLS', 'KL' (or 'SWLS').")
+    if method_run == "PDHG":
+        _pdhg_refusals(self, _data_)
     self.data_fidelity = _data_["data_fidelity"]
     _data_.setdefault("ringGH_lambda", None)        # Group-Huber offsets: off unless a threshold is given
     _data_.setdefault("ringGH_accelerate", 50)
@@ -150,6 +195,8 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
         _regularisation_ = {}
     if not _regularisation_:
         _regularisation_["method"] = None
+    if method_run == "PDHG":   # before the prox methods' own checks: nothing but None / "PD_TV" gets that far
+        _pdhg_keys(_algorithm_, _regularisation_)
     nltv_check(_regularisation_)
     if is_nltv(_regularisation_.get("method")):   # before the defaults: "iterations" must still be the caller's own
         _nltv_keys(self, _regularisation_)

@@ -1,0 +1,125 @@
+"""Timing of RecToolsIRCuPy.PDHG (docs/kernels/pdhg.md: per iteration one forward projection, the sinogram dual, one matched
+back projection, the TV dual and the primal) on synthetic data.
+
+usage: python tools/pdhg_bench.py [--shapes 512:360,1024:900] [--fidelity LS] [--reps 5] [--short 4] [--long 14] [--out FILE]
+       python tools/pdhg_bench.py --kernel-db RESULTS.db [--out FILE]
+
+Per shape n:angles (an n^3 volume, n detector columns): one warm-up call, then `reps` pairs of calls with `short` and `long`
+iterations timed with device events; the time of one iteration is the median over the pairs of
+(t_long - t_short) / (long - short), which leaves the set-up of a call out.  The Lipschitz constant is given, so the power
+method is not part of a call.  One JSON line per shape, appended to profiles/pdhg_bench.jsonl.
+
+The split over the five launches comes from a run of its own under the profiler,
+    rocprofv3 --kernel-trace --stats -d DIR -o pdhg -- python tools/pdhg_bench.py --shapes 1024:900 --reps 1 --out /dev/null
+whose database the second form reads: per launch group the calls, the mean time and the share of the kernel time, and for
+the three new launches the rate over their algorithmic bytes (TV dual + primal: 28 + 28 B per voxel in 3D; the sinogram
+dual: 16 B per sample) against the plain-copy rate measured on this hardware (6.2 TB/s,
+profiles/archive/r4b_hbm_copy_probe.txt); give --shapes with the ONE shape the profiled run used."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+COPY_RATE_GBPS = 6200.0
+GROUPS = (("pdhg_sino", "sino_dual"), ("pdhg_dual", "tv_dual"), ("pdhg_primal", "primal"), ("bp_", "bp"), ("fp_", "fp"),
+          ("transpose64", "fp"))   # the in-plane transpose in front of the forward projector
+
+
+def bench(n, na, args):
+    import numpy as np
+    import torch
+    from tomobar_amd.methodsIR_CuPy import RecToolsIRCuPy
+    rt = RecToolsIRCuPy(n, 0, n, 0.0, np.linspace(0, np.pi, na, endpoint=False), n, 0, None, adjoint="matched")
+    gen = torch.Generator(device="cuda").manual_seed(3)
+    sino = torch.rand((n, na, n), device="cuda", generator=gen) * (0.5 * n)
+    reg = {"method": "PD_TV", "regul_param": 0.5, "methodTV": 0}
+    out = [None]
+
+    def run(iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out[0] = rt.PDHG({"projection_data": sino, "data_fidelity": args.fidelity},
+                         {"iterations": iters, "lipschitz_const": float(n) * na, "nonnegativity": True, "recon_mask_radius": None},
+                         dict(reg))
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    run(args.short)   # warm-up: code objects, the placed block
+    per_iter, calls = [], []
+    for _ in range(args.reps):
+        ts, tl = run(args.short), run(args.long)
+        per_iter.append((tl - ts) / (args.long - args.short))
+        calls.append(tl)
+    from tomobar_amd import ops
+    return {"op": "pdhg", "fidelity": args.fidelity, "n": n, "nz": n, "nu": n, "angles": na, "reps": args.reps,
+            "device": torch.cuda.get_device_name(0), "ms_per_iteration": round(statistics.median(per_iter), 3),
+            "ms_per_iteration_min_max": [round(min(per_iter), 3), round(max(per_iter), 3)],
+            f"ms_per_call_{args.long}_iterations": round(statistics.median(calls), 2),
+            "kernel_path": {"fp": rt.Atools.kernel_path("fp"), "bp": rt.Atools.kernel_path("bp")},
+            "finite": bool(torch.isfinite(out[0]).all()), "placement": ops.placement_last()}
+
+
+def split(db_path, n, na):
+    """the launch groups of a profiled run: calls, mean ms per launch, ms per iteration, share of the kernel time; rates of
+    the three new launches"""
+    import sqlite3
+    rows = sqlite3.connect(db_path).execute("select name, count(*), sum(duration) from kernels group by name").fetchall()
+    agg = {}
+    for name, calls, total in rows:
+        group = next((g for key, g in GROUPS if key in name), "other")
+        c, t = agg.get(group, (0, 0.0))
+        agg[group] = (c + calls, t + total / 1e6)
+    whole = sum(t for _, t in agg.values()) or 1.0
+    iterations = agg.get("primal", (1, 0.0))[0]   # one primal launch per iteration
+    line = {"op": "pdhg_split", "n": n, "angles": na, "iterations": iterations,
+            "groups": {g: {"calls": c, "mean_ms": round(t / c, 4), "ms_per_iteration": round(t / iterations, 3),
+                           "share": round(t / whole, 4)} for g, (c, t) in sorted(agg.items())}}
+    new = sum(agg.get(g, (0, 0.0))[1] for g in ("sino_dual", "tv_dual", "primal"))
+    line["share_of_the_three_new_launches"] = round(new / whole, 4)
+    nbytes = {"tv_dual": 28 * n ** 3, "primal": 28 * n ** 3, "sino_dual": 16 * n * n * na}
+    for g, b in nbytes.items():
+        if g in agg:
+            rate = b / (agg[g][1] / agg[g][0] * 1e-3) / 1e9
+            line["groups"][g].update(algorithmic_GBps=round(rate, 1), ratio_to_copy_rate_6200_GBps=round(rate / COPY_RATE_GBPS, 3))
+    return line
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="512:360,1024:900")
+    ap.add_argument("--fidelity", default="LS", choices=("LS", "L1", "KL"))
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--short", type=int, default=4)
+    ap.add_argument("--long", type=int, default=14)
+    ap.add_argument("--kernel-db", default=None, help="summarise the kernels table of a rocprofv3 --kernel-trace --stats run instead")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pdhg_bench.jsonl"))
+    args = ap.parse_args()
+    if not 0 < args.short < args.long or args.reps < 1:
+        ap.error("need 0 < --short < --long and --reps >= 1")
+    shapes = [tuple(int(v) for v in item.split(":")) for item in args.shapes.split(",")]
+    lines = []
+    if args.kernel_db:
+        if len(shapes) != 1:
+            ap.error("--kernel-db needs --shapes with the one shape the profiled run used")
+        lines.append(split(args.kernel_db, *shapes[0]))
+        print(json.dumps(lines[-1]), flush=True)
+    else:
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("pdhg_bench needs a GPU (there is no CPU path)")
+        for n, na in shapes:
+            lines.append(bench(n, na, args))
+            print(json.dumps(lines[-1]), flush=True)
+            torch.cuda.empty_cache()
+    with open(args.out, "a") as fh:
+        for line in lines:
+            fh.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()

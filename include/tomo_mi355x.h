@@ -33,7 +33,7 @@ extern "C" {
  * points joined it the same way, for the same reason.  So did the four tomo_wavelet_* entry points, and tomo_halo_pack2 /
  * tomo_halo_pull2 with the four tomo_ipc_region_* entry points, and tomo_nltv_scratch_bytes, tomo_patch_select and
  * tomo_nltv, and the five entry points of the private volume layout (TOMO_VOLUME_ZQUAD below), and the four tomo_pdhg_* entry
- * points (tests/test_matched_bp_oracle.py pins the number 10 as well). */
+ * points (tests/test_matched_bp_oracle.py pins the number 10 as well), and the five tomo_spdhg_* entry points. */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -424,6 +424,36 @@ int tomo_pdhg_tv_dual(int device, const float *xbar_dev, float *q1_dev, float *q
 int tomo_pdhg_primal(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *q1_dev,
                      const float *q2_dev, const float *q3_dev, int dx, int dy, int dz, int nd, float tau, int nonneg,
                      void *stream);
+/* The launches of SPDHG (stochastic PDHG over ordered subsets: one block update touches one subset of angles or the TV
+ * block) beside the per-subset forward projector and the subset form of the matched back projector: a subset update of
+ * RecToolsIRCuPy.SPDHG runs tomo_fp3d on x, tomo_spdhg_sino_dual, tomo_bp3d_matched, tomo_spdhg_primal; a TV update runs
+ * tomo_spdhg_tv_dual, tomo_spdhg_tv_primal.  No reference counterpart: the algorithm is stated in docs/kernels/spdhg.md and
+ * restated in numpy by tests/_spdhg_oracle.py -- formula-level parity, unpinned; the float32 results equal that restatement
+ * bit for bit.  All scalars are float32 values computed by the caller; `w` is 1 / the block's probability.
+ *   tomo_spdhg_sino_dual: v = the update of tomo_pdhg_sino_dual (same `fidelity`) on (y, r, b) over `count` samples;
+ *     r <- v - y (the change the back projector takes), y <- v, both in place.  16-byte accesses when the three arrays are
+ *     16-byte aligned, with a scalar tail.  TOMO_E_INVALID: an unknown term, a non-positive sigma, NULL, aliasing arrays.
+ *   tomo_spdhg_primal: z' = z + delta, zb = z' + w delta, x' = x - tau zb, clamped at 0 with nonneg; x <- x', z <- z', in
+ *     place over `count` voxels (delta = A_j^T of the change).  The same two access forms.  TOMO_E_INVALID: a non-positive
+ *     tau or w, NULL, aliasing arrays.
+ *   tomo_spdhg_tv_dual: p_d = the update of tomo_pdhg_tv_dual on (x, q) (methodTV 0 / 1, radius lambda); e_d <- p_d - q_d,
+ *     q_d <- p_d.  dims as for tomo_pdtv (a dimension of 1 is valid); nd = 2 ignores dz, q3_dev and e3_dev.
+ *   tomo_spdhg_tv_primal: div = (B_1 e1 + B_2 e2) + B_3 e3 (backward differences); z' = z - div, zb = z' - w div,
+ *     x' = x - tau zb, clamped at 0 with nonneg; x <- x', z <- z', in place.
+ *   Both marches: TOMO_E_INVALID for nd outside {2, 3}, a dimension below 1, a non-positive step size, weight or lambda,
+ *     NULL or aliasing arrays.  One launch each.
+ *   tomo_spdhg_scratch_bytes: 2 + 2 nd float arrays (z, delta, q_1..q_nd, e_1..e_nd), each rounded up to 256 bytes and
+ *     followed by the 69888-byte array skew -- the layout of a tomo_placed_scratch block the driver takes them from. */
+size_t tomo_spdhg_scratch_bytes(int dx, int dy, int dz, int nd);
+int tomo_spdhg_sino_dual(float *y_dev, float *r_dev, const float *b_dev, size_t count, int fidelity, float sigma,
+                         void *stream);
+int tomo_spdhg_primal(float *x_dev, float *z_dev, const float *delta_dev, size_t count, float tau, float w, int nonneg,
+                      void *stream);
+int tomo_spdhg_tv_dual(int device, const float *x_dev, float *q1_dev, float *q2_dev, float *q3_dev, float *e1_dev,
+                       float *e2_dev, float *e3_dev, int dx, int dy, int dz, int nd, float sigma, float lambda, int methodTV,
+                       void *stream);
+int tomo_spdhg_tv_primal(int device, float *x_dev, float *z_dev, const float *e1_dev, const float *e2_dev,
+                         const float *e3_dev, int dx, int dy, int dz, int nd, float tau, float w, int nonneg, void *stream);
 /* Nonlinear diffusion (NDF) by explicit time marching: U^0 = in, n times
  *     U' = U + tau (lambda S - (U - in)),   S = sum over the axes of g(U[i + e] - U[i]) + g(U[i - e] - U[i]),
  * with zero flux through the faces of the volume and the flux g chosen by `penalty`:

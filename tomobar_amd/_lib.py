@@ -120,6 +120,11 @@ SIGNATURES = {
     "tomo_pdhg_sino_dual": (_i, [_vp, _vp, _vp, _sz, _i, _f, _vp]),
     "tomo_pdhg_tv_dual": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "tomo_pdhg_primal": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
+    "tomo_spdhg_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_spdhg_sino_dual": (_i, [_vp, _vp, _vp, _sz, _i, _f, _vp]),
+    "tomo_spdhg_primal": (_i, [_vp, _vp, _vp, _sz, _f, _f, _i, _vp]),
+    "tomo_spdhg_tv_dual": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "tomo_spdhg_tv_primal": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "tomo_ndf": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),
     "tomo_ndf_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_diff4th": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _d, C.POINTER(_i), C.POINTER(_d), _vp]),

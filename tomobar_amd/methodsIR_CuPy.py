@@ -74,7 +74,7 @@ class _RunMonitor:
 
 
 class RecToolsIRCuPy:
-    """Iterative reconstruction algorithms (FISTA, ADMM, PDHG, OSEM, SIRT, CGLS, Landweber, power method).
+    """Iterative reconstruction algorithms (FISTA, ADMM, PDHG, SPDHG, OSEM, SIRT, CGLS, Landweber, power method).
 
     Args:
         DetectorsDimH (int): Horizontal detector dimension size.
@@ -193,7 +193,8 @@ class RecToolsIRCuPy:
     def __common_initialisation(self, _data_, _algorithm_, _regularisation_, method_run):
         d, a, r = self._prepare_data(_data_, _algorithm_, _regularisation_, method_run)
         if a.get("lipschitz_const") is None:
-            a["lipschitz_const"] = self.powermethod(d)
+            # SPDHG steps with one bound for every subset's operator; the other drivers with subset 0's (the reference's)
+            a["lipschitz_const"] = self._largest_subset_norm() if method_run == "SPDHG" else self.powermethod(d)
         rec_dim = geom_size(self.Atools.vol_geom)
         x0 = None
         if a["initialise"] is not None:
@@ -207,8 +208,8 @@ class RecToolsIRCuPy:
         use_os = self.OS_number > 1
         w = ops.pwls_weights(d["projection_data"], self.slab) if _data_["data_fidelity"] in ["PWLS", "SWLS"] else None
         # the TV operators' scratch arena is allocated and placed here, at set-up, not inside the first proximal step
-        # (PDHG runs no prox: its work arrays are a placed block of its own)
-        if method_run != "PDHG":
+        # (PDHG and SPDHG run no prox: their work arrays are a placed block of their own)
+        if method_run not in ("PDHG", "SPDHG"):
             reserve_prox_scratch(self, rec_dim, r)
         return (d, a, r, x0, w, use_os)
 
@@ -218,13 +219,20 @@ class RecToolsIRCuPy:
         (reference: methodsIR_CuPy.py:311-354)."""
         if _data_.get("data_fidelity") is None:
             _data_["data_fidelity"] = "LS"
+        return self._power_iterations(0 if self.OS_number > 1 else None)
+
+    def _largest_subset_norm(self) -> float:
+        """The largest of the power-method values of the OS_number subsets' operators (each from the same start vector)."""
+        return max(self._power_iterations(j if self.OS_number > 1 else None) for j in range(self.OS_number))
+
+    def _power_iterations(self, sub) -> float:
+        """Largest eigenvalue of A_sub^T A_sub (`sub` None: all angles) by 15 power iterations."""
         A = self.Atools
         gen = None
         if self.power_seed is not None:
             gen = torch.Generator(device=A._device)
             gen.manual_seed(int(self.power_seed))
         x1 = torch.randn(A.vol_shape(), dtype=torch.float32, device=A._device, generator=gen)
-        sub = 0 if self.OS_number > 1 else None
         y = A.forward(x1, sub)  # PWLS weights are all-ones here (:331-333,:344-346): no effect
         s = 1.0
         for _ in range(15):
@@ -451,6 +459,95 @@ class RecToolsIRCuPy:
                 if a["verbose"] and np.mod(k, (round)(a["iterations"] / 5) + 1) == 0:
                     print("PDHG iteration (", k + 1, ") using", r.get("method"), "regularisation")
                 if mon.stop(k + 1, x):
+                    break
+        finally:
+            A.set_residual_layout("planar")
+            if planar_volume is not None:
+                planar_volume("planar")
+            A.invalidate()
+        return self._finalise(x, a)
+
+    # ------------------------------------------------------------------ SPDHG
+    def SPDHG(self, _data_: dict, _algorithm_: Union[dict, None] = None,
+              _regularisation_: Union[dict, None] = None) -> torch.Tensor:
+        """Stochastic PDHG over the ordered subsets (Chambolle, Ehrhardt, Richtarik, Schoenlieb 2018; no reference
+        counterpart in this reference version; the algorithm is stated in docs/kernels/spdhg.md, formula-level parity,
+        unpinned): PDHG's problem, data terms and TV block, but one update touches one subset of angles or the TV block,
+        drawn with ``numpy.random.default_rng(_algorithm_["SPDHG_seed"])``.  ``iterations`` counts epochs: OS_number block
+        updates, twice as many with TV, i.e. the projector work of one PDHG iteration.  ``lipschitz_const`` bounds every
+        subset's operator (absent: the largest power-method value of the subsets).  Needs ``adjoint="matched"``; any
+        OS_number >= 1; no z-slabs.  Returns the float32 volume ``[detY, N, N]``."""
+        (d, a, r, x, _, use_os) = self.__common_initialisation(_data_, _algorithm_, _regularisation_, "SPDHG")
+        A = self.Atools
+        fid = self.data_fidelity
+        nonneg = bool(a["nonnegativity"])
+        has_tv = r.get("method") is not None
+        nd = 3 if A.vol_shape()[0] > 1 else 2
+        m = self.OS_number
+        blocks = 2 * m if has_tv else m          # E: the block updates of one epoch
+        draws = np.random.default_rng(a["SPDHG_seed"]).integers(0, blocks, size=a["iterations"] * blocks)
+
+        # the step sizes, float32 throughout: sigma_j tau |K_j|^2 <= 0.95^2 p_j with p = 1 / E per subset, 1 / 2 for TV
+        c, gamma = float32(0.95), float32(a["PDHG_ratio"])
+        n_A, n_G = np.sqrt(float32(a["lipschitz_const"])), np.sqrt(float32(4 * nd))
+        sigma_A, sigma_G = (c * gamma) / n_A, (c * gamma) / n_G
+        w_A, w_G = float32(blocks), float32(2)
+        tau = (c / gamma) / (w_A * n_A)
+        if has_tv:
+            tau = min(tau, (c / gamma) / (w_G * n_G))
+        lam = float32(r["regul_param"]) if has_tv else None
+
+        # z = sum K_j^T y_j, delta and the TV fields live in a placed block of their own; b and y are held subset-major,
+        # every subset one contiguous [nz, Na_j, Nu] array (the caller's data are gathered once, never written)
+        z, delta, q, e, _ = ops.spdhg_work_arrays(A.vol_shape(), A._device, has_tv)
+        for field in [z] + q:
+            ops.fill(field, 0.0)
+        subs = [j if use_os else None for j in range(m)]
+        sizes = [int(np.prod(A.sino_shape(sub))) for sub in subs]
+        offsets = np.concatenate(([0], np.cumsum(sizes)))
+        full = d["projection_data"]
+        b_all = torch.empty(int(offsets[-1]), dtype=torch.float32, device=full.device)
+        y_all = torch.empty_like(b_all)
+        ops.fill(y_all, 0.0)
+        proj_all = torch.empty(max(sizes), dtype=torch.float32, device=full.device)
+        b, y, proj = [], [], []
+        for j, sub in enumerate(subs):
+            shape = A.sino_shape(sub)
+            b.append(b_all[offsets[j]:offsets[j + 1]].view(shape))
+            y.append(y_all[offsets[j]:offsets[j + 1]].view(shape))
+            proj.append(proj_all[:sizes[j]].view(shape))
+            if use_os:
+                index = torch.from_numpy(np.ascontiguousarray(A.subset_indices(j), dtype=np.int64)).to(full.device)
+                torch.index_select(full, 1, index, out=b[j])
+            else:
+                b[j].copy_(full)
+        if nonneg:
+            ops.clamp_min(x, 0.0)     # SPDHG's first primal step with z-bar = 0
+
+        planar_volume = getattr(A, "set_volume_layout", None)
+        A.invalidate()
+        A.set_residual_layout("planar")
+        if planar_volume is not None:
+            planar_volume("planar")
+        mon = _RunMonitor(self, "SPDHG", a, x)
+        done = [0, 0]
+        mon.run["block_updates"] = (0, 0)
+        try:
+            for epoch in range(a["iterations"]):
+                for j in draws[epoch * blocks:(epoch + 1) * blocks]:
+                    if j < m:
+                        A.forward(x, subs[j], out=proj[j])
+                        ops.spdhg_sino_dual(y[j], proj[j], b[j], fid, sigma_A)
+                        A.backward(proj[j], subs[j], out=delta)
+                        ops.spdhg_primal(x, z, delta, tau, w_A, nonneg)
+                    else:
+                        ops.spdhg_tv_dual(x, q, e, sigma_G, lam, r["methodTV"])
+                        ops.spdhg_tv_primal(x, z, e, tau, w_G, nonneg)
+                    done[int(j >= m)] += 1
+                mon.run["block_updates"] = tuple(done)
+                if a["verbose"] and np.mod(epoch, (round)(a["iterations"] / 5) + 1) == 0:
+                    print("SPDHG epoch (", epoch + 1, ") using", r.get("method"), "regularisation")
+                if mon.stop(epoch + 1, x):
                     break
         finally:
             A.set_residual_layout("planar")

@@ -401,6 +401,99 @@ def pdhg_primal(x, xbar, g, q, tau, nonneg=False):
                                          float(tau), int(bool(nonneg)), stream_ptr(x)))
 
 
+# ----------------------------------------------------------------------------- SPDHG (docs/kernels/spdhg.md)
+SPDHG_SLOT = 6   # the placed block of the SPDHG driver's work arrays
+
+
+def spdhg_work_arrays(shape, device, tv: bool = True):
+    """The work arrays of one SPDHG call on a volume of `shape` ([nz, ny, nx]), uninitialised, from the placed block of
+    ``SPDHG_SLOT``: (z, delta, [q_1 .. q_nd], [e_1 .. e_nd]) and the lease token of ``placed_empty``; nd = 3 if nz > 1 else
+    2, no q and e without the TV block.  With it the block has the size ``tomo_spdhg_scratch_bytes`` states."""
+    nd = 3 if shape[0] > 1 else 2
+    arrays, lease = placed_empty([(tuple(shape), torch.float32)] * (2 + (2 * nd if tv else 0)), device, slot=SPDHG_SLOT)
+    return arrays[0], arrays[1], arrays[2:2 + nd] if tv else [], arrays[2 + nd:] if tv else [], lease
+
+
+def _spdhg_positive(value, name):
+    if not float(value) > 0.0:
+        raise ValueError(f"SPDHG: {name} must be positive")
+    return float(value)
+
+
+def _spdhg_distinct(named):
+    """no two of the (name, tensor) pairs start at the same address"""
+    seen = {}
+    for name, t in named:
+        if t.data_ptr() in seen:
+            raise ValueError(f"{name} must not alias {seen[t.data_ptr()]}")
+        seen[t.data_ptr()] = name
+
+
+def _spdhg_flat(first, named):
+    """the element-wise launches: float32, contiguous, the size and the device of `first`, no aliasing"""
+    for name, t in named:
+        _chk_f32(t, name)
+        if t.numel() != first.numel() or t.device != first.device:
+            raise ValueError(f"{name} must have the size and the device of {named[0][0]}")
+    _spdhg_distinct(named)
+
+
+def spdhg_sino_dual(y, r, b, fidelity: str, sigma):
+    """Step 2 of an SPDHG subset update (tomo_spdhg_sino_dual): v = PDHG's sinogram dual of the data term `fidelity` ("LS",
+    "L1" or "KL") on (y, r, b); `r` <- v - y, `y` <- v, both in place.  `r` = A_j x, `b` = the subset's data, `sigma` a
+    float32 scalar.  Returns (y, r)."""
+    if fidelity not in L.PDHG_FID:
+        raise ValueError(f"unknown SPDHG data term {fidelity!r}: LS, L1 and KL are supported")
+    _spdhg_flat(y, [("y", y), ("r", r), ("b", b)])
+    sigma = _spdhg_positive(sigma, "the step size sigma")
+    with _on(y):
+        L.check(L.lib().tomo_spdhg_sino_dual(ptr(y), ptr(r), ptr(b), y.numel(), L.PDHG_FID[fidelity], sigma, stream_ptr(y)))
+    return y, r
+
+
+def spdhg_primal(x, z, delta, tau, w, nonneg=False):
+    """Step 4 of an SPDHG subset update (tomo_spdhg_primal): z' = z + delta, zb = z' + w delta, x' = x - tau zb, clamped at 0
+    with `nonneg`; `x` <- x', `z` <- z', in place.  `delta` = A_j^T of the dual's change, `w` = 1 / the block's probability."""
+    _spdhg_flat(x, [("x", x), ("z", z), ("delta", delta)])
+    tau, w = _spdhg_positive(tau, "the step size tau"), _spdhg_positive(w, "the weight w")
+    with _on(x):
+        L.check(L.lib().tomo_spdhg_primal(ptr(x), ptr(z), ptr(delta), x.numel(), tau, w, int(bool(nonneg)), stream_ptr(x)))
+
+
+def _spdhg_fields(x, fields, what):
+    dx, dy, dz, nd = _pdhg_dims(x)
+    for name, group in fields:
+        if len(group) != nd:
+            raise ValueError(f"a volume of {dz} plane{'s' if dz > 1 else ''} takes {nd} {what} fields, got {len(group)} for {name}")
+    named = [(f"{name}{d + 1}", t) for name, group in fields for d, t in enumerate(group)]
+    _pdhg_fields(x, named)
+    return dx, dy, dz, nd, named
+
+
+def spdhg_tv_dual(x, q, e, sigma, lam, methodTV=0):
+    """Step 1 of an SPDHG TV update (tomo_spdhg_tv_dual): p_d = q_d + sigma F_d(x), projected (methodTV 0: onto the ball of
+    radius `lam`, 1: onto the box); `e` <- p - q, `q` <- p.  `q` and `e` hold nd fields like `x` each."""
+    dx, dy, dz, nd, named = _spdhg_fields(x, [("q", q), ("e", e)], "dual")
+    _spdhg_distinct([("x", x)] + named)
+    sigma, lam = _spdhg_positive(sigma, "the step size sigma"), _spdhg_positive(lam, "lambda")
+    p = [ptr(t) for t in q] + [ptr(None)] * (3 - nd) + [ptr(t) for t in e] + [ptr(None)] * (3 - nd)
+    with _on(x):
+        L.check(L.lib().tomo_spdhg_tv_dual(x.device.index, ptr(x), *p, dx, dy, dz, nd, sigma, lam, int(methodTV), stream_ptr(x)))
+
+
+def spdhg_tv_primal(x, z, e, tau, w, nonneg=False):
+    """Steps 2 and 3 of an SPDHG TV update (tomo_spdhg_tv_primal): div = sum_d B_d(e_d); z' = z - div, zb = z' - w div,
+    x' = x - tau zb, clamped at 0 with `nonneg`; `x` <- x', `z` <- z', in place.  `e`: the nd fields spdhg_tv_dual left."""
+    dx, dy, dz, nd, named = _spdhg_fields(x, [("e", e)], "dual")
+    _pdhg_fields(x, [("z", z)])
+    _spdhg_distinct([("x", x), ("z", z)] + named)
+    tau, w = _spdhg_positive(tau, "the step size tau"), _spdhg_positive(w, "the weight w")
+    p = [ptr(t) for t in e] + [ptr(None)] * (3 - nd)
+    with _on(x):
+        L.check(L.lib().tomo_spdhg_tv_primal(x.device.index, ptr(x), ptr(z), *p, dx, dy, dz, nd, tau, w, int(bool(nonneg)),
+                                             stream_ptr(x)))
+
+
 def _wavelet_args(data, out, mix):
     _chk_f32(data, "data")
     if data.dim() not in (2, 3):
@@ -550,7 +643,8 @@ def placed_empty(specs, device, slot: int = 0):
     ``ARRAY_SKEW`` apart; a lease token).  The block belongs to the library (grow-only per (device, stream, slot), freed
     by ``tomo_release_scratch``): the tensors are views for the duration of ONE driver call, not allocations to keep, and
     a second ``placed_empty`` on the same (device, stream, slot) supersedes them -- ``lease_is_current(token)`` tells.
-    Slots in use: the ``slot`` of the records of tomobar_amd/supp/regularisers.py, one per slab driver, and ``PDHG_SLOT``."""
+    Slots in use: the ``slot`` of the records of tomobar_amd/supp/regularisers.py, one per slab driver, ``PDHG_SLOT`` and
+    ``SPDHG_SLOT``."""
     device = torch.device(device)
     sizes, total = [], 0
     for shape, dtype in specs:

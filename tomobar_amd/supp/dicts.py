@@ -8,6 +8,7 @@ pointer to ASTRA, astra_base.py:533-535).
 
 from __future__ import annotations
 
+import numbers
 from typing import Optional
 
 from .. import ops
@@ -23,6 +24,7 @@ LABELS_2D = ["angles", "detX"]
 _DEFAULT_ITERATIONS = {
     "SIRT": (200, 200), "CGLS": (30, 30), "power": (15, 15), "Landweber": (1500, 1500),
     "OSEM": (300, 15), "FISTA": (400, 20), "ADMM": (400, 10), "PDHG": (500, 500),
+    "SPDHG": (100, 100),   # epochs (docs/kernels/spdhg.md)
 }
 _NO_OS_METHODS = {"SIRT", "CGLS", "Landweber"}
 _NO_LIPSCHITZ = {"SIRT", "CGLS", "power", "Landweber", "OSEM"}
@@ -68,39 +70,47 @@ def _nltv_keys(self, reg: dict) -> None:
             raise ValueError(f"_regularisation_['{NLTV_ITERATIONS}'] must not be negative")
 
 
-def _pdhg_refusals(self, _data_: dict) -> None:
-    """What PDHG (RecToolsIRCuPy.PDHG; docs/kernels/pdhg.md) cannot run on, as a ValueError before any projector call: an
-    unmatched operator pair (the iteration assumes the exact adjoint), ordered subsets, a z-slab, the weighted data terms,
-    the ring and robust keys."""
+_PDHG_METHODS = {"PDHG", "SPDHG"}   # the primal-dual drivers: the same data terms, keys and refusals but for the subsets
+
+
+def _pdhg_refusals(self, _data_: dict, name: str = "PDHG") -> None:
+    """What PDHG and SPDHG (RecToolsIRCuPy.PDHG, .SPDHG; docs/kernels/pdhg.md, spdhg.md) cannot run on, as a ValueError before
+    any projector call: an unmatched operator pair (the iteration assumes the exact adjoint), ordered subsets (PDHG only), a
+    z-slab, the weighted data terms, the ring and robust keys."""
     if getattr(self, "adjoint", None) != "matched":
-        raise ValueError("PDHG needs the exact adjoint of the forward projector: construct with adjoint=\"matched\"")
-    if self.OS_number > 1:
+        raise ValueError(f"{name} needs the exact adjoint of the forward projector: construct with adjoint=\"matched\"")
+    if self.OS_number > 1 and name == "PDHG":
         raise ValueError("There is no ordered-subsets implementation of PDHG, please set OS_number=None")
     if getattr(self, "slab", None) is not None:
-        raise ValueError("PDHG is not available in z-slab mode")
+        raise ValueError(f"{name} is not available in z-slab mode")
     if _data_["data_fidelity"] not in {"LS", "KL", "L1"}:
-        raise ValueError(f"PDHG supports the 'LS', 'KL' and 'L1' data fidelities, not {_data_['data_fidelity']!r}")
+        raise ValueError(f"{name} supports the 'LS', 'KL' and 'L1' data fidelities, not {_data_['data_fidelity']!r}")
     for key in ("ringGH_lambda", "huber_threshold", "studentst_threshold"):
         if _data_.get(key) is not None:
-            raise ValueError(f"_data_['{key}'] is available in FISTA only (PDHG: the 'L1' data fidelity is the robust term)")
+            raise ValueError(f"_data_['{key}'] is available in FISTA only ({name}: the 'L1' data fidelity is the robust term)")
 
 
-def _pdhg_keys(_algorithm_: dict, _regularisation_: dict) -> None:
-    """PDHG's own keys: ``PDHG_ratio`` (sigma / tau, default 1.0, positive) and a regulariser that is None or exactly
-    "PD_TV" -- the same TV semi-norm, solved jointly in the dual, so only ``regul_param`` and ``methodTV`` are read (and
-    filled); no prox runs, hence no slice-wise or half-precision form."""
+def _pdhg_keys(_algorithm_: dict, _regularisation_: dict, name: str = "PDHG") -> None:
+    """The keys of PDHG and SPDHG: ``PDHG_ratio`` (sigma / tau, default 1.0, positive), for SPDHG ``SPDHG_seed`` (the seed
+    of the block draws, default 0, a non-negative int), and a regulariser that is None or exactly "PD_TV" -- the same TV
+    semi-norm, solved jointly in the dual, so only ``regul_param`` and ``methodTV`` are read (and filled); no prox runs,
+    hence no slice-wise or half-precision form."""
     _algorithm_.setdefault("PDHG_ratio", 1.0)
     if not float(_algorithm_["PDHG_ratio"]) > 0.0:
         raise ValueError("_algorithm_['PDHG_ratio'] (sigma / tau) must be positive")
+    if name == "SPDHG":
+        seed = _algorithm_.setdefault("SPDHG_seed", 0)
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or seed < 0:
+            raise ValueError("_algorithm_['SPDHG_seed'] must be a non-negative int")
     method = _regularisation_.get("method")
     if method is None:
         return
     if method != "PD_TV":
-        raise ValueError(f"PDHG takes _regularisation_['method'] = None or 'PD_TV' (the TV term in its dual), not {method!r}")
+        raise ValueError(f"{name} takes _regularisation_['method'] = None or 'PD_TV' (the TV term in its dual), not {method!r}")
     if _regularisation_.get("slicewise", False) is not False:
-        raise ValueError("PDHG does not support slicewise=True")
+        raise ValueError(f"{name} does not support slicewise=True")
     if _regularisation_.get("half_precision", False):
-        raise ValueError("PDHG does not support half_precision=True")
+        raise ValueError(f"{name} does not support half_precision=True")
     _regularisation_.setdefault("regul_param", 0.001)
     _regularisation_.setdefault("methodTV", 0)
     if not float(_regularisation_["regul_param"]) > 0.0:
@@ -133,12 +143,12 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
     # "SWLS" (stripe-weighted least squares) and the Group-Huber keys below are the ring-artefact data terms of the
     # reference's removed RecToolsIR class (docs/source/tutorials/real_data_recon.rst:100-151); the reference's current
     # dicts_check knows LS / PWLS / KL only
-    # "L1" is PDHG's alone (docs/kernels/pdhg.md): the other drivers need a differentiable data term
+    # "L1" is PDHG's and SPDHG's alone (docs/kernels/pdhg.md): the other drivers need a differentiable data term
     if _data_["data_fidelity"] not in {"LS", "PWLS", "KL", "SWLS"} and not (
-            method_run == "PDHG" and _data_["data_fidelity"] == "L1"):
+            method_run in _PDHG_METHODS and _data_["data_fidelity"] == "L1"):
         raise ValueError("_data_['data_fidelity'] should be provided as 'LS', 'PWLS', 'KL' (or 'SWLS').")
-    if method_run == "PDHG":
-        _pdhg_refusals(self, _data_)
+    if method_run in _PDHG_METHODS:
+        _pdhg_refusals(self, _data_, method_run)
     self.data_fidelity = _data_["data_fidelity"]
     _data_.setdefault("ringGH_lambda", None)        # Group-Huber offsets: off unless a threshold is given
     _data_.setdefault("ringGH_accelerate", 50)
@@ -195,8 +205,8 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
         _regularisation_ = {}
     if not _regularisation_:
         _regularisation_["method"] = None
-    if method_run == "PDHG":   # before the prox methods' own checks: nothing but None / "PD_TV" gets that far
-        _pdhg_keys(_algorithm_, _regularisation_)
+    if method_run in _PDHG_METHODS:   # before the prox methods' own checks: nothing but None / "PD_TV" gets that far
+        _pdhg_keys(_algorithm_, _regularisation_, method_run)
     nltv_check(_regularisation_)
     if is_nltv(_regularisation_.get("method")):   # before the defaults: "iterations" must still be the caller's own
         _nltv_keys(self, _regularisation_)

@@ -1,35 +1,34 @@
-// The three launches PDHG (primal-dual hybrid gradient, Chambolle-Pock, on the reconstruction problem itself:
+// The launches that PDHG (primal-dual hybrid gradient, Chambolle-Pock, on the reconstruction problem itself:
 //     min_x F(Ax) + lambda TV(x)  [+ x >= 0],   F = 1/2 |. - b|^2, |. - b|_1 or the Kullback-Leibler term)
-// adds to the forward projector and the matched back projector for gfx950.  There is no reference implementation in the
-// tree: what is computed is the algorithm stated in docs/kernels/pdhg.md, formula-level parity, unpinned --
-// tests/_pdhg_oracle.py restates it in numpy and the kernels reproduce its float32 form bit for bit (one rounding per
-// operation in the stated order, no FMA contraction: -ffp-contract=off and no fmaf here; sqrtf and / are the compiler's
-// correctly rounded ones).
+// and SPDHG (its stochastic form over ordered subsets; Chambolle, Ehrhardt, Richtarik, Schoenlieb 2018: one block update
+// touches one subset of angles or the TV block) add to the forward projector and the matched back projector for gfx950.
+// There is no reference implementation in the tree: what is computed are the algorithms stated in docs/kernels/pdhg.md and
+// docs/kernels/spdhg.md, formula-level parity, unpinned -- tests/_pdhg_oracle.py and tests/_spdhg_oracle.py restate them in
+// numpy and the kernels reproduce their float32 form bit for bit (one rounding per operation in the stated order, no FMA
+// contraction: -ffp-contract=off and no fmaf here; sqrtf and / are the compiler's correctly rounded ones).
 //
-//   pdhg_sino_kernel    step 2: the prox of the conjugate of the data term on the sinogram dual y, element-wise, in place
-//   pdhg_dual_kernel    step 4: q_d += sigma F_d(x-bar), projected onto the ball (isotropic) or the box (anisotropic)
-//   pdhg_primal_kernel  step 5: x' = x - tau (g - div q) [clamped], x-bar = 2 x' - x
-// The last two are plane marches on the skeleton of tgv_dual.inl / tgv_primal.inl (4 rows per lane, 2 x 2 waves, 63
-// columns per wave; the wave shifts, the plane I/O, the z-march grid and the array skew are the one copy in
-// zmarch_common.h).  Each voxel's own q, x are read by that voxel only, and the neighbours a launch reads belong to fields
-// it does not write, so nothing is ping-ponged.  Algorithmic traffic in 3D: dual 4 + 3 x 8 = 28 B, primal 3 x 4 + 8 + 8 =
-// 28 B per voxel and iteration; the sinogram kernel moves 16 B per sample.
+// Both families run on ONE copy of three device skeletons; what a launch computes per element is a functor or a flag:
+//   stream3_kernel<PdhgSino>        PDHG step 2:       y <- the prox of the conjugate of the data term at y + sigma r
+//   stream3_kernel<StochSino>       SPDHG subset 2:    v = that prox on (y_j, r, b_j); d = v - y_j over r, y_j <- v
+//   stream3_kernel<StochPrimal>     SPDHG subset 4:    z' = z + delta, zb = z' + w delta, x' = x - tau zb [clamped]
+//   tv_dual_march<EMIT_E = false>   PDHG step 4:       q_d <- q_d + sigma F_d(x-bar), projected onto the ball or the box
+//   tv_dual_march<EMIT_E = true>    SPDHG TV step 1:   the same p_d from x; e_d = p_d - q_d, q_d <- p_d
+//   tv_primal_march<PdhgUpdate>     PDHG step 5:       x' = x - tau (g - div q) [clamped], x-bar = 2 x' - x
+//   tv_primal_march<StochTvUpdate>  SPDHG TV 2, 3:     div = sum B_d(e_d); z' = z - div, zb = z' - w div, x' = x - tau zb
+// The streaming launches move 16 B (PdhgSino: r is not written) or 20 B per element.  The marches are plane marches on the
+// skeleton of tgv_dual.inl / tgv_primal.inl (4 rows per lane, 2 x 2 waves, 63 columns per wave; the wave shifts, the plane
+// I/O, the z-march grid and the array skew are the one copy in zmarch_common.h).  Each voxel's own values are read by that
+// voxel only, and the neighbours a launch reads belong to fields it does not write, so nothing is ping-ponged.  Algorithmic
+// traffic in 3D: the dual march 4 + 3 x 8 = 28 B (with e: 4 + 3 x 12 = 40 B), the primal march 3 x 4 + 8 + 8 = 28 B per voxel.
 #include "zmarch_common.h"
+#include <initializer_list>
 
 namespace {
 
-struct PdhgArgs {
-    float *x, *xb;     // the primal variable and its extrapolation x-bar
-    const float *g;    // A^T y
-    float *q[3];       // the TV dual (q[0] null: no TV block)
-    int dx, dy, dz;
-    float sigma, tau, lambda;
-    int nonneg;
-};
-
-// ------------------------------------------------------------------------------------------ step 2: the sinogram dual
+// ------------------------------------------------------------------------------------------ the data term
+// the prox of the conjugate of the data term at y + sigma r (step 2 of both algorithms)
 template <int MODE>
-__device__ __forceinline__ float pdhg_sino_one(float y, float r, float b, float sigma, float one_sigma, float c4)
+__device__ __forceinline__ float data_prox(float y, float r, float b, float sigma, float one_sigma, float c4)
 {
     if (MODE == TOMO_PDHG_LS) return (y + sigma * (r - b)) / one_sigma;
     if (MODE == TOMO_PDHG_L1) {
@@ -42,57 +41,123 @@ __device__ __forceinline__ float pdhg_sino_one(float y, float r, float b, float 
     return 0.5f * ((1.0f + v) - sqrtf(t * t + c4 * bp));
 }
 
-constexpr int SINO_BLOCK = 256;
-constexpr int SINO_MAX_GRID = 256 * 8;   // 256 CUs x 8 blocks, grid-stride beyond
+// The per-element functors of stream3_kernel: op(a, b, c) updates a, and b where WRITES_B says so.
+template <int MODE>
+struct PdhgSino {   // y <- v
+    static constexpr bool WRITES_B = false;
+    float sigma, one_sigma, c4;
+    __device__ __forceinline__ void operator()(float &y, float &r, float b) const { y = data_prox<MODE>(y, r, b, sigma, one_sigma, c4); }
+};
 
+template <int MODE>
+struct StochSino {   // y <- v and r <- d = v - y
+    static constexpr bool WRITES_B = true;
+    float sigma, one_sigma, c4;
+    __device__ __forceinline__ void operator()(float &y, float &r, float b) const
+    {
+        const float v = data_prox<MODE>(y, r, b, sigma, one_sigma, c4);
+        r = v - y;
+        y = v;
+    }
+};
+
+struct StochPrimal {   // SPDHG subset step 4
+    static constexpr bool WRITES_B = true;
+    float tau, w;
+    int nonneg;
+    __device__ __forceinline__ void operator()(float &x, float &z, float delta) const
+    {
+        const float zn = z + delta;
+        const float zb = zn + w * delta;
+        float xn = x - tau * zb;
+        if (nonneg) xn = xn < 0.0f ? 0.0f : xn;
+        x = xn;
+        z = zn;
+    }
+};
+
+// ------------------------------------------------------------------------------------------ the streaming skeleton
+constexpr int STREAM_BLOCK = 256;
+constexpr int STREAM_MAX_GRID = 256 * 8;   // 256 CUs x 8 blocks, grid-stride beyond
+
+// element i in scalar form
+template <class Op>
+__device__ __forceinline__ void stream3_one(const Op &op, float *a, float *b, const float *c, size_t i)
+{
+    float sa = a[i], sb = b[i];
+    op(sa, sb, c[i]);
+    a[i] = sa;
+    if (Op::WRITES_B) b[i] = sb;
+}
+
+// Three arrays of n floats: a is read and written, b is read (and written: Op::WRITES_B), c is read.
 // VEC: 16-byte accesses over the first n / 4 quads and a scalar tail by block 0 (all three arrays 16-byte aligned)
-template <int MODE, bool VEC>
-__global__ __launch_bounds__(SINO_BLOCK) void pdhg_sino_kernel(float *y, const float *r, const float *b, size_t n,
-                                                               float sigma, float one_sigma, float c4)
+template <class Op, bool VEC>
+__global__ __launch_bounds__(STREAM_BLOCK) void stream3_kernel(float *a, float *b, const float *c, size_t n, Op op)
 {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (VEC) {
         const size_t n4 = n >> 2;
         for (size_t i = first; i < n4; i += stride) {
-            float4 vy = reinterpret_cast<const float4 *>(y)[i];
-            const float4 vr = reinterpret_cast<const float4 *>(r)[i];
-            const float4 vb = reinterpret_cast<const float4 *>(b)[i];
-            vy.x = pdhg_sino_one<MODE>(vy.x, vr.x, vb.x, sigma, one_sigma, c4);
-            vy.y = pdhg_sino_one<MODE>(vy.y, vr.y, vb.y, sigma, one_sigma, c4);
-            vy.z = pdhg_sino_one<MODE>(vy.z, vr.z, vb.z, sigma, one_sigma, c4);
-            vy.w = pdhg_sino_one<MODE>(vy.w, vr.w, vb.w, sigma, one_sigma, c4);
-            reinterpret_cast<float4 *>(y)[i] = vy;
+            float4 va = reinterpret_cast<const float4 *>(a)[i];
+            float4 vb = reinterpret_cast<const float4 *>(b)[i];
+            const float4 vc = reinterpret_cast<const float4 *>(c)[i];
+            op(va.x, vb.x, vc.x);
+            op(va.y, vb.y, vc.y);
+            op(va.z, vb.z, vc.z);
+            op(va.w, vb.w, vc.w);
+            reinterpret_cast<float4 *>(a)[i] = va;
+            if (Op::WRITES_B) reinterpret_cast<float4 *>(b)[i] = vb;
         }
         const size_t i = (n4 << 2) + threadIdx.x;
-        if (blockIdx.x == 0 && i < n) y[i] = pdhg_sino_one<MODE>(y[i], r[i], b[i], sigma, one_sigma, c4);
+        if (blockIdx.x == 0 && i < n) stream3_one(op, a, b, c, i);
     } else {
-        for (size_t i = first; i < n; i += stride) y[i] = pdhg_sino_one<MODE>(y[i], r[i], b[i], sigma, one_sigma, c4);
+        for (size_t i = first; i < n; i += stride) stream3_one(op, a, b, c, i);
     }
 }
 
-template <int MODE>
-static void pdhg_sino_launch(float *y, const float *r, const float *b, size_t n, float sigma, hipStream_t st)
+// the only launch site of the streaming skeleton
+template <class Op>
+static void stream3_launch(float *a, float *b, const float *c, size_t n, Op op, hipStream_t st)
 {
-    const bool vec = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
+    const bool vec = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15u) == 0;
     const size_t items = vec ? (n >> 2) : n;
-    size_t grid = (items + SINO_BLOCK - 1) / SINO_BLOCK;
+    size_t grid = (items + STREAM_BLOCK - 1) / STREAM_BLOCK;
     if (grid < 1) grid = 1;
-    if (grid > (size_t)SINO_MAX_GRID) grid = SINO_MAX_GRID;
-    const float one_sigma = 1.0f + sigma, c4 = 4.0f * sigma;
+    if (grid > (size_t)STREAM_MAX_GRID) grid = STREAM_MAX_GRID;
     if (vec)
-        pdhg_sino_kernel<MODE, true><<<(unsigned)grid, SINO_BLOCK, 0, st>>>(y, r, b, n, sigma, one_sigma, c4);
+        stream3_kernel<Op, true><<<(unsigned)grid, STREAM_BLOCK, 0, st>>>(a, b, c, n, op);
     else
-        pdhg_sino_kernel<MODE, false><<<(unsigned)grid, SINO_BLOCK, 0, st>>>(y, r, b, n, sigma, one_sigma, c4);
+        stream3_kernel<Op, false><<<(unsigned)grid, STREAM_BLOCK, 0, st>>>(a, b, c, n, op);
 }
 
-// ------------------------------------------------------------------------------------------ step 4: the TV dual
-// A lane owns RY rows of one x column and walks z.  The +x neighbour is the next lane (lane 63 of a wave is a halo lane:
-// 63 columns per wave), the +y neighbour the next register (one halo row below the tile), the +z neighbour the plane loaded
-// one step ahead, which becomes the current plane of the next step: x-bar is read once per launch (plus halos), q read and
-// written once.
-template <int ND, bool ANISO, int RY, int WX, int WY>
-__global__ __launch_bounds__(64 * WX * WY) void pdhg_dual_kernel(PdhgArgs a, int gx, int gy, int tiles_per_xcd, int zchunk)
+// the sinogram dual of either family over the three data terms
+template <template <int> class Sino>
+static void sino_launch(int fidelity, float *y, float *r, const float *b, size_t n, float sigma, hipStream_t st)
+{
+    const float one_sigma = 1.0f + sigma, c4 = 4.0f * sigma;
+    if (fidelity == TOMO_PDHG_LS) stream3_launch(y, r, b, n, Sino<TOMO_PDHG_LS>{sigma, one_sigma, c4}, st);
+    else if (fidelity == TOMO_PDHG_L1) stream3_launch(y, r, b, n, Sino<TOMO_PDHG_L1>{sigma, one_sigma, c4}, st);
+    else stream3_launch(y, r, b, n, Sino<TOMO_PDHG_KL>{sigma, one_sigma, c4}, st);
+}
+
+// ------------------------------------------------------------------------------------------ the forward-difference march
+struct TvDualArgs {
+    const float *src;  // the field whose gradient is taken: PDHG's x-bar, SPDHG's x
+    float *q[3];       // the TV dual
+    float *e[3];       // its change p - q of this update (EMIT_E only)
+    int dx, dy, dz;
+    float sigma, lambda;
+};
+
+// p_d = q_d + sigma F_d(src), projected onto the ball (isotropic) or the box (anisotropic); q_d <- p_d and, with EMIT_E,
+// e_d <- p_d - q_d.  A lane owns RY rows of one x column and walks z.  The +x neighbour is the next lane (lane 63 of a wave
+// is a halo lane: 63 columns per wave), the +y neighbour the next register (one halo row below the tile), the +z neighbour
+// the plane loaded one step ahead, which becomes the current plane of the next step: src is read once per launch (plus
+// halos), q read and written once, e written once.
+template <int ND, bool ANISO, bool EMIT_E, int RY, int WX, int WY>
+__global__ __launch_bounds__(64 * WX * WY) void tv_dual_march(TvDualArgs a, int gx, int gy, int tiles_per_xcd, int zchunk)
 {
     // XCD banding of rof_zmarch.inl: every XCD owns one contiguous eighth of the row-major tile list
     const int j = (int)blockIdx.x >> 3;
@@ -124,7 +189,7 @@ __global__ __launch_bounds__(64 * WX * WY) void pdhg_dual_kernel(PdhgArgs a, int
 
     float cur[RY + 1], nxt[RY + 1];
 #pragma unroll
-    for (int q = 0; q <= RY; ++q) cur[q] = io.ld(a.xb + sz * zc0, xo, rowoff(q));
+    for (int q = 0; q <= RY; ++q) cur[q] = io.ld(a.src + sz * zc0, xo, rowoff(q));
 
     for (int t = zc0; t < zc1; ++t) {
         __syncthreads();  // lockstep: the waves of a workgroup stay on the same plane
@@ -132,9 +197,9 @@ __global__ __launch_bounds__(64 * WX * WY) void pdhg_dual_kernel(PdhgArgs a, int
         if (ND == 3) {
             const size_t pn = sz * min(t + 1, dz - 1);
 #pragma unroll
-            for (int q = 0; q <= RY; ++q) nxt[q] = io.ld(a.xb + pn, xo, rowoff(q));
+            for (int q = 0; q <= RY; ++q) nxt[q] = io.ld(a.src + pn, xo, rowoff(q));
         }
-        float Q[ND][RY];
+        float Q[ND][RY], E[ND][RY];
 #pragma unroll
         for (int d = 0; d < ND; ++d)
 #pragma unroll
@@ -143,28 +208,34 @@ __global__ __launch_bounds__(64 * WX * WY) void pdhg_dual_kernel(PdhgArgs a, int
 #pragma unroll
         for (int r = 0; r < RY; ++r) {
             const bool y_next = y0 + r < dy - 1;
-            // F_d(x-bar): a[i + e_d] - a[i], exactly 0 on the last index of the axis
+            // F_d(src): a[i + e_d] - a[i], exactly 0 on the last index of the axis
             const float c = cur[r];
             const float cx = wave_next(c);
             float F[3];
             F[0] = x_next ? cx - c : 0.0f;
             F[1] = y_next ? cur[r + 1] - c : 0.0f;
             F[2] = (ND == 3 && z_next) ? nxt[r] - c : 0.0f;
+            float P[ND];
 #pragma unroll
-            for (int d = 0; d < ND; ++d) Q[d][r] = Q[d][r] + a.sigma * F[d];
+            for (int d = 0; d < ND; ++d) P[d] = Q[d][r] + a.sigma * F[d];
             if (ANISO) {
 #pragma unroll
                 for (int d = 0; d < ND; ++d) {
-                    const float v = Q[d][r] < -a.lambda ? -a.lambda : Q[d][r];
-                    Q[d][r] = v > a.lambda ? a.lambda : v;
+                    const float v = P[d] < -a.lambda ? -a.lambda : P[d];
+                    P[d] = v > a.lambda ? a.lambda : v;
                 }
             } else {
-                float m = Q[0][r] * Q[0][r] + Q[1][r] * Q[1][r];
-                if (ND == 3) m = m + Q[ND - 1][r] * Q[ND - 1][r];
+                float m = P[0] * P[0] + P[1] * P[1];
+                if (ND == 3) m = m + P[ND - 1] * P[ND - 1];
                 const float n = sqrtf(m) / a.lambda;
-                const float den = n > 1.0f ? n : 1.0f;   // q / 1 is q: the same bits as leaving it alone
+                const float den = n > 1.0f ? n : 1.0f;   // p / 1 is p: the same bits as leaving it alone
 #pragma unroll
-                for (int d = 0; d < ND; ++d) Q[d][r] = Q[d][r] / den;
+                for (int d = 0; d < ND; ++d) P[d] = P[d] / den;
+            }
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                E[d][r] = P[d] - Q[d][r];
+                Q[d][r] = P[d];
             }
         }
 
@@ -172,7 +243,10 @@ __global__ __launch_bounds__(64 * WX * WY) void pdhg_dual_kernel(PdhgArgs a, int
         for (int r = 0; r < RY; ++r) {
             if (emit_lane && y0 + r < dy) {
 #pragma unroll
-                for (int d = 0; d < ND; ++d) io.st(a.q[d] + sz * t, xo, rowoff(r), Q[d][r]);
+                for (int d = 0; d < ND; ++d) {
+                    io.st(a.q[d] + sz * t, xo, rowoff(r), Q[d][r]);
+                    if (EMIT_E) io.st(a.e[d] + sz * t, xo, rowoff(r), E[d][r]);
+                }
             }
         }
         if (ND == 3) {
@@ -182,13 +256,54 @@ __global__ __launch_bounds__(64 * WX * WY) void pdhg_dual_kernel(PdhgArgs a, int
     }
 }
 
-// ------------------------------------------------------------------------------------------ step 5: the primal
-// The mirror image: the -x neighbour is the previous lane (lane 0 of a wave is the halo lane), the -y neighbour the previous
-// register (one halo row above the tile, q2 only), the -z neighbour the carried registers of the plane before (q3; a
-// z-chunk loads them once for the plane below its first).  q and g are read and not written; x is read and x, x-bar are
-// written at the lane's own voxels only.  TV = false drops the q loads: div is 0.
-template <int ND, bool TV, int RY, int WX, int WY>
-__global__ __launch_bounds__(64 * WX * WY) void pdhg_primal_kernel(PdhgArgs a, int gx, int gy, int tiles_per_xcd, int zchunk)
+// ------------------------------------------------------------------------------------------ the backward-difference march
+struct TvPrimalArgs {
+    float *x;          // the primal variable
+    const float *s;    // the second array the update reads: PDHG's g = A^T y, SPDHG's z = sum K_j^T y_j
+    float *s_out;      // the second array it writes: PDHG's x-bar, SPDHG's z (Update::IN_PLACE: the same array)
+    const float *f[3]; // the fields whose divergence is taken: PDHG's q, SPDHG's e (TV = false: none, div = 0)
+    int dx, dy, dz;
+};
+
+// The per-voxel functors of tv_primal_march: (X, S, div) -> the new x and the second output; IN_PLACE: the second output
+// replaces the second input.
+struct XS {   // what an update returns: the new x and the second output
+    float x, s;
+};
+
+struct PdhgUpdate {   // x' = x - tau (g - div) [clamped], x-bar = 2 x' - x
+    static constexpr bool IN_PLACE = false;
+    float tau;
+    int nonneg;
+    __device__ __forceinline__ XS operator()(float X, float G, float div) const
+    {
+        float xn = X - tau * (G - div);
+        if (nonneg) xn = xn < 0.0f ? 0.0f : xn;
+        return {xn, (xn + xn) - X};
+    }
+};
+
+struct StochTvUpdate {   // z' = z - div, zb = z' - w div, x' = x - tau zb [clamped]
+    static constexpr bool IN_PLACE = true;
+    float tau, w;
+    int nonneg;
+    __device__ __forceinline__ XS operator()(float X, float Z, float div) const
+    {
+        const float zn = Z - div;
+        const float zb = zn - w * div;
+        float xn = X - tau * zb;
+        if (nonneg) xn = xn < 0.0f ? 0.0f : xn;
+        return {xn, zn};
+    }
+};
+
+// The mirror image of tv_dual_march: the -x neighbour is the previous lane (lane 0 of a wave is the halo lane), the -y
+// neighbour the previous register (one halo row above the tile, f2 only), the -z neighbour the carried registers of the
+// plane before (f3; a z-chunk loads them once for the plane below its first).  f is read and not written; x and s are read
+// and x and s_out written at the lane's own voxels only.  div = (B_1 f_1 + B_2 f_2) + B_3 f_3.
+template <int ND, bool TV, class Update, int RY, int WX, int WY>
+__global__ __launch_bounds__(64 * WX * WY) void tv_primal_march(TvPrimalArgs a, Update update, int gx, int gy, int tiles_per_xcd,
+                                                               int zchunk)
 {
     const int j = (int)blockIdx.x >> 3;
     const int xcd = (int)blockIdx.x & 7;
@@ -214,91 +329,125 @@ __global__ __launch_bounds__(64 * WX * WY) void pdhg_primal_kernel(PdhgArgs a, i
     const int wy0 = __builtin_amdgcn_readfirstlane(y0);
     const int pitch = dx * 4;
     const PlaneIO io{(int)(sz * 4)};
+    const float *s = Update::IN_PLACE ? a.s_out : a.s;   // one pointer where the two are one array
     // slot q = row y0 - 1 + q (q = 0: the halo row), clamped into the plane
     auto rowoff = [&](int q) __attribute__((always_inline)) { return min(max(wy0 - 1 + q, 0), dy - 1) * pitch; };
 
-    // the plane below: q3
+    // the plane below: f3
     float Zp[RY];
 #pragma unroll
     for (int r = 0; r < RY; ++r) Zp[r] = 0.0f;
     if (TV && ND == 3 && zc0 > 0) {
 #pragma unroll
-        for (int r = 0; r < RY; ++r) Zp[r] = io.ld(a.q[ND - 1] + sz * (zc0 - 1), xo, rowoff(r + 1));
+        for (int r = 0; r < RY; ++r) Zp[r] = io.ld(a.f[ND - 1] + sz * (zc0 - 1), xo, rowoff(r + 1));
     }
 
     for (int t = zc0; t < zc1; ++t) {
         __syncthreads();  // lockstep: the waves of a workgroup stay on the same plane
         const bool z_prev = t > 0;
         const size_t pt = sz * t;
-        float Q1[RY], Q2[RY + 1], Q3[RY], X[RY], G[RY];
+        float F1[RY], F2[RY + 1], F3[RY], X[RY], S[RY];
         if (TV) {
 #pragma unroll
-            for (int q = 0; q <= RY; ++q) Q2[q] = io.ld(a.q[1] + pt, xo, rowoff(q));
+            for (int q = 0; q <= RY; ++q) F2[q] = io.ld(a.f[1] + pt, xo, rowoff(q));
         }
 #pragma unroll
         for (int r = 0; r < RY; ++r) {
             if (TV) {
-                Q1[r] = io.ld(a.q[0] + pt, xo, rowoff(r + 1));
-                if (ND == 3) Q3[r] = io.ld(a.q[ND - 1] + pt, xo, rowoff(r + 1));
+                F1[r] = io.ld(a.f[0] + pt, xo, rowoff(r + 1));
+                if (ND == 3) F3[r] = io.ld(a.f[ND - 1] + pt, xo, rowoff(r + 1));
             }
             X[r] = io.ld(a.x + pt, xo, rowoff(r + 1));
-            G[r] = io.ld(a.g + pt, xo, rowoff(r + 1));
+            S[r] = io.ld(s + pt, xo, rowoff(r + 1));
         }
 
-        float Xn[RY], Xb[RY];
+        float Xn[RY], Sn[RY];
 #pragma unroll
         for (int r = 0; r < RY; ++r) {
             float div = 0.0f;
             if (TV) {
                 const bool y_prev = y0 + r > 0;
                 // B_d(a)[i] = a[i] - a[i - e_d], a[i] itself on the first index of the axis
-                const float l = wave_prev(Q1[r]);
-                div = (x_prev ? Q1[r] - l : Q1[r]) + (y_prev ? Q2[r + 1] - Q2[r] : Q2[r + 1]);
+                const float l = wave_prev(F1[r]);
+                div = (x_prev ? F1[r] - l : F1[r]) + (y_prev ? F2[r + 1] - F2[r] : F2[r + 1]);
                 if (ND == 3) {
-                    div = div + (z_prev ? Q3[r] - Zp[r] : Q3[r]);
-                    Zp[r] = Q3[r];
+                    div = div + (z_prev ? F3[r] - Zp[r] : F3[r]);
+                    Zp[r] = F3[r];
                 }
             }
-            float xn = X[r] - a.tau * (G[r] - div);
-            if (a.nonneg) xn = xn < 0.0f ? 0.0f : xn;
-            Xn[r] = xn;
-            Xb[r] = (xn + xn) - X[r];
+            const XS o = update(X[r], S[r], div);
+            Xn[r] = o.x;
+            Sn[r] = o.s;
         }
 
 #pragma unroll
         for (int r = 0; r < RY; ++r) {
             if (emit_lane && y0 + r < dy) {
                 io.st(a.x + pt, xo, rowoff(r + 1), Xn[r]);
-                io.st(a.xb + pt, xo, rowoff(r + 1), Xb[r]);
+                io.st(a.s_out + pt, xo, rowoff(r + 1), Sn[r]);
             }
         }
     }
 }
 
-// The only launch sites of the two marches: TGV's tile, 4 rows per lane, 2 x 2 waves, 63 columns per wave.
-template <int ND, bool ANISO>
-static int pdhg_dual_launch(const PdhgArgs &a, hipStream_t st)
+// ------------------------------------------------------------------------------------------ the host side of the marches
+// The only launch sites of the two marches: TGV's tile, 4 rows per lane, 2 x 2 waves, 63 columns per wave.  `op` names the
+// operator in messages.
+template <int ND, bool ANISO, bool EMIT_E>
+static int tv_dual_launch(const char *op, const TvDualArgs &a, hipStream_t st)
 {
     ZmarchGrid g;
-    if (int rc = zmarch_grid(g, "PDHG", a.dx, a.dy, a.dz, 63, 2, 2, 4, ND == 3)) return rc;
-    pdhg_dual_kernel<ND, ANISO, 4, 2, 2><<<(unsigned)g.blocks, 64 * 2 * 2, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd, g.zchunk);
+    if (int rc = zmarch_grid(g, op, a.dx, a.dy, a.dz, 63, 2, 2, 4, ND == 3)) return rc;
+    tv_dual_march<ND, ANISO, EMIT_E, 4, 2, 2><<<(unsigned)g.blocks, 64 * 2 * 2, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd, g.zchunk);
+    TOMO_LAUNCH_CHECK();
     return TOMO_OK;
 }
 
-template <int ND, bool TV>
-static int pdhg_primal_launch(const PdhgArgs &a, hipStream_t st)
+template <int ND, bool TV, class Update>
+static int tv_primal_launch(const char *op, const TvPrimalArgs &a, Update update, hipStream_t st)
 {
     ZmarchGrid g;
-    if (int rc = zmarch_grid(g, "PDHG", a.dx, a.dy, a.dz, 63, 2, 2, 4, ND == 3)) return rc;
-    pdhg_primal_kernel<ND, TV, 4, 2, 2><<<(unsigned)g.blocks, 64 * 2 * 2, 0, st>>>(a, g.gx, g.gy, g.tiles_per_xcd, g.zchunk);
+    if (int rc = zmarch_grid(g, op, a.dx, a.dy, a.dz, 63, 2, 2, 4, ND == 3)) return rc;
+    tv_primal_march<ND, TV, Update, 4, 2, 2><<<(unsigned)g.blocks, 64 * 2 * 2, 0, st>>>(a, update, g.gx, g.gy, g.tiles_per_xcd, g.zchunk);
+    TOMO_LAUNCH_CHECK();
+    return TOMO_OK;
+}
+
+template <bool EMIT_E>
+static int tv_dual_run(const char *op, const TvDualArgs &a, int nd, int methodTV, hipStream_t st)
+{
+    return nd == 3 ? (methodTV ? tv_dual_launch<3, true, EMIT_E>(op, a, st) : tv_dual_launch<3, false, EMIT_E>(op, a, st))
+                   : (methodTV ? tv_dual_launch<2, true, EMIT_E>(op, a, st) : tv_dual_launch<2, false, EMIT_E>(op, a, st));
+}
+
+// the checks the marches share; `dz` becomes 1 for nd = 2
+static int require_volume(const char *op, int device, int dx, int dy, int &dz, int nd)
+{
+    TOMO_REQUIRE(device >= 0, "The gpu_device must be a positive integer or zero");
+    TOMO_REQUIRE(nd == 2 || nd == 3, "2D or 3D arrays must be provided only");
+    if (nd == 2) dz = 1;
+    TOMO_REQUIRE(dx >= 1 && dy >= 1 && dz >= 1, "%s needs every dimension >= 1", op);
+    TOMO_REQUIRE((size_t)dx * (size_t)dy < ((size_t)1 << 29),
+                 "a plane of %d x %d exceeds the 2 GiB a buffer descriptor of the TV kernels addresses", dx, dy);
     return TOMO_OK;
 }
 
 static bool positive_finite(float v) { return v > 0.0f && std::isfinite(v); }
 
+// no two of the pointers are equal (null pointers excepted)
+static bool distinct(std::initializer_list<const float *> ptrs)
+{
+    for (auto i = ptrs.begin(); i != ptrs.end(); ++i)
+        for (auto k = i + 1; k != ptrs.end(); ++k)
+            if (*i && *i == *k) return false;
+    return true;
+}
+
+static bool known_fidelity(int f) { return f == TOMO_PDHG_LS || f == TOMO_PDHG_L1 || f == TOMO_PDHG_KL; }
+
 }  // namespace
 
-// ------------------------------------------------------------------------------------------ C-ABI
+// ------------------------------------------------------------------------------------------ C-ABI: PDHG
 extern "C" size_t tomo_pdhg_scratch_bytes(int dx, int dy, int dz, int nd)
 {
     if (nd == 2) dz = 1;
@@ -308,77 +457,115 @@ extern "C" size_t tomo_pdhg_scratch_bytes(int dx, int dy, int dz, int nd)
 extern "C" int tomo_pdhg_sino_dual(float *y_dev, const float *r_dev, const float *b_dev, size_t count, int fidelity,
                                    float sigma, void *stream)
 {
-    TOMO_REQUIRE(fidelity == TOMO_PDHG_LS || fidelity == TOMO_PDHG_L1 || fidelity == TOMO_PDHG_KL,
-                 "PDHG: the data term must be TOMO_PDHG_LS, TOMO_PDHG_L1 or TOMO_PDHG_KL");
+    TOMO_REQUIRE(known_fidelity(fidelity), "PDHG: the data term must be TOMO_PDHG_LS, TOMO_PDHG_L1 or TOMO_PDHG_KL");
     TOMO_REQUIRE(positive_finite(sigma), "PDHG: the step size sigma must be positive");
     TOMO_REQUIRE(y_dev && r_dev && b_dev, "NULL data pointer");
     TOMO_REQUIRE(y_dev != r_dev && y_dev != b_dev, "PDHG: the dual array must not alias an array the launch reads");
     if (count == 0) return TOMO_OK;
-    hipStream_t st = as_stream(stream);
-    if (fidelity == TOMO_PDHG_LS) pdhg_sino_launch<TOMO_PDHG_LS>(y_dev, r_dev, b_dev, count, sigma, st);
-    else if (fidelity == TOMO_PDHG_L1) pdhg_sino_launch<TOMO_PDHG_L1>(y_dev, r_dev, b_dev, count, sigma, st);
-    else pdhg_sino_launch<TOMO_PDHG_KL>(y_dev, r_dev, b_dev, count, sigma, st);
+    sino_launch<PdhgSino>(fidelity, y_dev, const_cast<float *>(r_dev) /* PdhgSino does not write it */, b_dev, count, sigma,
+                          as_stream(stream));
     TOMO_LAUNCH_CHECK();
     return TOMO_OK;
 }
 
-// the checks the two marches share; `dz` becomes 1 for nd = 2
-#define PDHG_REQUIRE_VOLUME()                                                                                              \
-    TOMO_REQUIRE(device >= 0, "The gpu_device must be a positive integer or zero");                                        \
-    TOMO_REQUIRE(nd == 2 || nd == 3, "2D or 3D arrays must be provided only");                                             \
-    if (nd == 2) dz = 1;                                                                                                   \
-    TOMO_REQUIRE(dx >= 1 && dy >= 1 && dz >= 1, "PDHG needs every dimension >= 1");                                        \
-    TOMO_REQUIRE((size_t)dx * (size_t)dy < ((size_t)1 << 29),                                                              \
-                 "a plane of %d x %d exceeds the 2 GiB a buffer descriptor of the TV kernels addresses", dx, dy)
-
 extern "C" int tomo_pdhg_tv_dual(int device, const float *xbar_dev, float *q1_dev, float *q2_dev, float *q3_dev, int dx,
                                  int dy, int dz, int nd, float sigma, float lambda, int methodTV, void *stream)
 {
-    PDHG_REQUIRE_VOLUME();
+    if (int rc = require_volume("PDHG", device, dx, dy, dz, nd)) return rc;
     TOMO_REQUIRE(methodTV == 0 || methodTV == 1, "PDHG: methodTV must be 0 (isotropic) or 1 (anisotropic)");
     TOMO_REQUIRE(positive_finite(sigma), "PDHG: the step size sigma must be positive");
     TOMO_REQUIRE(positive_finite(lambda), "PDHG: lambda must be positive");
     TOMO_REQUIRE(xbar_dev && q1_dev && q2_dev && (nd == 2 || q3_dev), "NULL data pointer");
-    TOMO_REQUIRE(q1_dev != xbar_dev && q2_dev != xbar_dev && q3_dev != xbar_dev && q1_dev != q2_dev && q1_dev != q3_dev &&
-                 q2_dev != q3_dev, "PDHG: the dual fields must not alias each other or x-bar");
+    TOMO_REQUIRE(distinct({xbar_dev, q1_dev, q2_dev, q3_dev}), "PDHG: the dual fields must not alias each other or x-bar");
     TOMO_ON_DEVICE(device);
-    PdhgArgs a{};
-    a.xb = const_cast<float *>(xbar_dev);   // read only in this launch
-    a.q[0] = q1_dev; a.q[1] = q2_dev; a.q[2] = nd == 3 ? q3_dev : nullptr;
-    a.dx = dx; a.dy = dy; a.dz = dz;
-    a.sigma = sigma; a.lambda = lambda;
-    hipStream_t st = as_stream(stream);
-    const int rc = nd == 3 ? (methodTV ? pdhg_dual_launch<3, true>(a, st) : pdhg_dual_launch<3, false>(a, st))
-                           : (methodTV ? pdhg_dual_launch<2, true>(a, st) : pdhg_dual_launch<2, false>(a, st));
-    if (rc != TOMO_OK) return rc;
-    TOMO_LAUNCH_CHECK();
-    return TOMO_OK;
+    const TvDualArgs a{xbar_dev, {q1_dev, q2_dev, nd == 3 ? q3_dev : nullptr}, {}, dx, dy, dz, sigma, lambda};
+    return tv_dual_run<false>("PDHG", a, nd, methodTV, as_stream(stream));
 }
 
 extern "C" int tomo_pdhg_primal(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *q1_dev,
                                 const float *q2_dev, const float *q3_dev, int dx, int dy, int dz, int nd, float tau,
                                 int nonneg, void *stream)
 {
-    PDHG_REQUIRE_VOLUME();
+    if (int rc = require_volume("PDHG", device, dx, dy, dz, nd)) return rc;
     TOMO_REQUIRE(positive_finite(tau), "PDHG: the step size tau must be positive");
     TOMO_REQUIRE(x_dev && xbar_dev && g_dev, "NULL data pointer");
     const bool tv = q1_dev != nullptr;
     TOMO_REQUIRE(tv ? (q2_dev && (nd == 2 || q3_dev)) : (!q2_dev && !q3_dev),
                  "PDHG: give every dual field of the TV block (q3 for nd = 3 only) or none");
-    TOMO_REQUIRE(x_dev != xbar_dev && g_dev != x_dev && g_dev != xbar_dev, "PDHG: x, x-bar and g must not alias");
+    TOMO_REQUIRE(distinct({x_dev, xbar_dev, g_dev}), "PDHG: x, x-bar and g must not alias");
     for (const float *q : {q1_dev, q2_dev, q3_dev})
         TOMO_REQUIRE(!q || (q != x_dev && q != xbar_dev), "PDHG: a dual field must not alias an array the launch writes");
     TOMO_ON_DEVICE(device);
-    PdhgArgs a{};
-    a.x = x_dev; a.xb = xbar_dev; a.g = g_dev;
-    a.q[0] = const_cast<float *>(q1_dev); a.q[1] = const_cast<float *>(q2_dev);   // read only in this launch
-    a.q[2] = nd == 3 ? const_cast<float *>(q3_dev) : nullptr;
-    a.dx = dx; a.dy = dy; a.dz = dz;
-    a.tau = tau; a.nonneg = nonneg ? 1 : 0;
+    const TvPrimalArgs a{x_dev, g_dev, xbar_dev, {q1_dev, q2_dev, nd == 3 ? q3_dev : nullptr}, dx, dy, dz};
+    const PdhgUpdate update{tau, nonneg ? 1 : 0};
     hipStream_t st = as_stream(stream);
-    const int rc = nd == 3 ? (tv ? pdhg_primal_launch<3, true>(a, st) : pdhg_primal_launch<3, false>(a, st))
-                           : (tv ? pdhg_primal_launch<2, true>(a, st) : pdhg_primal_launch<2, false>(a, st));
-    if (rc != TOMO_OK) return rc;
+    return nd == 3 ? (tv ? tv_primal_launch<3, true>("PDHG", a, update, st) : tv_primal_launch<3, false>("PDHG", a, update, st))
+                   : (tv ? tv_primal_launch<2, true>("PDHG", a, update, st) : tv_primal_launch<2, false>("PDHG", a, update, st));
+}
+
+// ------------------------------------------------------------------------------------------ C-ABI: SPDHG
+extern "C" size_t tomo_spdhg_scratch_bytes(int dx, int dy, int dz, int nd)
+{
+    if (nd == 2) dz = 1;
+    return (size_t)(2 + 2 * nd) * work_array_bytes((size_t)dx * dy * dz);   // z, delta, q_1..q_nd, e_1..e_nd
+}
+
+extern "C" int tomo_spdhg_sino_dual(float *y_dev, float *r_dev, const float *b_dev, size_t count, int fidelity, float sigma,
+                                    void *stream)
+{
+    TOMO_REQUIRE(known_fidelity(fidelity), "SPDHG: the data term must be TOMO_PDHG_LS, TOMO_PDHG_L1 or TOMO_PDHG_KL");
+    TOMO_REQUIRE(positive_finite(sigma), "SPDHG: the step size sigma must be positive");
+    TOMO_REQUIRE(y_dev && r_dev && b_dev, "NULL data pointer");
+    TOMO_REQUIRE(distinct({y_dev, r_dev, b_dev}), "SPDHG: the dual array, the projection and the data must not alias");
+    if (count == 0) return TOMO_OK;
+    sino_launch<StochSino>(fidelity, y_dev, r_dev, b_dev, count, sigma, as_stream(stream));
     TOMO_LAUNCH_CHECK();
     return TOMO_OK;
+}
+
+extern "C" int tomo_spdhg_primal(float *x_dev, float *z_dev, const float *delta_dev, size_t count, float tau, float w,
+                                 int nonneg, void *stream)
+{
+    TOMO_REQUIRE(positive_finite(tau), "SPDHG: the step size tau must be positive");
+    TOMO_REQUIRE(positive_finite(w), "SPDHG: the extrapolation weight w (1 / the block's probability) must be positive");
+    TOMO_REQUIRE(x_dev && z_dev && delta_dev, "NULL data pointer");
+    TOMO_REQUIRE(distinct({x_dev, z_dev, delta_dev}), "SPDHG: x, z and delta must not alias");
+    if (count == 0) return TOMO_OK;
+    stream3_launch(x_dev, z_dev, delta_dev, count, StochPrimal{tau, w, nonneg ? 1 : 0}, as_stream(stream));
+    TOMO_LAUNCH_CHECK();
+    return TOMO_OK;
+}
+
+extern "C" int tomo_spdhg_tv_dual(int device, const float *x_dev, float *q1_dev, float *q2_dev, float *q3_dev, float *e1_dev,
+                                  float *e2_dev, float *e3_dev, int dx, int dy, int dz, int nd, float sigma, float lambda,
+                                  int methodTV, void *stream)
+{
+    if (int rc = require_volume("SPDHG", device, dx, dy, dz, nd)) return rc;
+    TOMO_REQUIRE(methodTV == 0 || methodTV == 1, "SPDHG: methodTV must be 0 (isotropic) or 1 (anisotropic)");
+    TOMO_REQUIRE(positive_finite(sigma), "SPDHG: the step size sigma must be positive");
+    TOMO_REQUIRE(positive_finite(lambda), "SPDHG: lambda must be positive");
+    TOMO_REQUIRE(x_dev && q1_dev && q2_dev && e1_dev && e2_dev && (nd == 2 || (q3_dev && e3_dev)), "NULL data pointer");
+    if (nd == 2) q3_dev = e3_dev = nullptr;
+    TOMO_REQUIRE(distinct({x_dev, q1_dev, q2_dev, q3_dev, e1_dev, e2_dev, e3_dev}),
+                 "SPDHG: the dual fields and their changes must not alias each other or x");
+    TOMO_ON_DEVICE(device);
+    const TvDualArgs a{x_dev, {q1_dev, q2_dev, q3_dev}, {e1_dev, e2_dev, e3_dev}, dx, dy, dz, sigma, lambda};
+    return tv_dual_run<true>("SPDHG", a, nd, methodTV, as_stream(stream));
+}
+
+extern "C" int tomo_spdhg_tv_primal(int device, float *x_dev, float *z_dev, const float *e1_dev, const float *e2_dev,
+                                    const float *e3_dev, int dx, int dy, int dz, int nd, float tau, float w, int nonneg,
+                                    void *stream)
+{
+    if (int rc = require_volume("SPDHG", device, dx, dy, dz, nd)) return rc;
+    TOMO_REQUIRE(positive_finite(tau), "SPDHG: the step size tau must be positive");
+    TOMO_REQUIRE(positive_finite(w), "SPDHG: the extrapolation weight w (1 / the block's probability) must be positive");
+    TOMO_REQUIRE(x_dev && z_dev && e1_dev && e2_dev && (nd == 2 || e3_dev), "NULL data pointer");
+    if (nd == 2) e3_dev = nullptr;
+    TOMO_REQUIRE(distinct({x_dev, z_dev, e1_dev, e2_dev, e3_dev}), "SPDHG: x, z and the changes of the dual fields must not alias");
+    TOMO_ON_DEVICE(device);
+    const TvPrimalArgs a{x_dev, z_dev, z_dev, {e1_dev, e2_dev, e3_dev}, dx, dy, dz};
+    const StochTvUpdate update{tau, w, nonneg ? 1 : 0};
+    hipStream_t st = as_stream(stream);
+    return nd == 3 ? tv_primal_launch<3, true>("SPDHG", a, update, st) : tv_primal_launch<2, true>("SPDHG", a, update, st);
 }

@@ -1,6 +1,6 @@
-// What the z-march regularisers (tgv_kernels.hip, ndf_kernels.hip, diff4th_kernels.hip, llt_rof_kernels.hip) share: the
-// device helpers of a plane march, its launch grid, the layout of a work array, the early-stopping check and the host
-// driver of an explicit time march.  Everything here is internal to the including translation unit (anonymous namespace).
+// What the z-march operators (tgv_kernels.hip, ndf_kernels.hip, diff4th_kernels.hip, llt_rof_kernels.hip, pdhg_kernels.hip)
+// share: the device helpers of a plane march, its launch grid, the layout of a work array, the early-stopping check and the
+// host driver of an explicit time march.  Everything here is internal to the including translation unit (anonymous namespace).
 //
 // tv_kernels.hip does not include this header and keeps its own PlaneIO, zmarch_grid, tv_skew and tolerance rule: its
 // bytes are pinned by hash (profiles/pmc_traffic.json is keyed to them), so the copy there cannot be replaced by this one.

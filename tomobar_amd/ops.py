@@ -347,12 +347,40 @@ def pdhg_work_arrays(shape, device, tv: bool = True):
     return arrays[0], arrays[1], arrays[2:], lease
 
 
-def _pdhg_dims(t):
-    """(dx, dy, dz, nd) of a volume [nz, ny, nx]: nd = 3 if nz > 1 else 2 (a dimension of 1 elsewhere stays 3D)"""
-    _chk_f32(t, "volume")
-    if t.dim() != 3:
+# What the PDHG and SPDHG wrappers check before a launch.  Aliasing and the ranges of the scalars are the library's to refuse.
+def _pdhg_flat(named):
+    """the element-wise launches: the (name, array) pairs are float32, contiguous, of the size and the device of the first"""
+    first = named[0][1]
+    for name, t in named:
+        _chk_f32(t, name)
+        if t.numel() != first.numel() or t.device != first.device:
+            raise ValueError(f"{name} must have the size and the device of {named[0][0]}")
+
+
+def _pdhg_like(x, named):
+    for name, t in named:
+        _chk_f32(t, name)
+        if tuple(t.shape) != tuple(x.shape) or t.device != x.device:
+            raise ValueError(f"{name} must have the shape and the device of the volume")
+
+
+def _pdhg_fields(x, groups, or_none=False):
+    """(dx, dy, dz, nd) of a volume `x` [nz, ny, nx]: nd = 3 if nz > 1 else 2 (a dimension of 1 elsewhere stays 3D); every
+    (name, arrays) of `groups` holds nd fields like `x` (`or_none`: or is empty)"""
+    _chk_f32(x, "volume")
+    if x.dim() != 3:
         raise ValueError("PDHG volumes are [nz, ny, nx] arrays")
-    return t.shape[2], t.shape[1], t.shape[0], 3 if t.shape[0] > 1 else 2
+    dx, dy, dz, nd = x.shape[2], x.shape[1], x.shape[0], 3 if x.shape[0] > 1 else 2
+    for name, group in groups:
+        if len(group) != nd and not (or_none and len(group) == 0):
+            raise ValueError(f"a volume of {dz} plane{'s' if dz > 1 else ''} takes {nd} dual fields"
+                             f"{' or none' if or_none else ''}, got {len(group)} for {name}")
+        _pdhg_like(x, [(f"{name}{d + 1}", t) for d, t in enumerate(group)])
+    return dx, dy, dz, nd
+
+
+def _pdhg_ptrs(group):
+    return [ptr(t) for t in group] + [ptr(None)] * (3 - len(group))
 
 
 def pdhg_sino_dual(y, r, b, fidelity: str, sigma):
@@ -360,45 +388,29 @@ def pdhg_sino_dual(y, r, b, fidelity: str, sigma):
     `fidelity` ("LS", "L1" or "KL") at y + sigma r, in place; `r` = A x-bar, `b` = the data, `sigma` a float32 scalar."""
     if fidelity not in L.PDHG_FID:
         raise ValueError(f"unknown PDHG data term {fidelity!r}: LS, L1 and KL are supported")
-    for name, t in (("y", y), ("r", r), ("b", b)):
-        _chk_f32(t, name)
-        if t.numel() != y.numel() or t.device != y.device:
-            raise ValueError(f"{name} must have the size and the device of y")
+    _pdhg_flat([("y", y), ("r", r), ("b", b)])
     with _on(y):
         L.check(L.lib().tomo_pdhg_sino_dual(ptr(y), ptr(r), ptr(b), y.numel(), L.PDHG_FID[fidelity], float(sigma), stream_ptr(y)))
     return y
 
 
-def _pdhg_fields(x, named):
-    for name, t in named:
-        _chk_f32(t, name)
-        if tuple(t.shape) != tuple(x.shape) or t.device != x.device:
-            raise ValueError(f"{name} must have the shape and the device of the volume")
-
-
 def pdhg_tv_dual(xbar, q, sigma, lam, methodTV=0):
     """Step 4 of a PDHG iteration (tomo_pdhg_tv_dual): q_d <- q_d + sigma F_d(x-bar), projected (methodTV 0: onto the ball of
     radius `lam`, 1: onto the box), in place; `q` holds nd fields like `xbar`."""
-    dx, dy, dz, nd = _pdhg_dims(xbar)
-    if len(q) != nd:
-        raise ValueError(f"a volume of {dz} plane{'s' if dz > 1 else ''} takes {nd} dual fields, got {len(q)}")
-    _pdhg_fields(xbar, [(f"q{d + 1}", t) for d, t in enumerate(q)])
+    dx, dy, dz, nd = _pdhg_fields(xbar, [("q", q)])
     with _on(xbar):
-        L.check(L.lib().tomo_pdhg_tv_dual(xbar.device.index, ptr(xbar), ptr(q[0]), ptr(q[1]), ptr(q[2] if nd == 3 else None),
-                                          dx, dy, dz, nd, float(sigma), float(lam), int(methodTV), stream_ptr(xbar)))
+        L.check(L.lib().tomo_pdhg_tv_dual(xbar.device.index, ptr(xbar), *_pdhg_ptrs(q), dx, dy, dz, nd, float(sigma), float(lam),
+                                          int(methodTV), stream_ptr(xbar)))
 
 
 def pdhg_primal(x, xbar, g, q, tau, nonneg=False):
     """Step 5 of a PDHG iteration (tomo_pdhg_primal): x' = x - tau (g - div q), clamped at 0 with `nonneg`; x-bar <- 2 x' - x,
     x <- x', in place.  `q`: the nd dual fields, or an empty sequence for no TV block (div q = 0)."""
-    dx, dy, dz, nd = _pdhg_dims(x)
-    if len(q) not in (0, nd):
-        raise ValueError(f"a volume of {dz} plane{'s' if dz > 1 else ''} takes {nd} dual fields or none, got {len(q)}")
-    _pdhg_fields(x, [("xbar", xbar), ("g", g)] + [(f"q{d + 1}", t) for d, t in enumerate(q)])
-    qp = [ptr(t) for t in q] + [ptr(None)] * (3 - len(q))
+    dx, dy, dz, nd = _pdhg_fields(x, [("q", q)], or_none=True)
+    _pdhg_like(x, [("xbar", xbar), ("g", g)])
     with _on(x):
-        L.check(L.lib().tomo_pdhg_primal(x.device.index, ptr(x), ptr(xbar), ptr(g), qp[0], qp[1], qp[2], dx, dy, dz, nd,
-                                         float(tau), int(bool(nonneg)), stream_ptr(x)))
+        L.check(L.lib().tomo_pdhg_primal(x.device.index, ptr(x), ptr(xbar), ptr(g), *_pdhg_ptrs(q), dx, dy, dz, nd, float(tau),
+                                         int(bool(nonneg)), stream_ptr(x)))
 
 
 # ----------------------------------------------------------------------------- SPDHG (docs/kernels/spdhg.md)
@@ -414,84 +426,44 @@ def spdhg_work_arrays(shape, device, tv: bool = True):
     return arrays[0], arrays[1], arrays[2:2 + nd] if tv else [], arrays[2 + nd:] if tv else [], lease
 
 
-def _spdhg_positive(value, name):
-    if not float(value) > 0.0:
-        raise ValueError(f"SPDHG: {name} must be positive")
-    return float(value)
-
-
-def _spdhg_distinct(named):
-    """no two of the (name, tensor) pairs start at the same address"""
-    seen = {}
-    for name, t in named:
-        if t.data_ptr() in seen:
-            raise ValueError(f"{name} must not alias {seen[t.data_ptr()]}")
-        seen[t.data_ptr()] = name
-
-
-def _spdhg_flat(first, named):
-    """the element-wise launches: float32, contiguous, the size and the device of `first`, no aliasing"""
-    for name, t in named:
-        _chk_f32(t, name)
-        if t.numel() != first.numel() or t.device != first.device:
-            raise ValueError(f"{name} must have the size and the device of {named[0][0]}")
-    _spdhg_distinct(named)
-
-
 def spdhg_sino_dual(y, r, b, fidelity: str, sigma):
     """Step 2 of an SPDHG subset update (tomo_spdhg_sino_dual): v = PDHG's sinogram dual of the data term `fidelity` ("LS",
     "L1" or "KL") on (y, r, b); `r` <- v - y, `y` <- v, both in place.  `r` = A_j x, `b` = the subset's data, `sigma` a
     float32 scalar.  Returns (y, r)."""
     if fidelity not in L.PDHG_FID:
         raise ValueError(f"unknown SPDHG data term {fidelity!r}: LS, L1 and KL are supported")
-    _spdhg_flat(y, [("y", y), ("r", r), ("b", b)])
-    sigma = _spdhg_positive(sigma, "the step size sigma")
+    _pdhg_flat([("y", y), ("r", r), ("b", b)])
     with _on(y):
-        L.check(L.lib().tomo_spdhg_sino_dual(ptr(y), ptr(r), ptr(b), y.numel(), L.PDHG_FID[fidelity], sigma, stream_ptr(y)))
+        L.check(L.lib().tomo_spdhg_sino_dual(ptr(y), ptr(r), ptr(b), y.numel(), L.PDHG_FID[fidelity], float(sigma), stream_ptr(y)))
     return y, r
 
 
 def spdhg_primal(x, z, delta, tau, w, nonneg=False):
     """Step 4 of an SPDHG subset update (tomo_spdhg_primal): z' = z + delta, zb = z' + w delta, x' = x - tau zb, clamped at 0
     with `nonneg`; `x` <- x', `z` <- z', in place.  `delta` = A_j^T of the dual's change, `w` = 1 / the block's probability."""
-    _spdhg_flat(x, [("x", x), ("z", z), ("delta", delta)])
-    tau, w = _spdhg_positive(tau, "the step size tau"), _spdhg_positive(w, "the weight w")
+    _pdhg_flat([("x", x), ("z", z), ("delta", delta)])
     with _on(x):
-        L.check(L.lib().tomo_spdhg_primal(ptr(x), ptr(z), ptr(delta), x.numel(), tau, w, int(bool(nonneg)), stream_ptr(x)))
-
-
-def _spdhg_fields(x, fields, what):
-    dx, dy, dz, nd = _pdhg_dims(x)
-    for name, group in fields:
-        if len(group) != nd:
-            raise ValueError(f"a volume of {dz} plane{'s' if dz > 1 else ''} takes {nd} {what} fields, got {len(group)} for {name}")
-    named = [(f"{name}{d + 1}", t) for name, group in fields for d, t in enumerate(group)]
-    _pdhg_fields(x, named)
-    return dx, dy, dz, nd, named
+        L.check(L.lib().tomo_spdhg_primal(ptr(x), ptr(z), ptr(delta), x.numel(), float(tau), float(w), int(bool(nonneg)),
+                                          stream_ptr(x)))
 
 
 def spdhg_tv_dual(x, q, e, sigma, lam, methodTV=0):
     """Step 1 of an SPDHG TV update (tomo_spdhg_tv_dual): p_d = q_d + sigma F_d(x), projected (methodTV 0: onto the ball of
     radius `lam`, 1: onto the box); `e` <- p - q, `q` <- p.  `q` and `e` hold nd fields like `x` each."""
-    dx, dy, dz, nd, named = _spdhg_fields(x, [("q", q), ("e", e)], "dual")
-    _spdhg_distinct([("x", x)] + named)
-    sigma, lam = _spdhg_positive(sigma, "the step size sigma"), _spdhg_positive(lam, "lambda")
-    p = [ptr(t) for t in q] + [ptr(None)] * (3 - nd) + [ptr(t) for t in e] + [ptr(None)] * (3 - nd)
+    dx, dy, dz, nd = _pdhg_fields(x, [("q", q), ("e", e)])
     with _on(x):
-        L.check(L.lib().tomo_spdhg_tv_dual(x.device.index, ptr(x), *p, dx, dy, dz, nd, sigma, lam, int(methodTV), stream_ptr(x)))
+        L.check(L.lib().tomo_spdhg_tv_dual(x.device.index, ptr(x), *_pdhg_ptrs(q), *_pdhg_ptrs(e), dx, dy, dz, nd, float(sigma),
+                                           float(lam), int(methodTV), stream_ptr(x)))
 
 
 def spdhg_tv_primal(x, z, e, tau, w, nonneg=False):
     """Steps 2 and 3 of an SPDHG TV update (tomo_spdhg_tv_primal): div = sum_d B_d(e_d); z' = z - div, zb = z' - w div,
     x' = x - tau zb, clamped at 0 with `nonneg`; `x` <- x', `z` <- z', in place.  `e`: the nd fields spdhg_tv_dual left."""
-    dx, dy, dz, nd, named = _spdhg_fields(x, [("e", e)], "dual")
-    _pdhg_fields(x, [("z", z)])
-    _spdhg_distinct([("x", x), ("z", z)] + named)
-    tau, w = _spdhg_positive(tau, "the step size tau"), _spdhg_positive(w, "the weight w")
-    p = [ptr(t) for t in e] + [ptr(None)] * (3 - nd)
+    dx, dy, dz, nd = _pdhg_fields(x, [("e", e)])
+    _pdhg_like(x, [("z", z)])
     with _on(x):
-        L.check(L.lib().tomo_spdhg_tv_primal(x.device.index, ptr(x), ptr(z), *p, dx, dy, dz, nd, tau, w, int(bool(nonneg)),
-                                             stream_ptr(x)))
+        L.check(L.lib().tomo_spdhg_tv_primal(x.device.index, ptr(x), ptr(z), *_pdhg_ptrs(e), dx, dy, dz, nd, float(tau), float(w),
+                                             int(bool(nonneg)), stream_ptr(x)))
 
 
 def _wavelet_args(data, out, mix):

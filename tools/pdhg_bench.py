@@ -18,6 +18,7 @@ profiles/archive/r4b_hbm_copy_probe.txt); give --shapes with the ONE shape the p
 import argparse
 import json
 import os
+import re
 import statistics
 import sys
 
@@ -25,8 +26,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 COPY_RATE_GBPS = 6200.0
-GROUPS = (("pdhg_sino", "sino_dual"), ("pdhg_dual", "tv_dual"), ("pdhg_primal", "primal"), ("bp_", "bp"), ("fp_", "fp"),
-          ("transpose64", "fp"))   # the in-plane transpose in front of the forward projector
+# regular expressions on the kernel names of csrc/pdhg_kernels.hip, which SPDHG's launches share: the functor names the launch,
+# the dual march's third template argument says whether it also writes e (SPDHG) or not (PDHG)
+GROUPS = (("PdhgSino", "sino_dual"), (r"tv_dual_march<\d, \w+, false,", "tv_dual"), ("PdhgUpdate", "primal"), ("bp_", "bp"),
+          ("fp_", "fp"), ("transpose64", "fp"))   # the in-plane transpose in front of the forward projector
 
 
 def bench(n, na, args):
@@ -71,7 +74,7 @@ def split(db_path, n, na):
     rows = sqlite3.connect(db_path).execute("select name, count(*), sum(duration) from kernels group by name").fetchall()
     agg = {}
     for name, calls, total in rows:
-        group = next((g for key, g in GROUPS if key in name), "other")
+        group = next((g for key, g in GROUPS if re.search(key, name)), "other")
         c, t = agg.get(group, (0, 0.0))
         agg[group] = (c + calls, t + total / 1e6)
     whole = sum(t for _, t in agg.values()) or 1.0

@@ -22,6 +22,7 @@ profiles/archive/r4b_hbm_copy_probe.txt); give --shapes and --subsets with the O
 import argparse
 import json
 import os
+import re
 import statistics
 import sys
 
@@ -30,8 +31,11 @@ sys.path.insert(0, ROOT)
 
 COPY_RATE_GBPS = 6200.0
 NEW = ("sino_dual", "primal", "tv_dual", "tv_primal")
-GROUPS = (("spdhg_sino", "sino_dual"), ("spdhg_primal", "primal"), ("spdhg_tv_dual", "tv_dual"), ("spdhg_tv_primal", "tv_primal"),
-          ("bp_", "bp"), ("fp_", "fp"), ("transpose64", "fp"))   # the in-plane transpose in front of the forward projector
+# regular expressions on the kernel names of csrc/pdhg_kernels.hip, which PDHG's launches share: the functor names the launch,
+# the dual march's third template argument says whether it also writes e (SPDHG) or not (PDHG)
+GROUPS = (("StochSino", "sino_dual"), ("StochPrimal", "primal"), (r"tv_dual_march<\d, \w+, true,", "tv_dual"),
+          ("StochTvUpdate", "tv_primal"), ("bp_", "bp"), ("fp_", "fp"),
+          ("transpose64", "fp"))   # the in-plane transpose in front of the forward projector
 
 
 def bench(n, na, args):
@@ -89,7 +93,7 @@ def split(db_path, n, na, subsets):
     rows = sqlite3.connect(db_path).execute("select name, count(*), sum(duration) from kernels group by name").fetchall()
     agg = {}
     for name, calls, total in rows:
-        group = next((g for key, g in GROUPS if key in name), "other")
+        group = next((g for key, g in GROUPS if re.search(key, name)), "other")
         c, t = agg.get(group, (0, 0.0))
         agg[group] = (c + calls, t + total / 1e6)
     whole = sum(t for _, t in agg.values()) or 1.0

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 import _diff4th_oracle
+from _guarded import guarded
 import _llt_rof_oracle
 import _ndf_oracle
 from _tgv_oracle import phantom
@@ -28,13 +29,15 @@ def same_bits(got, want, what):
 
 
 def run_op(call, f_host):
-    """call(input tensor, NaN-filled output tensor) on the GPU; the input's bits are checked afterwards.  Returns the output
-    on the host and what `call` returned."""
-    x = torch.from_numpy(f_host).cuda()
-    out = torch.full_like(x, float("nan"))
-    res = call(x, out)
-    assert np.array_equal(host(x).view(np.uint32), f_host.view(np.uint32)), "the input was written"
-    return host(out), res
+    """call(input tensor, NaN-filled output tensor) on the GPU, both inside guard bands (tests/_guarded.py: a load from
+    outside the input returns NaN); the input's bits and both arrays' bands are checked afterwards.  Returns the output on
+    the host and what `call` returned."""
+    x, out = guarded(f_host), guarded(f_host.shape)
+    res = call(x.view, out.view)
+    assert x.unchanged(), "the input was written"
+    x.check(("the input", f_host.shape))
+    out.check(("the output", f_host.shape))
+    return out.host(), res
 
 
 # ------------------------------------------------------------------------------------------------ the operators

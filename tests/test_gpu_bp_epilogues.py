@@ -6,11 +6,17 @@ accumulates in the same order, so every comparison is array_equal.
 Shapes: the kernels own 32 x 16 x 16 voxel bricks.  17 x 64 x 64 has whole bricks (the dwordx4 hand-over through LDS) and a
 ragged z-brick; the same with every volume array one float off 16-byte alignment stores whole bricks through the scalar
 path; 5 x 37 x 37 has ragged bricks only."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from _guarded import guarded  # noqa: E402
 
 NA = 9
 F32 = np.float32
@@ -43,13 +49,13 @@ def restate(form, g, i0, i1=None, i2=None, nonneg=False, relax_on=False):
     return z, z + i1
 
 
-def on_device(arr, misaligned):
-    """A device copy of `arr`; misaligned: a [1:] view of an allocation one float longer (4 bytes off 16-byte alignment)."""
-    flat = torch.full((arr.size + 1,), float("nan"), device="cuda")
-    view = (flat[1:] if misaligned else flat[:-1]).view(arr.shape)
-    view.copy_(torch.from_numpy(arr))
-    assert (view.data_ptr() % 16 != 0) == misaligned
-    return view
+def on_device(arr, misaligned, made):
+    """A device copy of `arr` inside guard bands (tests/_guarded.py); misaligned: 4 bytes off 16-byte alignment (shift=1).
+    The guarded object joins `made`, whose bands the test checks at its end."""
+    g = guarded(arr, shift=1 if misaligned else 0)
+    assert (g.view.data_ptr() % 16 != 0) == misaligned
+    made.append(g)
+    return g.view
 
 
 def quad_interleaved(r):
@@ -82,8 +88,9 @@ def test_fused_epilogues_equal_one_restatement(adjoint, nz, n, nu, misaligned, l
     H.set_residual_layout(layout)
     assert H.residual_layout() == layout
     res = torch.from_numpy(quad_interleaved(r) if layout == "zquad" else r).cuda()
-    dev = lambda a: on_device(a, misaligned)
-    blank = lambda: on_device(np.full((nz, n, n), np.nan, np.float32), misaligned)
+    made = []
+    dev = lambda a: on_device(a, misaligned, made)
+    blank = lambda: on_device(np.full((nz, n, n), np.nan, np.float32), misaligned, made)
     try:
         for nonneg in (False, True):
             (X,) = restate("fista", g, x, nonneg=nonneg)
@@ -103,6 +110,8 @@ def test_fused_epilogues_equal_one_restatement(adjoint, nz, n, nu, misaligned, l
                 assert np.array_equal(host(z_d), Z), (nonneg, relax_on)
                 assert np.array_equal(host(zu_d), ZU), (nonneg, relax_on)
         assert H.kernel_path("bp").startswith("matched" if adjoint == "matched" else "brick")
+        for k, g in enumerate(made):
+            g.check((adjoint, layout, "volume array", k))
     finally:
         H.set_residual_layout("planar")
 

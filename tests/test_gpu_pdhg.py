@@ -15,31 +15,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import _cupy_standin  # noqa: E402
+from _guarded import guarded  # noqa: E402
 import _matched_bp_oracle as M  # noqa: E402
 import _pdhg_cases as K  # noqa: E402
 import _pdhg_oracle as P  # noqa: E402
 
-GUARD = 64   # floats of sentinel on either side of every array a kernel writes
-SENTINEL = 12345.0
-
-
 def host(t):
     torch.cuda.synchronize()
     return t.detach().cpu().numpy()
-
-
-def guarded(a):
-    """(a device copy of `a` inside a larger buffer, the buffer): the floats around the copy hold SENTINEL"""
-    a = np.ascontiguousarray(a, np.float32)
-    buf = torch.full((a.size + 2 * GUARD,), SENTINEL, dtype=torch.float32, device="cuda")
-    view = buf[GUARD:GUARD + a.size].view(a.shape)
-    view.copy_(torch.from_numpy(a))
-    return view, buf
-
-
-def guards_intact(buf):
-    h = host(buf)
-    return bool(np.all(h[:GUARD] == SENTINEL) and np.all(h[-GUARD:] == SENTINEL))
 
 
 def _same_bits(got, want, what):
@@ -74,11 +57,11 @@ def test_sino_dual_equals_the_oracle(shape, fidelity, sigma):
     assert want.dtype == np.float32
     if fidelity == "L1" and y.size > 8:
         assert (np.abs(want) == 1).any() and (np.abs(want) < 1).any()
-    yd, buf = guarded(y)
-    rd, bd = torch.from_numpy(r).cuda(), torch.from_numpy(b).cuda()
+    yg, rg, bg = guarded(y), guarded(r), guarded(b)
+    yd, rd, bd = yg.view, rg.view, bg.view
     assert ops.pdhg_sino_dual(yd, rd, bd, fidelity, sigma) is yd
     _same_bits(host(yd), want, (shape, fidelity, float(sigma)))
-    assert guards_intact(buf) and np.array_equal(host(rd), r) and np.array_equal(host(bd), b)
+    assert yg.intact() and rg.intact() and bg.intact() and rg.unchanged() and bg.unchanged()
     # two applications: the dual is really updated in place
     ops.pdhg_sino_dual(yd, rd, bd, fidelity, sigma)
     _same_bits(host(yd), P.sino_dual(want, r, b, fidelity, sigma), (shape, fidelity, "second application"))
@@ -114,7 +97,8 @@ def test_sino_dual_refuses_what_it_cannot_run():
 def test_tv_dual_and_primal_equal_the_oracle(shape):
     from tomobar_amd import ops
     g_host = K.march_g(shape)
-    g = torch.from_numpy(g_host).cuda()
+    gg = guarded(g_host)
+    g = gg.view
     nd = 3 if shape[0] > 1 else 2
     for kind in ("noise", "terraces"):
         x0 = K.march_input(kind, shape)
@@ -124,10 +108,10 @@ def test_tv_dual_and_primal_equal_the_oracle(shape):
                 want, share = K.march_oracle(kind, shape, methodTV, nonneg)
                 if kind == "noise":   # a condition on the inputs: both branches of the projection run
                     assert 0.1 <= share <= 0.9, (shape, methodTV, share)
-                x, xbuf = guarded(x0)
-                xbar, bbuf = guarded(x0)
+                xg, bg = guarded(x0), guarded(x0)
+                x, xbar = xg.view, bg.view
                 qs = [guarded(np.zeros(shape, np.float32)) for _ in range(nd)]
-                q = [v for v, _ in qs]
+                q = [b.view for b in qs]
                 for n in range(1, max(K.MARCH_COUNTS) + 1):
                     ops.pdhg_tv_dual(xbar, q, K.MARCH_SIGMA, lam, methodTV)
                     ops.pdhg_primal(x, xbar, g, q, K.MARCH_TAU, nonneg)
@@ -138,19 +122,19 @@ def test_tv_dual_and_primal_equal_the_oracle(shape):
                         _same_bits(host(xbar), wb, what + ("x-bar",))
                         for d in range(nd):
                             _same_bits(host(q[d]), wq[d], what + (f"q{d + 1}",))
-                assert all(guards_intact(b) for b in [xbuf, bbuf] + [b for _, b in qs]), (shape, kind, "a guard was written")
-                assert np.array_equal(host(g), g_host), "g was written"
+                assert all(b.intact() for b in [xg, bg, gg] + qs), (shape, kind, "a guard was written")
+                assert gg.unchanged(), "g was written"
     # without the TV block: div q = 0
     x0 = K.march_input("noise", shape) - np.float32(0.4)
     for nonneg in (0, 1):
         want = P.march_steps(x0, g_host, K.MARCH_SIGMA, K.MARCH_TAU, None, 0, nonneg, (3,))[3]
-        x, xbuf = guarded(x0)
-        xbar, bbuf = guarded(x0)
+        xg, bg = guarded(x0), guarded(x0)
+        x, xbar = xg.view, bg.view
         for _ in range(3):
             ops.pdhg_primal(x, xbar, g, [], K.MARCH_TAU, nonneg)
         _same_bits(host(x), want[0], (shape, "no TV", nonneg, "x"))
         _same_bits(host(xbar), want[1], (shape, "no TV", nonneg, "x-bar"))
-        assert guards_intact(xbuf) and guards_intact(bbuf)
+        assert xg.intact() and bg.intact() and gg.intact() and gg.unchanged()
 
 
 def test_marches_refuse_what_they_cannot_run():

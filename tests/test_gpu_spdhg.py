@@ -15,33 +15,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import _cupy_standin  # noqa: E402
+from _guarded import guarded  # noqa: E402
 import _pdhg_cases as K  # noqa: E402
 import _pdhg_oracle as P  # noqa: E402
 import _spdhg_cases as SK  # noqa: E402
 import _spdhg_oracle as S  # noqa: E402
 
-GUARD = 64   # floats of sentinel on either side of every array a kernel writes
-SENTINEL = 12345.0
-
-
 def host(t):
     torch.cuda.synchronize()
     return t.detach().cpu().numpy()
-
-
-def guarded(a, shift=0):
-    """(a device copy of `a` inside a larger buffer, the buffer): the floats around the copy hold SENTINEL; `shift` moves
-    the copy that many floats further into the buffer (1: four bytes past a 16-byte boundary)"""
-    a = np.ascontiguousarray(a, np.float32)
-    buf = torch.full((a.size + 2 * GUARD + shift,), SENTINEL, dtype=torch.float32, device="cuda")
-    view = buf[GUARD + shift:GUARD + shift + a.size].view(a.shape)
-    view.copy_(torch.from_numpy(a))
-    return view, buf
-
-
-def guards_intact(buf, shift=0):
-    h = host(buf)
-    return bool(np.all(h[:GUARD + shift] == SENTINEL) and np.all(h[-GUARD:] == SENTINEL))
 
 
 def _same_bits(got, want, what):
@@ -76,14 +58,13 @@ def test_sino_dual_equals_the_oracle(shape, fidelity, sigma):
     assert want_y.dtype == want_d.dtype == np.float32
     if fidelity == "L1" and y.size > 8:
         assert (np.abs(want_y) == 1).any() and (np.abs(want_y) < 1).any()
-    yd, ybuf = guarded(y)
-    rd, rbuf = guarded(r)
-    bd = torch.from_numpy(b).cuda()
+    yg, rg, bg = guarded(y), guarded(r), guarded(b)
+    yd, rd, bd = yg.view, rg.view, bg.view
     out = ops.spdhg_sino_dual(yd, rd, bd, fidelity, sigma)
     assert out[0] is yd and out[1] is rd
     _same_bits(host(yd), want_y, (shape, fidelity, float(sigma), "y"))
     _same_bits(host(rd), want_d, (shape, fidelity, float(sigma), "d"))
-    assert guards_intact(ybuf) and guards_intact(rbuf) and np.array_equal(host(bd), b)
+    assert yg.intact() and rg.intact() and bg.intact() and bg.unchanged()
     # a second application on a fresh projection: the dual is really updated in place
     r2 = (r[::-1] if r.ndim == 1 else r[::-1, ::-1]).copy()
     rd.copy_(torch.from_numpy(r2))
@@ -91,7 +72,7 @@ def test_sino_dual_equals_the_oracle(shape, fidelity, sigma):
     want_y2, want_d2 = S.sino_step(want_y, r2, b, fidelity, sigma)
     _same_bits(host(yd), want_y2, (shape, fidelity, "second application", "y"))
     _same_bits(host(rd), want_d2, (shape, fidelity, "second application", "d"))
-    assert guards_intact(ybuf) and guards_intact(rbuf)
+    assert yg.intact() and rg.intact() and bg.intact() and bg.unchanged()
 
 
 @pytest.mark.parametrize("fidelity", P.FIDELITIES)
@@ -100,13 +81,14 @@ def test_sino_dual_on_arrays_that_are_not_16_byte_aligned(fidelity):
     from tomobar_amd import ops
     y, r, b = _sino_inputs((4100,))
     sigma = np.float32(0.4)
-    (yd, ybuf), (rd, rbuf), (bd, _) = (guarded(a, shift=1) for a in (y, r, b))
+    yg, rg, bg = (guarded(a, shift=1) for a in (y, r, b))
+    yd, rd, bd = yg.view, rg.view, bg.view
     assert all(t.data_ptr() % 16 == 4 and t.is_contiguous() for t in (yd, rd, bd))
     ops.spdhg_sino_dual(yd, rd, bd, fidelity, sigma)
     want_y, want_d = S.sino_step(y, r, b, fidelity, sigma)
     _same_bits(host(yd), want_y, (fidelity, "y"))
     _same_bits(host(rd), want_d, (fidelity, "d"))
-    assert guards_intact(ybuf, 1) and guards_intact(rbuf, 1) and np.array_equal(host(bd), b)
+    assert yg.intact() and rg.intact() and bg.intact() and bg.unchanged()
 
 
 # ------------------------------------------------------------------------------------------------ subset step 4
@@ -133,12 +115,13 @@ def test_streaming_primal_equals_the_oracle(shape, nonneg, w, shift):
     if x.size > 8:   # a condition on the inputs: the clamp acts on some voxels and not on others
         free = S.primal_step(x, z, delta, tau, w, 0)[0]
         assert (free < 0).any() and (free > 0).any()
-    (xd, xbuf), (zd, zbuf), (dd, _) = (guarded(a, shift=shift) for a in (x, z, delta))
+    xg, zg, dg = (guarded(a, shift=shift) for a in (x, z, delta))
+    xd, zd, dd = xg.view, zg.view, dg.view
     assert all(t.data_ptr() % 16 == 4 * shift for t in (xd, zd, dd))
     ops.spdhg_primal(xd, zd, dd, tau, w, nonneg)
     _same_bits(host(xd), want_x, (shape, nonneg, float(w), "x"))
     _same_bits(host(zd), want_z, (shape, nonneg, float(w), "z"))
-    assert guards_intact(xbuf, shift) and guards_intact(zbuf, shift) and np.array_equal(host(dd), delta)
+    assert xg.intact() and zg.intact() and dg.intact() and dg.unchanged()
     ops.spdhg_primal(xd, zd, dd, tau, w, nonneg)
     want_x, want_z = S.primal_step(want_x, want_z, delta, tau, w, nonneg)
     _same_bits(host(xd), want_x, (shape, nonneg, float(w), "second application", "x"))
@@ -159,11 +142,11 @@ def test_tv_pair_equals_the_oracle(shape):
                 want, share = SK.tv_oracle(kind, shape, methodTV, nonneg)
                 if kind == "noise":   # a condition on the inputs: both branches of the projection run
                     assert 0.1 <= share <= 0.9, (shape, methodTV, share)
-                x, xbuf = guarded(x0)
-                z, zbuf = guarded(z0)
+                xg, zg = guarded(x0), guarded(z0)
+                x, z = xg.view, zg.view
                 qs = [guarded(np.zeros(shape, np.float32)) for _ in range(nd)]
                 es = [guarded(np.full(shape, 7.0, np.float32)) for _ in range(nd)]   # e is written, never read first
-                q, e = [v for v, _ in qs], [v for v, _ in es]
+                q, e = [b.view for b in qs], [b.view for b in es]
                 for n in range(1, max(K.MARCH_COUNTS) + 1):
                     ops.spdhg_tv_dual(x, q, e, K.MARCH_SIGMA, lam, methodTV)
                     if n == 1:
@@ -177,8 +160,7 @@ def test_tv_pair_equals_the_oracle(shape):
                         for d in range(nd):
                             _same_bits(host(q[d]), wq[d], what + (f"q{d + 1}",))
                             _same_bits(host(e[d]), we[d], what + (f"e{d + 1}",))
-                bufs = [xbuf, zbuf] + [b for _, b in qs] + [b for _, b in es]
-                assert all(guards_intact(b) for b in bufs), (shape, kind, "a guard was written")
+                assert all(b.intact() for b in [xg, zg] + qs + es), (shape, kind, "a guard was written")
 
 
 # ------------------------------------------------------------------------------------------------ refusals, the block

@@ -38,21 +38,34 @@ def _worker(rank, world, port, case):
     try:
         _seams()
         from oracle import tomo_oracle as O
-        from tomobar_amd.slab import SlabComm, pd_tv_slab, rof_tv_slab, slab_bounds
+        from tomobar_amd.slab import SlabComm, pd_launch_plan, pd_tv_slab, rof_tv_slab, slab_bounds
         comm = SlabComm(rank, world)
         nz, dy, dx = case["shape"]
         rng = np.random.default_rng(5)
         vol = (rng.random((nz, dy, dx)) * 0.3 + (np.indices((nz, dy, dx))[2] > dx // 2)).astype(np.float32)
         z0, z1 = slab_bounds(nz, world, rank)
         mine = torch.from_numpy(vol[z0:z1].copy())
-        if case["kind"] == "pd":
-            want = O.pd_tv(vol, 0.04, case["iters"], case["mtv"], case["nn"], 8.0, case["half"])
-            got = pd_tv_slab(mine, comm, 0.04, case["iters"], case["mtv"], case["nn"], 8.0, case["half"],
-                             pair_fn=O.pd_pair_slab, step_fn=O.pd_step_slab)
+        iters = case["iters"]
+        if iters == 0:
+            want = vol   # nothing is computed: the result is the input
+        elif case["kind"] == "pd":
+            want = O.pd_tv(vol, 0.04, iters, case["mtv"], case["nn"], 8.0, case["half"])
         else:
-            want = O.rof_tv(vol, 0.05, case["iters"], 0.005, case["half"])
-            got = rof_tv_slab(mine, comm, 0.05, case["iters"], 0.005, case["half"], step_fn=O.rof_step_slab)
-        assert np.array_equal(got.numpy(), want[z0:z1]), (rank, np.abs(got.numpy() - want[z0:z1]).max())
+            want = O.rof_tv(vol, 0.05, iters, 0.005, case["half"])
+        for overlap in (True, False):
+            before = comm.stats["exchanges"]
+            if case["kind"] == "pd":
+                got = pd_tv_slab(mine, comm, 0.04, iters, case["mtv"], case["nn"], 8.0, case["half"],
+                                 pair_fn=O.pd_pair_slab, step_fn=O.pd_step_slab, overlap=overlap)
+                launches = len(pd_launch_plan(iters, case["half"]))
+            else:
+                got = rof_tv_slab(mine, comm, 0.05, iters, 0.005, case["half"], step_fn=O.rof_step_slab, overlap=overlap)
+                launches = iters
+            assert np.array_equal(got.numpy(), want[z0:z1]), (rank, overlap, np.abs(got.numpy() - want[z0:z1]).max())
+            assert got.data_ptr() != mine.data_ptr(), "the result is a copy, never the caller's tensor"
+            # one exchange before the first launch and one after every launch but the last, in either schedule; none at all
+            # when there is no launch
+            assert comm.stats["exchanges"] - before == launches, (rank, overlap, comm.stats, launches)
         # one message each way per neighbour and exchange, whatever the number of arrays (U, P1, P2, P3) it carries
         st = comm.timing_summary()
         assert st["messages"] == 2 * st["exchanges"] * (int(comm.has_lo) + int(comm.has_hi)) or world == 1, st
@@ -73,6 +86,9 @@ CASES = [
     dict(kind="rof", shape=(9, 7, 11), iters=6, half=False),
     dict(kind="rof", shape=(22, 6, 10), iters=5, half=False),   # long enough for the overlapped schedule
     dict(kind="rof", shape=(10, 5, 9), iters=4, half=True),
+    # no iteration: no launch, so no exchange either (every rank sees the same count), and the result is a copy of the input
+    dict(kind="pd", shape=(9, 6, 11), iters=0, mtv=0, nn=0, half=False),
+    dict(kind="rof", shape=(9, 6, 11), iters=0, half=False),
 ]
 
 

@@ -20,7 +20,8 @@ element-wise glue need no communication.  What does:
 ``SlabComm`` wraps ``torch.distributed`` (backend "nccl" = RCCL on ROCm, "gloo" in the CPU tests); over a gloo group the
 ghost planes can also travel device to device through HIP IPC regions (``transport``, tomobar_amd/halo_ipc.py).  The TV drivers are
 written against small "step" callables so that the same halo logic runs on the HIP kernels and, in the CPU tests, on
-the oracle's single-iteration functions.
+the oracle's single-iteration functions.  That logic is one loop, ``_run_slab`` (the overlap of exchange and compute is
+explained there); each operator's state class (``PdSlab``, ``RofSlab``, ``MarchSlab``) tells it what a launch is.
 """
 
 from __future__ import annotations
@@ -416,7 +417,51 @@ def pd_launch_plan(iterations: int, half: bool, kmax: Optional[int] = None):
     return plan
 
 
-class PdSlab:
+class _SlabState:
+    """What PdSlab, RofSlab and MarchSlab share: how they come by their work arrays, and the schedule protocol `_run_slab`
+    drives.  The defaults are those of an operator that runs one iteration per launch and addresses its ping-pong arrays by
+    the iteration number (``source``, ``step``, ``send_*`` / ``recv_*`` of the subclass)."""
+
+    def _arrays(self, specs, device, alloc):
+        """One array per (shape, dtype) of `specs`.  `alloc(specs, device)` (the HIP drivers pass ops.placed_empty) gives
+        them as views of one block the library places in HBM (docs/kernels/placement.md) with a lease on it; default: one
+        allocation of the caller's allocator each."""
+        self.lease = None
+        self.placed = alloc is not None   # the arrays belong to the library's block
+        if alloc is not None:
+            arrs, self.lease = alloc(specs, device)
+        else:
+            arrs = [torch.empty(sh, dtype=dt, device=device) for sh, dt in specs]
+        return arrs
+
+    def local(self, t: torch.Tensor) -> torch.Tensor:
+        return t[self.lo:self.lo + self.nzl]
+
+    def plan(self, iterations):
+        """the iterations each launch runs"""
+        return [1] * int(iterations)
+
+    def splits(self, k) -> bool:
+        """whether a launch of k iterations can run on a range of the local planes (the overlapped order needs it)"""
+        return True
+
+    def iterate(self, n) -> torch.Tensor:
+        """the local planes of iterate ``n``, once the launches up to it are committed"""
+        return self.local(self.source(n))
+
+    def launch(self, n, k, params, zr=None):
+        """k iterations from iterate ``n``: all local planes, or only the local range ``zr``"""
+        self.step(n, *params, zr)
+
+    def commit(self, k):
+        """every launch of a k-iteration pass has been issued"""
+
+    def halo(self, n):
+        """the ghost planes of iterate ``n`` as `comm.exchange` takes them: (send_down, recv_down, send_up, recv_up)"""
+        return self.send_down(n), self.recv_down(n), self.send_up(n), self.recv_up(n)
+
+
+class PdSlab(_SlabState):
     """Ghosted ping-pong state of a slab-sharded PD_TV run.
 
     Arrays address ``[lo + nz_local + hi][dy][dx]`` with ``lo = GHOST`` below an interior boundary (else 0) and
@@ -431,22 +476,12 @@ class PdSlab:
         self.has_lo, self.has_hi = bool(has_lo), bool(has_hi)
         self.lo = GHOST if has_lo else 0
         self.hi = GHOST if has_hi else 0
-        planes = nzl + self.lo + self.hi
-        dev = data.device
         pd = torch.float16 if half else torch.float32
         self.half = bool(half)
         # only the initial duals need zeros; every other plane that influences an output is copied, received or
         # overwritten before it is read (the outermost Input ghost only feeds warm-up values that are discarded)
-        # `alloc(specs, device)` (the HIP drivers pass ops.placed_empty): the nine work arrays as views of one block the
-        # library places in HBM (docs/kernels/placement.md); default: nine allocations of the caller's allocator
-        shape = (planes, dy, dx)
-        specs = [(shape, torch.float32)] * 3 + [(shape, pd)] * 6
-        self.lease = None
-        if alloc is not None:
-            arrs, self.lease = alloc(specs, dev)
-        else:
-            arrs = [torch.empty(sh, dtype=dt, device=dev) for sh, dt in specs]
-        self.placed = alloc is not None   # the arrays belong to the library's block: results leave it as copies
+        shape = (nzl + self.lo + self.hi, dy, dx)
+        arrs = self._arrays([(shape, torch.float32)] * 3 + [(shape, pd)] * 6, data.device, alloc)
         self.inp = arrs[0]
         self.inp[self.lo:self.lo + nzl] = data
         # the first step reads its primal variable from ``inp`` (U^0 = Input), so U[0] needs no initial copy
@@ -457,9 +492,7 @@ class PdSlab:
             t.zero_()
         self.pair_fn, self.step_fn = pair_fn, step_fn
         self.cur = 0  # buffer set holding the current iterate
-
-    def local(self, t: torch.Tensor) -> torch.Tensor:
-        return t[self.lo:self.lo + self.nzl]
+        self.committed = 0  # iterations `commit` has counted: the iterate buffer set ``cur`` holds in a `_run_slab` run
 
     def result(self) -> torch.Tensor:
         return self.local(self.inp if self.first else self.U[self.cur])
@@ -490,8 +523,13 @@ class PdSlab:
         return ([(0, b0)] if self.has_lo else []) + ([(b1, self.nzl)] if self.has_hi and b1 < self.nzl else []), (b0, b1)
 
     def single(self, sigma, tau, lt, theta, methodTV, nonneg):
-        """One iteration on the same arrays: the single-iteration kernel sees one ghost plane either side, i.e. the
-        arrays shifted by GHOST - 1 planes where a ghost zone exists."""
+        """One iteration for every local plane."""
+        self._single(sigma, tau, lt, theta, methodTV, nonneg)
+        self.flip()
+
+    def _single(self, sigma, tau, lt, theta, methodTV, nonneg):
+        """One iteration on the same arrays (buffer set cur -> cur ^ 1, no flip): the single-iteration kernel sees one
+        ghost plane either side, i.e. the arrays shifted by GHOST - 1 planes where a ghost zone exists."""
         i, o = self.cur, self.cur ^ 1
         s = GHOST - 1 if self.has_lo else 0
         n = self.nzl + (1 if self.has_lo else 0) + (1 if self.has_hi else 0)
@@ -499,7 +537,32 @@ class PdSlab:
         self.step_fn(v(self.inp), v(self._u_in()), v(self.U[o]), [v(p) for p in self.P[i]], [v(p) for p in self.P[o]],
                      self.dx, self.dy, self.nzl, self.has_lo, self.has_hi, sigma, tau, lt, theta, methodTV, nonneg,
                      self.half)
+
+    # ---- the schedule `_run_slab` drives: the launches of tomo_pdtv itself, the buffer sets flipped once per launch
+    def plan(self, iterations):
+        return pd_launch_plan(iterations, self.half)
+
+    def splits(self, k) -> bool:
+        return k >= 2   # the single-iteration kernel takes no plane range
+
+    def iterate(self, n) -> torch.Tensor:
+        return self.result()
+
+    def launch(self, n, k, params, zr=None):
+        if k >= 2:
+            self.multi_range(k, *params, *(zr if zr is not None else (0, self.nzl)))
+        else:
+            self._single(*params)
+
+    def commit(self, k):
         self.flip()
+        self.committed += k
+
+    def halo(self, n):
+        if n == 0:
+            return self.initial_send_down(), self.initial_recv_down(), self.initial_send_up(), self.initial_recv_up()
+        # an iterate whose launch is issued but not committed yet lies in the set the launch writes
+        return super().halo(self.cur if n <= self.committed else self.cur ^ 1)
 
     # ---- ghost planes of buffer set b.  Up = to rank+1 (its lo ghosts), down = to rank-1 (its hi ghosts).
     #      Up: U and P1..3 of the last GHOST planes; down: U of the first GHOST planes, P1..3 of the first GHOST - 1
@@ -603,9 +666,9 @@ def _hip_rel_change(x, ref, keep):
 class _SlabTolerance:
     """The stopping rule of a TV operator on a z-slab (tomobar_amd/convergence.py): at a check point every rank runs
     rel_change on its LOCAL planes (ghost planes are not counted), the (num, den) pair is summed over the ranks in one
-    all-reduce, and all ranks take the same -- the whole-volume -- decision.  Call `stop` only between exchanges: every
-    check point has a launch after it, so the ghost refresh that follows its launch has been posted AND completed on all
-    ranks; no rank is left waiting on a neighbour that stopped."""
+    all-reduce, and all ranks take the same -- the whole-volume -- decision.  Call `stop` only between exchanges, as
+    _run_slab does at the top of every pass: every check point has a launch after it, so the ghost refresh that follows its
+    launch has been posted AND completed on all ranks; no rank is left waiting on a neighbour that stopped."""
 
     def __init__(self, comm, data, iterations, tolerance, info):
         self.comm, self.data, self.iterations = comm, data.contiguous(), int(iterations)
@@ -628,13 +691,54 @@ class _SlabTolerance:
         return False
 
 
+def _run_slab(st: _SlabState, comm, data, iterations, params, out, overlap, tolerance, info):
+    """The exchange / overlap / tolerance loop of every slab driver, on the state ``st`` through the schedule protocol of
+    `_SlabState`; ``params`` are what the operator's launches take.  The ghosts travel once before the first launch and once
+    after every launch but the last; without a launch (no iteration: every rank sees the same count) nothing is posted.
+
+    Overlap: the planes the neighbours wait for are computed first (two thin launches), their exchange runs on RCCL's
+    stream while the interior of the slab is computed, and the next launch starts when both are done.  A slab without an
+    interior boundary or with fewer than four interior planes, and a launch that cannot be split, take the plain order.
+    The stopping rule is asked between exchanges only (see _SlabTolerance).  The result leaves as a copy, or in `out`."""
+    if iterations > 0:
+        comm.exchange(*st.halo(0))
+    edge_ranges, interior = st.boundary_ranges()
+    overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
+    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
+    done = 0   # iterations committed
+    for k in st.plan(iterations):
+        if rule.stop(done, st.iterate(done)):
+            break
+        more = done + k < iterations
+        if overlap and more and st.splits(k):
+            for zr in edge_ranges:
+                st.launch(done, k, params, zr)
+            handle = comm.exchange_start(*st.halo(done + k))
+            st.launch(done, k, params, interior)
+            st.commit(k)
+            comm.exchange_wait(handle)
+        else:
+            st.launch(done, k, params)
+            st.commit(k)
+            if more:
+                comm.exchange(*st.halo(done + k))
+        done += k
+    _check_lease(st)
+    res = st.iterate(done)  # a view of the last output buffer
+    if out is not None:
+        out.copy_(res)
+        return out
+    return res.clone()
+
+
 def pd_tv_slab(data: torch.Tensor, comm, regularisation_parameter, iterations, methodTV=0, nonneg=0,
                lipschitz_const=8.0, half_precision=False, pair_fn: Optional[Callable] = None,
                step_fn: Optional[Callable] = None, out=None, overlap: bool = True, tolerance: float = 0.0,
                info: Optional[dict] = None):
     """PD_TV of a z-slab of a larger 3D volume; bit-identical to running PD_TV_cupy on the whole volume -- with a
     `tolerance` too: all ranks stop after the iteration the whole-volume run stops after (`info`, when given, receives
-    "iterations_done" and "rel_change")."""
+    "iterations_done" and "rel_change").  Every check point is a launch boundary of the plan, as in tomo_pdtv_tol; the
+    schedule, `overlap` included, is _run_slab's."""
     tau = np.float32(regularisation_parameter * 0.1)
     sigma = np.float32(1.0 / (lipschitz_const * tau))
     theta = np.float32(1.0)
@@ -642,48 +746,11 @@ def pd_tv_slab(data: torch.Tensor, comm, regularisation_parameter, iterations, m
     comm.validate_slabs(data.shape[0], GHOST)
     st = PdSlab(data, comm.has_lo, comm.has_hi, half_precision, pair_fn or _hip_pd_pair, step_fn or _hip_pd_step,
                 alloc=_hip_alloc(PLACED_SLOT_PD) if (pair_fn is None and step_fn is None and data.is_cuda) else None)
-    comm.exchange(st.initial_send_down(), st.initial_recv_down(), st.initial_send_up(), st.initial_recv_up())
-    edge_ranges, interior = st.boundary_ranges()
-    # Overlap: the planes the neighbours wait for are computed first (two thin launches), their exchange runs on RCCL's
-    # stream while the interior of the slab is computed, and the next launch starts when both are done.
-    overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
-    plan = pd_launch_plan(iterations, half_precision)
-    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
-    done = 0
-    for n, k in enumerate(plan):
-        if rule.stop(done, st.result()):   # (every check point is a launch boundary of the plan, as in tomo_pdtv_tol)
-            iterations = done
-            break
-        done += k
-        more = n + 1 < len(plan)
-        if k >= 2 and overlap and more:
-            for z0, z1 in edge_ranges:
-                st.multi_range(k, sigma, tau, lt, theta, methodTV, nonneg, z0, z1)
-            b = st.cur ^ 1
-            reqs = comm.exchange_start(st.send_down(b), st.recv_down(b), st.send_up(b), st.recv_up(b))
-            st.multi_range(k, sigma, tau, lt, theta, methodTV, nonneg, interior[0], interior[1])
-            st.flip()
-            comm.exchange_wait(reqs)
-            continue
-        if k >= 2:
-            st.multi(k, sigma, tau, lt, theta, methodTV, nonneg)
-        else:
-            st.single(sigma, tau, lt, theta, methodTV, nonneg)
-        if more:
-            b = st.cur
-            comm.exchange(st.send_down(b), st.recv_down(b), st.send_up(b), st.recv_up(b))
-    _check_lease(st)
-    res = st.result()  # a view of the last output buffer (the buffer lives as long as the view)
-    if iterations == 0:
-        res = data
-    if out is not None:
-        out.copy_(res)
-        return out
-    return res.clone() if (st.placed and iterations > 0) else res
+    return _run_slab(st, comm, data, iterations, (sigma, tau, lt, theta, methodTV, nonneg), out, overlap, tolerance, info)
 
 
 # ------------------------------------------------------------------------------------------------ ROF_TV on a slab
-class RofSlab:
+class RofSlab(_SlabState):
     """Ghosted ping-pong state for ROF_TV: two ghost planes of U below (D3 of the plane below needs U two planes
     down), one above."""
 
@@ -693,32 +760,29 @@ class RofSlab:
         self.nzl, self.dy, self.dx = nzl, dy, dx
         self.lo = 2 if has_lo else 0
         self.hi = 1 if has_hi else 0
-        planes = nzl + self.lo + self.hi
-        dev = data.device
         self.half = bool(half)
-        specs = [((planes, dy, dx), torch.float32)] * 3
-        self.lease = None
-        if alloc is not None:
-            arrs, self.lease = alloc(specs, dev)
-        else:
-            arrs = [torch.empty(sh, dtype=dt, device=dev) for sh, dt in specs]
+        arrs = self._arrays([((nzl + self.lo + self.hi, dy, dx), torch.float32)] * 3, data.device, alloc)
         self.inp = arrs[0]
         self.inp[self.lo:self.lo + nzl] = data
         self.U = arrs[1:3]
         self.U[0][self.lo:self.lo + nzl] = data
         self.step_fn = step_fn
 
-    def local(self, t):
-        return t[self.lo:self.lo + self.nzl]
+    def source(self, it):
+        """the array that holds iterate ``it``"""
+        return self.U[it & 1]
+
+    def halo(self, n):
+        return super().halo(n & 1)   # send_* / recv_* take the buffer index
 
     def step(self, it, lam, tau, zr=None):
         """iteration ``it``: buffer it&1 -> (it+1)&1, all local planes or only the local range ``zr``"""
+        args = (self.inp, self.source(it), self.source(it + 1), self.dx, self.dy, self.nzl, self.lo, self.hi, lam, tau,
+                self.half)
         if zr is None:
-            self.step_fn(self.inp, self.U[it & 1], self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi,
-                         lam, tau, self.half)
+            self.step_fn(*args)
         elif zr[1] > zr[0]:
-            self.step_fn(self.inp, self.U[it & 1], self.U[(it + 1) & 1], self.dx, self.dy, self.nzl, self.lo, self.hi,
-                         lam, tau, self.half, zr)
+            self.step_fn(*args, zr)
 
     def boundary_ranges(self):
         """planes the neighbours wait for (first plane below an interior boundary, last two above one) and the rest"""
@@ -753,41 +817,16 @@ def _hip_rof_step(inp, u_in, u_out, dx, dy, nzl, lo, hi, lam, tau, half, zr=None
 def rof_tv_slab(data: torch.Tensor, comm, regularisation_parameter, iterations, time_marching_parameter,
                 half_precision=False, step_fn: Optional[Callable] = None, out=None, overlap: bool = True,
                 tolerance: float = 0.0, info: Optional[dict] = None):
-    """ROF_TV of a z-slab of a larger 3D volume (`tolerance`, `info`: see pd_tv_slab)."""
+    """ROF_TV of a z-slab of a larger 3D volume (`tolerance`, `info`: see pd_tv_slab; `overlap`: see _run_slab)."""
     comm.validate_slabs(data.shape[0])
     st = RofSlab(data, comm.has_lo, comm.has_hi, half_precision, step_fn or _hip_rof_step,
                  alloc=_hip_alloc(PLACED_SLOT_ROF) if (step_fn is None and data.is_cuda) else None)
     lam, tau = np.float32(regularisation_parameter), np.float32(time_marching_parameter)
-    comm.exchange(st.send_down(0), st.recv_down(0), st.send_up(0), st.recv_up(0))
-    edge_ranges, interior = st.boundary_ranges()
-    overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
-    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
-    for it in range(iterations):
-        if rule.stop(it, st.local(st.U[it & 1])):
-            iterations = it
-            break
-        more = it + 1 < iterations
-        b = (it + 1) & 1
-        if overlap and more:  # boundary planes, exchange in flight, interior (see pd_tv_slab)
-            for zr in edge_ranges:
-                st.step(it, lam, tau, zr)
-            reqs = comm.exchange_start(st.send_down(b), st.recv_down(b), st.send_up(b), st.recv_up(b))
-            st.step(it, lam, tau, interior)
-            comm.exchange_wait(reqs)
-            continue
-        st.step(it, lam, tau)
-        if more:
-            comm.exchange(st.send_down(b), st.recv_down(b), st.send_up(b), st.recv_up(b))
-    _check_lease(st)
-    res = st.local(st.U[iterations & 1])
-    if out is not None:
-        out.copy_(res)
-        return out
-    return res.clone()
+    return _run_slab(st, comm, data, iterations, (lam, tau), out, overlap, tolerance, info)
 
 
 # ------------------------------------------------------------------------------------ explicit time marching on a slab
-class MarchSlab:
+class MarchSlab(_SlabState):
     """Ghosted ping-pong state of an explicit time march (NDF, Diff4th, LLT_ROF) with a ghost depth of ``g`` planes of U per
     interior boundary.  Arrays address ``[lo + nz_local + hi][dy][dx]`` with ``lo`` / ``hi`` = g where a z-neighbour exists
     (else 0).  The first iteration reads its iterate from ``inp`` (U^0 = the input, whose ghost planes the initial exchange
@@ -800,20 +839,11 @@ class MarchSlab:
         self.nzl, self.dy, self.dx = nzl, dy, dx
         self.lo = g if has_lo else 0
         self.hi = g if has_hi else 0
-        planes = nzl + self.lo + self.hi
-        specs = [((planes, dy, dx), torch.float32)] * 3
-        self.lease = None
-        if alloc is not None:
-            arrs, self.lease = alloc(specs, data.device)
-        else:
-            arrs = [torch.empty(sh, dtype=dt, device=data.device) for sh, dt in specs]
+        arrs = self._arrays([((nzl + self.lo + self.hi, dy, dx), torch.float32)] * 3, data.device, alloc)
         self.inp = arrs[0]
         self.inp[self.lo:self.lo + nzl] = data
         self.U = arrs[1:3]
         self.step_fn, self.ints = step_fn, tuple(ints)
-
-    def local(self, t):
-        return t[self.lo:self.lo + self.nzl]
 
     def source(self, it):
         """the array iteration ``it`` reads = the array that holds iterate ``it``"""
@@ -864,38 +894,6 @@ def _hip_march_step(entry: str, n_ints: int = 0):
     return step
 
 
-def _march_slab(st: MarchSlab, comm, data, iterations, params, out, overlap, tolerance, info):
-    """The exchange / overlap / tolerance loop of ndf_slab, diff4th_slab and llt_rof_slab on the state ``st``; ``params`` are
-    the operator's two parameters and the step ``tau``."""
-    params = tuple(np.float32(v) for v in params)
-    if iterations > 0:
-        comm.exchange(st.send_down(0), st.recv_down(0), st.send_up(0), st.recv_up(0))
-    edge_ranges, interior = st.boundary_ranges()
-    overlap = overlap and bool(edge_ranges) and interior[1] - interior[0] >= 4
-    rule = _SlabTolerance(comm, data, iterations, tolerance, info)
-    for it in range(iterations):
-        if rule.stop(it, st.local(st.source(it))):
-            iterations = it
-            break
-        more = it + 1 < iterations
-        if overlap and more:  # boundary planes, exchange in flight, interior (see pd_tv_slab)
-            for zr in edge_ranges:
-                st.step(it, *params, zr)
-            reqs = comm.exchange_start(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
-            st.step(it, *params, interior)
-            comm.exchange_wait(reqs)
-            continue
-        st.step(it, *params)
-        if more:
-            comm.exchange(st.send_down(it + 1), st.recv_down(it + 1), st.send_up(it + 1), st.recv_up(it + 1))
-    _check_lease(st)
-    res = st.local(st.source(iterations))
-    if out is not None:
-        out.copy_(res)
-        return out
-    return res.clone()
-
-
 # ------------------------------------------------------------------------------------- NDF, Diff4th, LLT_ROF on a slab
 def _march_kind(name: str, n_ints: int = 0):
     """(the MarchSlab subclass, the HIP step, the driver) of the record ``name`` of supp/regularisers.py, which gives the ghost
@@ -918,7 +916,8 @@ def _march_kind(name: str, n_ints: int = 0):
         # the HIP step is looked up by name on every call: the CPU tests replace the module attribute
         st = Slab(data, comm.has_lo, comm.has_hi, *ints, step_fn or globals()[f"_hip_{name.lower()}_step"],
                   _hip_alloc(kind.slot) if (step_fn is None and data.is_cuda) else None)
-        return _march_slab(st, comm, data, iterations, (p0, p1, time_marching_parameter), out, overlap, tolerance, info)
+        params = tuple(np.float32(v) for v in (p0, p1, time_marching_parameter))
+        return _run_slab(st, comm, data, iterations, params, out, overlap, tolerance, info)
 
     driver.__doc__ = f"""{name} of a z-slab of a larger 3D volume; bit-identical to running {kind.cupy} on the whole volume
     (`tolerance`, `info`: see pd_tv_slab).  {kind.ghost} plane(s) of U travel each way after every iteration but the last, plus

@@ -33,7 +33,8 @@ extern "C" {
  * points joined it the same way, for the same reason.  So did the four tomo_wavelet_* entry points, and tomo_halo_pack2 /
  * tomo_halo_pull2 with the four tomo_ipc_region_* entry points, and tomo_nltv_scratch_bytes, tomo_patch_select and
  * tomo_nltv, and the five entry points of the private volume layout (TOMO_VOLUME_ZQUAD below), and the four tomo_pdhg_* entry
- * points (tests/test_matched_bp_oracle.py pins the number 10 as well), and the five tomo_spdhg_* entry points. */
+ * points (tests/test_matched_bp_oracle.py pins the number 10 as well), and the five tomo_spdhg_* entry points, and the four
+ * entry points of PDHG's diagonal preconditioner (tomo_pdhg_diag_*, tomo_pdhg_*_diag). */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -424,6 +425,24 @@ int tomo_pdhg_tv_dual(int device, const float *xbar_dev, float *q1_dev, float *q
 int tomo_pdhg_primal(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *q1_dev,
                      const float *q2_dev, const float *q3_dev, int dx, int dy, int dz, int nd, float tau, int nonneg,
                      void *stream);
+/* PDHG with the diagonal preconditioner of Pock and Chambolle (alpha = 1; RecToolsIRCuPy.PDHG with
+ * _algorithm_["PDHG_preconditioner"] = "diagonal", docs/kernels/pdhg.md): a step per sample and a step per voxel in place of
+ * the two scalars.  The same kernels with one more array stream each; bit for bit tests/_pdhg_diag_oracle.py.
+ *   tomo_pdhg_diag_steps: out = numer / max(in + add, 2^-10) over `count` elements, max as the comparison v < eps ? eps : v:
+ *     the steps from the row sums A 1 (add = 0) or the column sums A^T 1 (add = 2 nd with TV).  out_dev == in_dev is
+ *     allowed.  TOMO_E_INVALID: a non-positive numer, a negative add, NULL.
+ *   tomo_pdhg_sino_dual_diag: tomo_pdhg_sino_dual with sigma_dev[i] in place of sigma (1 + sigma_i and 4 sigma_i are
+ *     computed per sample); 20 B per sample.  TOMO_E_INVALID: an unknown term, NULL, y aliasing r, b or sigma.
+ *   tomo_pdhg_primal_diag: tomo_pdhg_primal with tau_dev[j] in place of tau, one more plane stream (32 B per voxel with TV).
+ *     TOMO_E_INVALID as for tomo_pdhg_primal; tau_dev must not be NULL nor alias x, x-bar or g.
+ *   tomo_pdhg_diag_scratch_bytes: tomo_pdhg_scratch_bytes plus one more skewed array, tau, behind the others. */
+size_t tomo_pdhg_diag_scratch_bytes(int dx, int dy, int dz, int nd);
+int tomo_pdhg_diag_steps(float *out_dev, const float *in_dev, size_t count, float numer, float add, void *stream);
+int tomo_pdhg_sino_dual_diag(float *y_dev, const float *r_dev, const float *b_dev, const float *sigma_dev, size_t count,
+                             int fidelity, void *stream);
+int tomo_pdhg_primal_diag(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *tau_dev,
+                          const float *q1_dev, const float *q2_dev, const float *q3_dev, int dx, int dy, int dz, int nd,
+                          int nonneg, void *stream);
 /* The launches of SPDHG (stochastic PDHG over ordered subsets: one block update touches one subset of angles or the TV
  * block) beside the per-subset forward projector and the subset form of the matched back projector: a subset update of
  * RecToolsIRCuPy.SPDHG runs tomo_fp3d on x, tomo_spdhg_sino_dual, tomo_bp3d_matched, tomo_spdhg_primal; a TV update runs

@@ -11,15 +11,20 @@
 //   stream3_kernel<PdhgSino>        PDHG step 2:       y <- the prox of the conjugate of the data term at y + sigma r
 //   stream3_kernel<StochSino>       SPDHG subset 2:    v = that prox on (y_j, r, b_j); d = v - y_j over r, y_j <- v
 //   stream3_kernel<StochPrimal>     SPDHG subset 4:    z' = z + delta, zb = z' + w delta, x' = x - tau zb [clamped]
+//   stream3_kernel<PdhgSinoDiag>    PDHG step 2 with a step per sample (the diagonal preconditioner): sigma_i from a 4th array
+//   stream3_kernel<DiagSteps>       its set-up:        out = numer / max(in + add, 2^-10), the steps from the row / column sums
 //   tv_dual_march<EMIT_E = false>   PDHG step 4:       q_d <- q_d + sigma F_d(x-bar), projected onto the ball or the box
 //   tv_dual_march<EMIT_E = true>    SPDHG TV step 1:   the same p_d from x; e_d = p_d - q_d, q_d <- p_d
 //   tv_primal_march<PdhgUpdate>     PDHG step 5:       x' = x - tau (g - div q) [clamped], x-bar = 2 x' - x
 //   tv_primal_march<StochTvUpdate>  SPDHG TV 2, 3:     div = sum B_d(e_d); z' = z - div, zb = z' - w div, x' = x - tau zb
-// The streaming launches move 16 B (PdhgSino: r is not written) or 20 B per element.  The marches are plane marches on the
+//   tv_primal_march<PdhgDiagUpdate> PDHG step 5 with a step per voxel: tau_j from one more plane stream
+// The streaming launches move 16 B (PdhgSino: r is not written), 20 B (PdhgSinoDiag too: 16 + the step) or, DiagSteps, 8 B
+// per element.  The marches are plane marches on the
 // skeleton of tgv_dual.inl / tgv_primal.inl (4 rows per lane, 2 x 2 waves, 63 columns per wave; the wave shifts, the plane
 // I/O, the z-march grid and the array skew are the one copy in zmarch_common.h).  Each voxel's own values are read by that
 // voxel only, and the neighbours a launch reads belong to fields it does not write, so nothing is ping-ponged.  Algorithmic
-// traffic in 3D: the dual march 4 + 3 x 8 = 28 B (with e: 4 + 3 x 12 = 40 B), the primal march 3 x 4 + 8 + 8 = 28 B per voxel.
+// traffic in 3D: the dual march 4 + 3 x 8 = 28 B (with e: 4 + 3 x 12 = 40 B), the primal march 3 x 4 + 8 + 8 = 28 B per voxel
+// (PdhgDiagUpdate: + 4 = 32 B).
 #include "zmarch_common.h"
 #include <initializer_list>
 
@@ -41,17 +46,38 @@ __device__ __forceinline__ float data_prox(float y, float r, float b, float sigm
     return 0.5f * ((1.0f + v) - sqrtf(t * t + c4 * bp));
 }
 
-// The per-element functors of stream3_kernel: op(a, b, c) updates a, and b where WRITES_B says so.
+// The per-element functors of stream3_kernel: op(a, b, c) updates a, and b where WRITES_B says so.  STEP_ARRAY: the functor
+// carries a fourth array, `step`, read beside the three, and is called as op(a, b, c, step[i]).
 template <int MODE>
 struct PdhgSino {   // y <- v
-    static constexpr bool WRITES_B = false;
+    static constexpr bool WRITES_B = false, STEP_ARRAY = false;
     float sigma, one_sigma, c4;
     __device__ __forceinline__ void operator()(float &y, float &r, float b) const { y = data_prox<MODE>(y, r, b, sigma, one_sigma, c4); }
 };
 
 template <int MODE>
+struct PdhgSinoDiag {   // y <- v with sigma_i = step[i]
+    static constexpr bool WRITES_B = false, STEP_ARRAY = true;
+    const float *step;
+    __device__ __forceinline__ void operator()(float &y, float &r, float b, float sigma) const
+    {
+        y = data_prox<MODE>(y, r, b, sigma, 1.0f + sigma, 4.0f * sigma);
+    }
+};
+
+struct DiagSteps {   // a <- numer / max(c + add, eps): neither a nor b is read, so the launch streams c in and a out
+    static constexpr bool WRITES_B = false, STEP_ARRAY = false;
+    float numer, add, eps;
+    __device__ __forceinline__ void operator()(float &out, float &, float in) const
+    {
+        const float v = in + add;
+        out = numer / (v < eps ? eps : v);
+    }
+};
+
+template <int MODE>
 struct StochSino {   // y <- v and r <- d = v - y
-    static constexpr bool WRITES_B = true;
+    static constexpr bool WRITES_B = true, STEP_ARRAY = false;
     float sigma, one_sigma, c4;
     __device__ __forceinline__ void operator()(float &y, float &r, float b) const
     {
@@ -62,7 +88,7 @@ struct StochSino {   // y <- v and r <- d = v - y
 };
 
 struct StochPrimal {   // SPDHG subset step 4
-    static constexpr bool WRITES_B = true;
+    static constexpr bool WRITES_B = true, STEP_ARRAY = false;
     float tau, w;
     int nonneg;
     __device__ __forceinline__ void operator()(float &x, float &z, float delta) const
@@ -85,13 +111,15 @@ template <class Op>
 __device__ __forceinline__ void stream3_one(const Op &op, float *a, float *b, const float *c, size_t i)
 {
     float sa = a[i], sb = b[i];
-    op(sa, sb, c[i]);
+    if constexpr (Op::STEP_ARRAY) op(sa, sb, c[i], op.step[i]);
+    else op(sa, sb, c[i]);
     a[i] = sa;
     if (Op::WRITES_B) b[i] = sb;
 }
 
 // Three arrays of n floats: a is read and written, b is read (and written: Op::WRITES_B), c is read.
-// VEC: 16-byte accesses over the first n / 4 quads and a scalar tail by block 0 (all three arrays 16-byte aligned)
+// VEC: 16-byte accesses over the first n / 4 quads and a scalar tail by block 0 (all three arrays, and the step array of
+// an Op::STEP_ARRAY functor, 16-byte aligned)
 template <class Op, bool VEC>
 __global__ __launch_bounds__(STREAM_BLOCK) void stream3_kernel(float *a, float *b, const float *c, size_t n, Op op)
 {
@@ -103,10 +131,18 @@ __global__ __launch_bounds__(STREAM_BLOCK) void stream3_kernel(float *a, float *
             float4 va = reinterpret_cast<const float4 *>(a)[i];
             float4 vb = reinterpret_cast<const float4 *>(b)[i];
             const float4 vc = reinterpret_cast<const float4 *>(c)[i];
-            op(va.x, vb.x, vc.x);
-            op(va.y, vb.y, vc.y);
-            op(va.z, vb.z, vc.z);
-            op(va.w, vb.w, vc.w);
+            if constexpr (Op::STEP_ARRAY) {
+                const float4 vs = reinterpret_cast<const float4 *>(op.step)[i];
+                op(va.x, vb.x, vc.x, vs.x);
+                op(va.y, vb.y, vc.y, vs.y);
+                op(va.z, vb.z, vc.z, vs.z);
+                op(va.w, vb.w, vc.w, vs.w);
+            } else {
+                op(va.x, vb.x, vc.x);
+                op(va.y, vb.y, vc.y);
+                op(va.z, vb.z, vc.z);
+                op(va.w, vb.w, vc.w);
+            }
             reinterpret_cast<float4 *>(a)[i] = va;
             if (Op::WRITES_B) reinterpret_cast<float4 *>(b)[i] = vb;
         }
@@ -121,7 +157,9 @@ __global__ __launch_bounds__(STREAM_BLOCK) void stream3_kernel(float *a, float *
 template <class Op>
 static void stream3_launch(float *a, float *b, const float *c, size_t n, Op op, hipStream_t st)
 {
-    const bool vec = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15u) == 0;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c);
+    if constexpr (Op::STEP_ARRAY) bits |= reinterpret_cast<uintptr_t>(op.step);
+    const bool vec = (bits & 15u) == 0;
     const size_t items = vec ? (n >> 2) : n;
     size_t grid = (items + STREAM_BLOCK - 1) / STREAM_BLOCK;
     if (grid < 1) grid = 1;
@@ -140,6 +178,14 @@ static void sino_launch(int fidelity, float *y, float *r, const float *b, size_t
     if (fidelity == TOMO_PDHG_LS) stream3_launch(y, r, b, n, Sino<TOMO_PDHG_LS>{sigma, one_sigma, c4}, st);
     else if (fidelity == TOMO_PDHG_L1) stream3_launch(y, r, b, n, Sino<TOMO_PDHG_L1>{sigma, one_sigma, c4}, st);
     else stream3_launch(y, r, b, n, Sino<TOMO_PDHG_KL>{sigma, one_sigma, c4}, st);
+}
+
+// the same with a step per sample
+static void sino_diag_launch(int fidelity, float *y, float *r, const float *b, const float *sigma, size_t n, hipStream_t st)
+{
+    if (fidelity == TOMO_PDHG_LS) stream3_launch(y, r, b, n, PdhgSinoDiag<TOMO_PDHG_LS>{sigma}, st);
+    else if (fidelity == TOMO_PDHG_L1) stream3_launch(y, r, b, n, PdhgSinoDiag<TOMO_PDHG_L1>{sigma}, st);
+    else stream3_launch(y, r, b, n, PdhgSinoDiag<TOMO_PDHG_KL>{sigma}, st);
 }
 
 // ------------------------------------------------------------------------------------------ the forward-difference march
@@ -266,13 +312,14 @@ struct TvPrimalArgs {
 };
 
 // The per-voxel functors of tv_primal_march: (X, S, div) -> the new x and the second output; IN_PLACE: the second output
-// replaces the second input.
+// replaces the second input.  STEP_ARRAY: the functor carries one more field, `step`, read at the lane's own voxels like x,
+// and is called as update(X, S, div, step[i]).
 struct XS {   // what an update returns: the new x and the second output
     float x, s;
 };
 
 struct PdhgUpdate {   // x' = x - tau (g - div) [clamped], x-bar = 2 x' - x
-    static constexpr bool IN_PLACE = false;
+    static constexpr bool IN_PLACE = false, STEP_ARRAY = false;
     float tau;
     int nonneg;
     __device__ __forceinline__ XS operator()(float X, float G, float div) const
@@ -283,8 +330,18 @@ struct PdhgUpdate {   // x' = x - tau (g - div) [clamped], x-bar = 2 x' - x
     }
 };
 
+struct PdhgDiagUpdate {   // the same with tau_j = step[j]
+    static constexpr bool IN_PLACE = false, STEP_ARRAY = true;
+    const float *step;
+    int nonneg;
+    __device__ __forceinline__ XS operator()(float X, float G, float div, float tau) const
+    {
+        return PdhgUpdate{tau, nonneg}(X, G, div);
+    }
+};
+
 struct StochTvUpdate {   // z' = z - div, zb = z' - w div, x' = x - tau zb [clamped]
-    static constexpr bool IN_PLACE = true;
+    static constexpr bool IN_PLACE = true, STEP_ARRAY = false;
     float tau, w;
     int nonneg;
     __device__ __forceinline__ XS operator()(float X, float Z, float div) const
@@ -299,8 +356,8 @@ struct StochTvUpdate {   // z' = z - div, zb = z' - w div, x' = x - tau zb [clam
 
 // The mirror image of tv_dual_march: the -x neighbour is the previous lane (lane 0 of a wave is the halo lane), the -y
 // neighbour the previous register (one halo row above the tile, f2 only), the -z neighbour the carried registers of the
-// plane before (f3; a z-chunk loads them once for the plane below its first).  f is read and not written; x and s are read
-// and x and s_out written at the lane's own voxels only.  div = (B_1 f_1 + B_2 f_2) + B_3 f_3.
+// plane before (f3; a z-chunk loads them once for the plane below its first).  f is read and not written; x and s (and the
+// step field of an Update::STEP_ARRAY functor) are read and x and s_out written at the lane's own voxels only.  div = (B_1 f_1 + B_2 f_2) + B_3 f_3.
 template <int ND, bool TV, class Update, int RY, int WX, int WY>
 __global__ __launch_bounds__(64 * WX * WY) void tv_primal_march(TvPrimalArgs a, Update update, int gx, int gy, int tiles_per_xcd,
                                                                int zchunk)
@@ -346,7 +403,7 @@ __global__ __launch_bounds__(64 * WX * WY) void tv_primal_march(TvPrimalArgs a, 
         __syncthreads();  // lockstep: the waves of a workgroup stay on the same plane
         const bool z_prev = t > 0;
         const size_t pt = sz * t;
-        float F1[RY], F2[RY + 1], F3[RY], X[RY], S[RY];
+        float F1[RY], F2[RY + 1], F3[RY], X[RY], S[RY], T[RY];
         if (TV) {
 #pragma unroll
             for (int q = 0; q <= RY; ++q) F2[q] = io.ld(a.f[1] + pt, xo, rowoff(q));
@@ -359,6 +416,7 @@ __global__ __launch_bounds__(64 * WX * WY) void tv_primal_march(TvPrimalArgs a, 
             }
             X[r] = io.ld(a.x + pt, xo, rowoff(r + 1));
             S[r] = io.ld(s + pt, xo, rowoff(r + 1));
+            if constexpr (Update::STEP_ARRAY) T[r] = io.ld(update.step + pt, xo, rowoff(r + 1));
         }
 
         float Xn[RY], Sn[RY];
@@ -375,7 +433,9 @@ __global__ __launch_bounds__(64 * WX * WY) void tv_primal_march(TvPrimalArgs a, 
                     Zp[r] = F3[r];
                 }
             }
-            const XS o = update(X[r], S[r], div);
+            XS o;
+            if constexpr (Update::STEP_ARRAY) o = update(X[r], S[r], div, T[r]);
+            else o = update(X[r], S[r], div);
             Xn[r] = o.x;
             Sn[r] = o.s;
         }
@@ -468,6 +528,37 @@ extern "C" int tomo_pdhg_sino_dual(float *y_dev, const float *r_dev, const float
     return TOMO_OK;
 }
 
+extern "C" size_t tomo_pdhg_diag_scratch_bytes(int dx, int dy, int dz, int nd)
+{
+    if (nd == 2) dz = 1;
+    return tomo_pdhg_scratch_bytes(dx, dy, dz, nd) + work_array_bytes((size_t)dx * dy * dz);   // ... and tau, behind them
+}
+
+extern "C" int tomo_pdhg_diag_steps(float *out_dev, const float *in_dev, size_t count, float numer, float add, void *stream)
+{
+    TOMO_REQUIRE(positive_finite(numer), "PDHG: the numerator of the steps must be positive");
+    TOMO_REQUIRE(add >= 0.0f && std::isfinite(add), "PDHG: the constant added to the sums must be finite and not negative");
+    TOMO_REQUIRE(out_dev && in_dev, "NULL data pointer");
+    if (count == 0) return TOMO_OK;
+    // the skeleton's second array is neither read nor written by DiagSteps: it only takes part in the alignment test
+    stream3_launch(out_dev, out_dev, in_dev, count, DiagSteps{numer, add, 0x1p-10f}, as_stream(stream));
+    TOMO_LAUNCH_CHECK();
+    return TOMO_OK;
+}
+
+extern "C" int tomo_pdhg_sino_dual_diag(float *y_dev, const float *r_dev, const float *b_dev, const float *sigma_dev, size_t count,
+                                        int fidelity, void *stream)
+{
+    TOMO_REQUIRE(known_fidelity(fidelity), "PDHG: the data term must be TOMO_PDHG_LS, TOMO_PDHG_L1 or TOMO_PDHG_KL");
+    TOMO_REQUIRE(y_dev && r_dev && b_dev && sigma_dev, "NULL data pointer");
+    TOMO_REQUIRE(y_dev != r_dev && y_dev != b_dev && y_dev != sigma_dev, "PDHG: the dual array must not alias an array the launch reads");
+    if (count == 0) return TOMO_OK;
+    sino_diag_launch(fidelity, y_dev, const_cast<float *>(r_dev) /* PdhgSinoDiag does not write it */, b_dev, sigma_dev, count,
+                     as_stream(stream));
+    TOMO_LAUNCH_CHECK();
+    return TOMO_OK;
+}
+
 extern "C" int tomo_pdhg_tv_dual(int device, const float *xbar_dev, float *q1_dev, float *q2_dev, float *q3_dev, int dx,
                                  int dy, int dz, int nd, float sigma, float lambda, int methodTV, void *stream)
 {
@@ -482,6 +573,25 @@ extern "C" int tomo_pdhg_tv_dual(int device, const float *xbar_dev, float *q1_de
     return tv_dual_run<false>("PDHG", a, nd, methodTV, as_stream(stream));
 }
 
+// what tomo_pdhg_primal and tomo_pdhg_primal_diag share: the checks and the choice of the instantiation; `tau_dev`, where
+// given, is one more array the launch reads
+template <class Update>
+static int pdhg_primal_run(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *tau_dev, const float *q1_dev,
+                           const float *q2_dev, const float *q3_dev, int dx, int dy, int dz, int nd, Update update, void *stream)
+{
+    const bool tv = q1_dev != nullptr;
+    TOMO_REQUIRE(tv ? (q2_dev && (nd == 2 || q3_dev)) : (!q2_dev && !q3_dev),
+                 "PDHG: give every dual field of the TV block (q3 for nd = 3 only) or none");
+    TOMO_REQUIRE(distinct({x_dev, xbar_dev, g_dev, tau_dev}), "PDHG: x, x-bar, g and the step array must not alias");
+    for (const float *q : {q1_dev, q2_dev, q3_dev})
+        TOMO_REQUIRE(!q || (q != x_dev && q != xbar_dev), "PDHG: a dual field must not alias an array the launch writes");
+    TOMO_ON_DEVICE(device);
+    const TvPrimalArgs a{x_dev, g_dev, xbar_dev, {q1_dev, q2_dev, nd == 3 ? q3_dev : nullptr}, dx, dy, dz};
+    hipStream_t st = as_stream(stream);
+    return nd == 3 ? (tv ? tv_primal_launch<3, true>("PDHG", a, update, st) : tv_primal_launch<3, false>("PDHG", a, update, st))
+                   : (tv ? tv_primal_launch<2, true>("PDHG", a, update, st) : tv_primal_launch<2, false>("PDHG", a, update, st));
+}
+
 extern "C" int tomo_pdhg_primal(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *q1_dev,
                                 const float *q2_dev, const float *q3_dev, int dx, int dy, int dz, int nd, float tau,
                                 int nonneg, void *stream)
@@ -489,18 +599,18 @@ extern "C" int tomo_pdhg_primal(int device, float *x_dev, float *xbar_dev, const
     if (int rc = require_volume("PDHG", device, dx, dy, dz, nd)) return rc;
     TOMO_REQUIRE(positive_finite(tau), "PDHG: the step size tau must be positive");
     TOMO_REQUIRE(x_dev && xbar_dev && g_dev, "NULL data pointer");
-    const bool tv = q1_dev != nullptr;
-    TOMO_REQUIRE(tv ? (q2_dev && (nd == 2 || q3_dev)) : (!q2_dev && !q3_dev),
-                 "PDHG: give every dual field of the TV block (q3 for nd = 3 only) or none");
-    TOMO_REQUIRE(distinct({x_dev, xbar_dev, g_dev}), "PDHG: x, x-bar and g must not alias");
-    for (const float *q : {q1_dev, q2_dev, q3_dev})
-        TOMO_REQUIRE(!q || (q != x_dev && q != xbar_dev), "PDHG: a dual field must not alias an array the launch writes");
-    TOMO_ON_DEVICE(device);
-    const TvPrimalArgs a{x_dev, g_dev, xbar_dev, {q1_dev, q2_dev, nd == 3 ? q3_dev : nullptr}, dx, dy, dz};
-    const PdhgUpdate update{tau, nonneg ? 1 : 0};
-    hipStream_t st = as_stream(stream);
-    return nd == 3 ? (tv ? tv_primal_launch<3, true>("PDHG", a, update, st) : tv_primal_launch<3, false>("PDHG", a, update, st))
-                   : (tv ? tv_primal_launch<2, true>("PDHG", a, update, st) : tv_primal_launch<2, false>("PDHG", a, update, st));
+    return pdhg_primal_run(device, x_dev, xbar_dev, g_dev, nullptr, q1_dev, q2_dev, q3_dev, dx, dy, dz, nd,
+                           PdhgUpdate{tau, nonneg ? 1 : 0}, stream);
+}
+
+extern "C" int tomo_pdhg_primal_diag(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *tau_dev,
+                                     const float *q1_dev, const float *q2_dev, const float *q3_dev, int dx, int dy, int dz, int nd,
+                                     int nonneg, void *stream)
+{
+    if (int rc = require_volume("PDHG", device, dx, dy, dz, nd)) return rc;
+    TOMO_REQUIRE(x_dev && xbar_dev && g_dev && tau_dev, "NULL data pointer");
+    return pdhg_primal_run(device, x_dev, xbar_dev, g_dev, tau_dev, q1_dev, q2_dev, q3_dev, dx, dy, dz, nd,
+                           PdhgDiagUpdate{tau_dev, nonneg ? 1 : 0}, stream);
 }
 
 // ------------------------------------------------------------------------------------------ C-ABI: SPDHG

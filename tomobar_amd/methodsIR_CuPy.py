@@ -192,7 +192,8 @@ class RecToolsIRCuPy:
 
     def __common_initialisation(self, _data_, _algorithm_, _regularisation_, method_run):
         d, a, r = self._prepare_data(_data_, _algorithm_, _regularisation_, method_run)
-        if a.get("lipschitz_const") is None:
+        # (PDHG with the diagonal preconditioner takes its steps from A 1 and A^T 1: no operator norm, no power method)
+        if a.get("lipschitz_const") is None and not (method_run == "PDHG" and a["PDHG_preconditioner"] == "diagonal"):
             # SPDHG steps with one bound for every subset's operator; the other drivers with subset 0's (the reference's)
             a["lipschitz_const"] = self._largest_subset_norm() if method_run == "SPDHG" else self.powermethod(d)
         rec_dim = geom_size(self.Atools.vol_geom)
@@ -424,23 +425,38 @@ class RecToolsIRCuPy:
         has_tv = r.get("method") is not None
         nd = 3 if A.vol_shape()[0] > 1 else 2
 
-        # the step sizes, float32 throughout: sigma tau L_K = 0.95^2 with L_K = |A|^2 + |grad|^2 <= L_A + 4 nd
-        L_K = float32(a["lipschitz_const"])
-        if has_tv:
-            L_K = L_K + float32(4 * nd)
-        s = float32(0.95) / np.sqrt(L_K)
+        diag = a["PDHG_preconditioner"] == "diagonal"
         rho = float32(a["PDHG_ratio"])
-        sigma, tau = s * rho, s / rho
         lam = float32(r["regul_param"]) if has_tv else None
+        if diag:
+            # Pock and Chambolle's diagonal steps (alpha = 1), float32 throughout: sigma_i = c rho / (A 1)_i for the
+            # sinogram block, c rho / 2 for the TV block (a forward-difference row has the absolute sum 2),
+            # tau_j = (c / rho) / ((A^T 1)_j + 2 nd); the arrays are built inside the loop's try, two projector calls
+            c = float32(0.95)
+            numer_sigma, numer_tau = c * rho, c / rho
+            sigma = numer_sigma / float32(2)
+            col_add = float32(2 * nd) if has_tv else float32(0)
+        else:
+            # the step sizes, float32 throughout: sigma tau L_K = 0.95^2 with L_K = |A|^2 + |grad|^2 <= L_A + 4 nd
+            L_K = float32(a["lipschitz_const"])
+            if has_tv:
+                L_K = L_K + float32(4 * nd)
+            s = float32(0.95) / np.sqrt(L_K)
+            sigma, tau = s * rho, s / rho
 
-        # x-bar, g = A^T y and the TV dual live in a placed block of their own; the projector calls see ordinary tensors
-        xbar, g, q, _ = ops.pdhg_work_arrays(A.vol_shape(), A._device, has_tv)
+        # x-bar, g = A^T y and the TV dual (and the steps per voxel) live in a placed block of their own; the projector calls
+        # see ordinary tensors
+        if diag:
+            xbar, g, q, tau, _ = ops.pdhg_work_arrays(A.vol_shape(), A._device, has_tv, tau=True)
+        else:
+            xbar, g, q, _ = ops.pdhg_work_arrays(A.vol_shape(), A._device, has_tv)
         xbar.copy_(x)
         for field in q:
             ops.fill(field, 0.0)
         y = torch.empty_like(b)
         ops.fill(y, 0.0)
         proj = torch.empty_like(b)
+        sigma_rows = torch.empty_like(b) if diag else None   # the steps per sample
 
         planar_volume = getattr(A, "set_volume_layout", None)
         A.invalidate()
@@ -448,14 +464,28 @@ class RecToolsIRCuPy:
         if planar_volume is not None:
             planar_volume("planar")
         mon = _RunMonitor(self, "PDHG", a, x)
+        self.last_run["preconditioner"] = "diagonal" if diag else None
         try:
+            if diag:   # the row and column sums of A; g and proj hold the ones, the loop overwrites both before it reads them
+                ops.fill(g, 1.0)
+                A.forward(g, None, out=sigma_rows)
+                ops.pdhg_diag_steps(sigma_rows, sigma_rows, numer_sigma)
+                ops.fill(proj, 1.0)
+                A.backward(proj, None, out=tau)
+                ops.pdhg_diag_steps(tau, tau, numer_tau, col_add)
             for k in range(a["iterations"]):
                 A.forward(xbar, None, out=proj)
-                ops.pdhg_sino_dual(y, proj, b, fid, sigma)
+                if diag:
+                    ops.pdhg_sino_dual_diag(y, proj, b, sigma_rows, fid)
+                else:
+                    ops.pdhg_sino_dual(y, proj, b, fid, sigma)
                 A.backward(y, None, out=g)
                 if has_tv:
                     ops.pdhg_tv_dual(xbar, q, sigma, lam, r["methodTV"])
-                ops.pdhg_primal(x, xbar, g, q, tau, nonneg)
+                if diag:
+                    ops.pdhg_primal_diag(x, xbar, g, q, tau, nonneg)
+                else:
+                    ops.pdhg_primal(x, xbar, g, q, tau, nonneg)
                 if a["verbose"] and np.mod(k, (round)(a["iterations"] / 5) + 1) == 0:
                     print("PDHG iteration (", k + 1, ") using", r.get("method"), "regularisation")
                 if mon.stop(k + 1, x):

@@ -338,12 +338,17 @@ def llt_rof(data, out, lam_rof, lam_llt, tau, iterations, tolerance=0.0):
 PDHG_SLOT = 5   # the placed block of the PDHG driver's work arrays (slots 0-4: the slab drivers, supp/regularisers.py)
 
 
-def pdhg_work_arrays(shape, device, tv: bool = True):
+def pdhg_work_arrays(shape, device, tv: bool = True, tau: bool = False):
     """The work arrays of one PDHG call on a volume of `shape` ([nz, ny, nx]), uninitialised, from the placed block of
     ``PDHG_SLOT``: (x-bar, g, [q_1 .. q_nd]) and the lease token of ``placed_empty``; nd = 3 if nz > 1 else 2, no q without
-    the TV block.  With it the block has the size ``tomo_pdhg_scratch_bytes`` states."""
+    the TV block.  With it the block has the size ``tomo_pdhg_scratch_bytes`` states.  `tau` (the diagonal preconditioner):
+    one more array behind the others, the steps per voxel, returned in front of the lease -- (x-bar, g, [q], tau, lease);
+    with TV the block then has the size ``tomo_pdhg_diag_scratch_bytes`` states."""
     nd = 3 if shape[0] > 1 else 2
-    arrays, lease = placed_empty([(tuple(shape), torch.float32)] * (2 + (nd if tv else 0)), device, slot=PDHG_SLOT)
+    count = 2 + (nd if tv else 0)
+    arrays, lease = placed_empty([(tuple(shape), torch.float32)] * (count + bool(tau)), device, slot=PDHG_SLOT)
+    if tau:
+        return arrays[0], arrays[1], arrays[2:count], arrays[count], lease
     return arrays[0], arrays[1], arrays[2:], lease
 
 
@@ -411,6 +416,35 @@ def pdhg_primal(x, xbar, g, q, tau, nonneg=False):
     with _on(x):
         L.check(L.lib().tomo_pdhg_primal(x.device.index, ptr(x), ptr(xbar), ptr(g), *_pdhg_ptrs(q), dx, dy, dz, nd, float(tau),
                                          int(bool(nonneg)), stream_ptr(x)))
+
+
+def pdhg_diag_steps(out, sums, numer, add=0.0):
+    """The steps of PDHG's diagonal preconditioner (tomo_pdhg_diag_steps): `out` <- numer / max(sums + add, 2^-10),
+    element-wise; `sums` = A 1 (the steps sigma_i, add = 0) or A^T 1 (the steps tau_j, add = 2 nd with TV); `numer`, `add`
+    float32 scalars.  `out` may be `sums` itself.  Returns `out`."""
+    _pdhg_flat([("out", out), ("sums", sums)])
+    with _on(out):
+        L.check(L.lib().tomo_pdhg_diag_steps(ptr(out), ptr(sums), out.numel(), float(numer), float(add), stream_ptr(out)))
+    return out
+
+
+def pdhg_sino_dual_diag(y, r, b, sigma, fidelity: str):
+    """`pdhg_sino_dual` with a step per sample (tomo_pdhg_sino_dual_diag): `sigma` is an array like `y`."""
+    if fidelity not in L.PDHG_FID:
+        raise ValueError(f"unknown PDHG data term {fidelity!r}: LS, L1 and KL are supported")
+    _pdhg_flat([("y", y), ("r", r), ("b", b), ("sigma", sigma)])
+    with _on(y):
+        L.check(L.lib().tomo_pdhg_sino_dual_diag(ptr(y), ptr(r), ptr(b), ptr(sigma), y.numel(), L.PDHG_FID[fidelity], stream_ptr(y)))
+    return y
+
+
+def pdhg_primal_diag(x, xbar, g, q, tau, nonneg=False):
+    """`pdhg_primal` with a step per voxel (tomo_pdhg_primal_diag): `tau` is an array like `x`."""
+    dx, dy, dz, nd = _pdhg_fields(x, [("q", q)], or_none=True)
+    _pdhg_like(x, [("xbar", xbar), ("g", g), ("tau", tau)])
+    with _on(x):
+        L.check(L.lib().tomo_pdhg_primal_diag(x.device.index, ptr(x), ptr(xbar), ptr(g), ptr(tau), *_pdhg_ptrs(q), dx, dy, dz, nd,
+                                              int(bool(nonneg)), stream_ptr(x)))
 
 
 # ----------------------------------------------------------------------------- SPDHG (docs/kernels/spdhg.md)

@@ -91,13 +91,20 @@ def _pdhg_refusals(self, _data_: dict, name: str = "PDHG") -> None:
 
 
 def _pdhg_keys(_algorithm_: dict, _regularisation_: dict, name: str = "PDHG") -> None:
-    """The keys of PDHG and SPDHG: ``PDHG_ratio`` (sigma / tau, default 1.0, positive), for SPDHG ``SPDHG_seed`` (the seed
+    """The keys of PDHG and SPDHG: ``PDHG_ratio`` (sigma / tau, default 1.0, positive), ``PDHG_preconditioner`` (None, the
+    default, or "diagonal"; SPDHG takes None only), for SPDHG ``SPDHG_seed`` (the seed
     of the block draws, default 0, a non-negative int), and a regulariser that is None or exactly "PD_TV" -- the same TV
     semi-norm, solved jointly in the dual, so only ``regul_param`` and ``methodTV`` are read (and filled); no prox runs,
     hence no slice-wise or half-precision form."""
     _algorithm_.setdefault("PDHG_ratio", 1.0)
     if not float(_algorithm_["PDHG_ratio"]) > 0.0:
         raise ValueError("_algorithm_['PDHG_ratio'] (sigma / tau) must be positive")
+    # the diagonal preconditioner (docs/kernels/pdhg.md): PDHG's alone, so SPDHG refuses it instead of ignoring it
+    pre = _algorithm_.setdefault("PDHG_preconditioner", None)
+    if name == "SPDHG" and pre is not None:
+        raise ValueError("_algorithm_['PDHG_preconditioner'] is available in PDHG only: there is no preconditioned SPDHG")
+    if pre not in (None, "diagonal"):
+        raise ValueError(f"_algorithm_['PDHG_preconditioner'] must be None or 'diagonal', not {pre!r}")
     if name == "SPDHG":
         seed = _algorithm_.setdefault("SPDHG_seed", 0)
         if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or seed < 0:

@@ -1,8 +1,13 @@
 """Timing of RecToolsIRCuPy.PDHG (docs/kernels/pdhg.md: per iteration one forward projection, the sinogram dual, one matched
 back projection, the TV dual and the primal) on synthetic data.
 
-usage: python tools/pdhg_bench.py [--shapes 512:360,1024:900] [--fidelity LS] [--reps 5] [--short 4] [--long 14] [--out FILE]
-       python tools/pdhg_bench.py --kernel-db RESULTS.db [--out FILE]
+usage: python tools/pdhg_bench.py [--shapes 512:360,1024:900] [--fidelity LS] [--preconditioner diagonal] [--power-method]
+                                  [--reps 5] [--short 4] [--long 14] [--out FILE]
+       python tools/pdhg_bench.py --kernel-db RESULTS.db [--preconditioner diagonal] [--out FILE]
+
+--preconditioner diagonal times the diagonally preconditioned driver (steps from A 1 and A^T 1 at the set-up of every call,
+20 B per sample and 32 B per voxel in the split); --power-method leaves lipschitz_const out of the scalar run, so that
+`ms_set_up_per_call` -- a short call minus its iterations -- shows what the power method costs.
 
 Per shape n:angles (an n^3 volume, n detector columns): one warm-up call, then `reps` pairs of calls with `short` and `long`
 iterations timed with device events; the time of one iteration is the median over the pairs of
@@ -28,8 +33,11 @@ sys.path.insert(0, ROOT)
 COPY_RATE_GBPS = 6200.0
 # regular expressions on the kernel names of csrc/pdhg_kernels.hip, which SPDHG's launches share: the functor names the launch,
 # the dual march's third template argument says whether it also writes e (SPDHG) or not (PDHG)
-GROUPS = (("PdhgSino", "sino_dual"), (r"tv_dual_march<\d, \w+, false,", "tv_dual"), ("PdhgUpdate", "primal"), ("bp_", "bp"),
+GROUPS = (("PdhgSino", "sino_dual"), (r"tv_dual_march<\d, \w+, false,", "tv_dual"), ("PdhgUpdate", "primal"),
+          ("PdhgDiagUpdate", "primal"), ("DiagSteps", "diag_steps"), ("bp_", "bp"),
           ("fp_", "fp"), ("transpose64", "fp"))   # the in-plane transpose in front of the forward projector
+# algorithmic bytes per voxel / per sample of (TV dual, primal, sinogram dual): the diagonal launches read one more array
+BYTES = {None: (28, 28, 16), "diagonal": (28, 32, 20)}
 
 
 def bench(n, na, args):
@@ -42,32 +50,40 @@ def bench(n, na, args):
     reg = {"method": "PD_TV", "regul_param": 0.5, "methodTV": 0}
     out = [None]
 
+    algo = {"nonnegativity": True, "recon_mask_radius": None}
+    if args.preconditioner is not None:      # its steps come from A 1 and A^T 1: two projections at set-up, no operator norm
+        algo["PDHG_preconditioner"] = args.preconditioner
+    elif not args.power_method:
+        algo["lipschitz_const"] = float(n) * na
+
     def run(iters):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        out[0] = rt.PDHG({"projection_data": sino, "data_fidelity": args.fidelity},
-                         {"iterations": iters, "lipschitz_const": float(n) * na, "nonnegativity": True, "recon_mask_radius": None},
-                         dict(reg))
+        out[0] = rt.PDHG({"projection_data": sino, "data_fidelity": args.fidelity}, dict(algo, iterations=iters), dict(reg))
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1)
 
     run(args.short)   # warm-up: code objects, the placed block
-    per_iter, calls = [], []
+    per_iter, calls, set_up = [], [], []
     for _ in range(args.reps):
         ts, tl = run(args.short), run(args.long)
         per_iter.append((tl - ts) / (args.long - args.short))
         calls.append(tl)
+        set_up.append(ts - args.short * per_iter[-1])   # what a call costs beside its iterations
     from tomobar_amd import ops
-    return {"op": "pdhg", "fidelity": args.fidelity, "n": n, "nz": n, "nu": n, "angles": na, "reps": args.reps,
+    return {"op": "pdhg", "fidelity": args.fidelity, "preconditioner": args.preconditioner,
+            "steps_from": "A1 and AT1" if args.preconditioner else ("power method" if args.power_method else "given"),
+            "n": n, "nz": n, "nu": n, "angles": na, "reps": args.reps,
             "device": torch.cuda.get_device_name(0), "ms_per_iteration": round(statistics.median(per_iter), 3),
             "ms_per_iteration_min_max": [round(min(per_iter), 3), round(max(per_iter), 3)],
             f"ms_per_call_{args.long}_iterations": round(statistics.median(calls), 2),
+            "ms_set_up_per_call": round(statistics.median(set_up), 2),
             "kernel_path": {"fp": rt.Atools.kernel_path("fp"), "bp": rt.Atools.kernel_path("bp")},
             "finite": bool(torch.isfinite(out[0]).all()), "placement": ops.placement_last()}
 
 
-def split(db_path, n, na):
+def split(db_path, n, na, preconditioner=None):
     """the launch groups of a profiled run: calls, mean ms per launch, ms per iteration, share of the kernel time; rates of
     the three new launches"""
     import sqlite3
@@ -79,12 +95,13 @@ def split(db_path, n, na):
         agg[group] = (c + calls, t + total / 1e6)
     whole = sum(t for _, t in agg.values()) or 1.0
     iterations = agg.get("primal", (1, 0.0))[0]   # one primal launch per iteration
-    line = {"op": "pdhg_split", "n": n, "angles": na, "iterations": iterations,
+    line = {"op": "pdhg_split", "preconditioner": preconditioner, "n": n, "angles": na, "iterations": iterations,
             "groups": {g: {"calls": c, "mean_ms": round(t / c, 4), "ms_per_iteration": round(t / iterations, 3),
                            "share": round(t / whole, 4)} for g, (c, t) in sorted(agg.items())}}
     new = sum(agg.get(g, (0, 0.0))[1] for g in ("sino_dual", "tv_dual", "primal"))
     line["share_of_the_three_new_launches"] = round(new / whole, 4)
-    nbytes = {"tv_dual": 28 * n ** 3, "primal": 28 * n ** 3, "sino_dual": 16 * n * n * na}
+    per_dual, per_primal, per_sample = BYTES[preconditioner]
+    nbytes = {"tv_dual": per_dual * n ** 3, "primal": per_primal * n ** 3, "sino_dual": per_sample * n * n * na}
     for g, b in nbytes.items():
         if g in agg:
             rate = b / (agg[g][1] / agg[g][0] * 1e-3) / 1e9
@@ -96,6 +113,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="512:360,1024:900")
     ap.add_argument("--fidelity", default="LS", choices=("LS", "L1", "KL"))
+    ap.add_argument("--preconditioner", default=None, choices=("diagonal",), help="_algorithm_['PDHG_preconditioner']")
+    ap.add_argument("--power-method", action="store_true", help="scalar steps without a given lipschitz_const: every call runs the power method")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--short", type=int, default=4)
     ap.add_argument("--long", type=int, default=14)
@@ -109,7 +128,7 @@ def main():
     if args.kernel_db:
         if len(shapes) != 1:
             ap.error("--kernel-db needs --shapes with the one shape the profiled run used")
-        lines.append(split(args.kernel_db, *shapes[0]))
+        lines.append(split(args.kernel_db, *shapes[0], args.preconditioner))
         print(json.dumps(lines[-1]), flush=True)
     else:
         import torch

@@ -509,6 +509,9 @@ extern "C" int tomo_roftv_slices(int device, const float *in_dev, float *out_dev
     TOMO_REQUIRE(device >= 0, "The gpu_device must be a positive integer or zero");
     TOMO_REQUIRE(dx >= 2 && dy >= 2 && nslices >= 1 && iters >= 0, "ROF_TV needs every dimension >= 2 (reflecting boundary)");
     TOMO_REQUIRE(g_variant_roftv == 0, "slice-wise ROF_TV runs the variant 0 only (selected: %d)", g_variant_roftv);
+    // (march_run checks these too, but only once the device is current: refuse them before it is touched, as every other entry does)
+    TOMO_REQUIRE((size_t)dx * (size_t)dy < ((size_t)1 << 29), "a plane of %d x %d exceeds the 2 GiB a buffer descriptor of the TV kernels addresses", dx, dy);
+    TOMO_REQUIRE(in_dev && out_dev, "NULL data pointer");
     TOMO_ON_DEVICE(device);
     hipStream_t st = as_stream(stream);
     tomo_prof_scope prof(PROF_ROFTV, st, iters > 0 ? iters : 0);

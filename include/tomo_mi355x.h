@@ -34,7 +34,8 @@ extern "C" {
  * tomo_halo_pull2 with the four tomo_ipc_region_* entry points, and tomo_nltv_scratch_bytes, tomo_patch_select and
  * tomo_nltv, and the five entry points of the private volume layout (TOMO_VOLUME_ZQUAD below), and the four tomo_pdhg_* entry
  * points (tests/test_matched_bp_oracle.py pins the number 10 as well), and the five tomo_spdhg_* entry points, and the four
- * entry points of PDHG's diagonal preconditioner (tomo_pdhg_diag_*, tomo_pdhg_*_diag). */
+ * entry points of PDHG's diagonal preconditioner (tomo_pdhg_diag_*, tomo_pdhg_*_diag), and the five tomo_pdhg_tgv_* entry
+ * points. */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -443,6 +444,31 @@ int tomo_pdhg_sino_dual_diag(float *y_dev, const float *r_dev, const float *b_de
 int tomo_pdhg_primal_diag(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *tau_dev,
                           const float *q1_dev, const float *q2_dev, const float *q3_dev, int dx, int dy, int dz, int nd,
                           int nonneg, void *stream);
+/* PDHG with the second-order TGV term lambda min_v (alpha1 |grad x - v| + alpha0 |E v|) in its dual (RecToolsIRCuPy.PDHG with
+ * _regularisation_["method"] = "PD_TGV", docs/kernels/pdhg.md): two plane marches in place of tomo_pdhg_tv_dual and
+ * tomo_pdhg_primal; bit for bit tests/_pdhg_tgv_oracle.py.  The fields of the TGV block are passed as host arrays of device
+ * pointers: v, v-bar and P hold nd, Q holds 3 (nd = 2: Q11, Q22, Q12) or 6 (nd = 3: Q11, Q22, Q12, Q33, Q13, Q23).
+ *   tomo_pdhg_tgv_dual: P_d <- P_d + sigma_p (F_d(x-bar) - v-bar_d), then P / max(1, |P| / r1); Q <- Q + sigma_q E(v-bar)
+ *     (symmetrised forward differences), then Q / max(1, |Q|_F / r0), off-diagonal components counted twice; in place,
+ *     88 B per voxel in 3D.  r1 = lambda alpha1, r0 = lambda alpha0.  TOMO_E_INVALID: non-positive steps or radii, NULL, P or
+ *     Q aliasing each other, x-bar or v-bar, a plane of 2^29 voxels or more.
+ *   tomo_pdhg_tgv_primal: x' = x - tau_x (g - div P), clamped at 0 with nonneg; x-bar <- (x' + x') - x, x <- x';
+ *     v'_d = v_d + tau_v (P_d + B_d(Q_dd) + sum_{e != d} B_e(Q_de)), v-bar_d <- (v'_d + v'_d) - v_d, v_d <- v'_d (never
+ *     clamped); in place, 88 B per voxel in 3D.  TOMO_E_INVALID: non-positive steps, NULL, any two arrays aliasing, the plane
+ *     limit.
+ *   tomo_pdhg_tgv_primal_diag: the same with tau_dev[j] in place of tau_x, one more plane stream (92 B).
+ *   tomo_pdhg_tgv_scratch_bytes: 17 (nd = 3) or 11 (nd = 2) float arrays -- x-bar, g, P, Q, v, v-bar --, each rounded up to
+ *     256 bytes and followed by the skew of the TV arena; tomo_pdhg_tgv_diag_scratch_bytes: one more, tau, behind them. */
+size_t tomo_pdhg_tgv_scratch_bytes(int dx, int dy, int dz, int nd);
+size_t tomo_pdhg_tgv_diag_scratch_bytes(int dx, int dy, int dz, int nd);
+int tomo_pdhg_tgv_dual(int device, const float *xbar_dev, const float *const *vbar_dev, float *const *p_dev, float *const *q_dev,
+                       int dx, int dy, int dz, int nd, float sigma_p, float sigma_q, float r1, float r0, void *stream);
+int tomo_pdhg_tgv_primal(int device, float *x_dev, float *xbar_dev, const float *g_dev, float *const *v_dev,
+                         float *const *vbar_dev, const float *const *p_dev, const float *const *q_dev, int dx, int dy, int dz,
+                         int nd, float tau_x, float tau_v, int nonneg, void *stream);
+int tomo_pdhg_tgv_primal_diag(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *tau_dev,
+                              float *const *v_dev, float *const *vbar_dev, const float *const *p_dev, const float *const *q_dev,
+                              int dx, int dy, int dz, int nd, float tau_v, int nonneg, void *stream);
 /* The launches of SPDHG (stochastic PDHG over ordered subsets: one block update touches one subset of angles or the TV
  * block) beside the per-subset forward projector and the subset form of the matched back projector: a subset update of
  * RecToolsIRCuPy.SPDHG runs tomo_fp3d on x, tomo_spdhg_sino_dual, tomo_bp3d_matched, tomo_spdhg_primal; a TV update runs

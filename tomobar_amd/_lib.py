@@ -124,6 +124,11 @@ SIGNATURES = {
     "tomo_pdhg_diag_steps": (_i, [_vp, _vp, _sz, _f, _f, _vp]),
     "tomo_pdhg_sino_dual_diag": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp]),
     "tomo_pdhg_primal_diag": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "tomo_pdhg_tgv_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_pdhg_tgv_diag_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "tomo_pdhg_tgv_dual": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp]),
+    "tomo_pdhg_tgv_primal": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "tomo_pdhg_tgv_primal_diag": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "tomo_spdhg_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_spdhg_sino_dual": (_i, [_vp, _vp, _vp, _sz, _i, _f, _vp]),
     "tomo_spdhg_primal": (_i, [_vp, _vp, _vp, _sz, _f, _f, _i, _vp]),

@@ -18,6 +18,9 @@
 //   tv_primal_march<PdhgUpdate>     PDHG step 5:       x' = x - tau (g - div q) [clamped], x-bar = 2 x' - x
 //   tv_primal_march<StochTvUpdate>  SPDHG TV 2, 3:     div = sum B_d(e_d); z' = z - div, zb = z' - w div, x' = x - tau zb
 //   tv_primal_march<PdhgDiagUpdate> PDHG step 5 with a step per voxel: tau_j from one more plane stream
+// and, with the second-order TGV term in PDHG's dual ("PD_TGV"), two marches of their own in pdhg_tgv.inl:
+//   pdhg_tgv_dual_march             PDHG step 4:       P, Q <- the TGV dual update on x-bar, v-bar (88 B per voxel in 3D)
+//   pdhg_tgv_primal_march<Update>   PDHG step 5:       PdhgUpdate / PdhgDiagUpdate on (x, g, div P), and v, v-bar (88 / 92 B)
 // The streaming launches move 16 B (PdhgSino: r is not written), 20 B (PdhgSinoDiag too: 16 + the step) or, DiagSteps, 8 B
 // per element.  The marches are plane marches on the
 // skeleton of tgv_dual.inl / tgv_primal.inl (4 rows per lane, 2 x 2 waves, 63 columns per wave; the wave shifts, the plane
@@ -505,6 +508,8 @@ static bool distinct(std::initializer_list<const float *> ptrs)
 
 static bool known_fidelity(int f) { return f == TOMO_PDHG_LS || f == TOMO_PDHG_L1 || f == TOMO_PDHG_KL; }
 
+#include "pdhg_tgv.inl"
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ C-ABI: PDHG
@@ -611,6 +616,97 @@ extern "C" int tomo_pdhg_primal_diag(int device, float *x_dev, float *xbar_dev, 
     TOMO_REQUIRE(x_dev && xbar_dev && g_dev && tau_dev, "NULL data pointer");
     return pdhg_primal_run(device, x_dev, xbar_dev, g_dev, tau_dev, q1_dev, q2_dev, q3_dev, dx, dy, dz, nd,
                            PdhgDiagUpdate{tau_dev, nonneg ? 1 : 0}, stream);
+}
+
+// ------------------------------------------------------------------------------------------ C-ABI: PDHG with TGV in the dual
+extern "C" size_t tomo_pdhg_tgv_scratch_bytes(int dx, int dy, int dz, int nd)
+{
+    if (nd == 2) dz = 1;
+    const size_t narr = nd == 2 ? 11 : 17;   // x-bar, g, P, v, v-bar (nd each), Q (3 or 6)
+    return narr * work_array_bytes((size_t)dx * dy * dz);
+}
+
+extern "C" size_t tomo_pdhg_tgv_diag_scratch_bytes(int dx, int dy, int dz, int nd)
+{
+    if (nd == 2) dz = 1;
+    return tomo_pdhg_tgv_scratch_bytes(dx, dy, dz, nd) + work_array_bytes((size_t)dx * dy * dz);   // ... and tau, behind them
+}
+
+// the fields of the TGV block as the entry points take them: host arrays of nd (v, v-bar, P) and 3 or 6 (Q) device pointers
+static bool all_given(const float *const *fields, int count)
+{
+    if (!fields) return false;
+    for (int k = 0; k < count; ++k)
+        if (!fields[k]) return false;
+    return true;
+}
+
+extern "C" int tomo_pdhg_tgv_dual(int device, const float *xbar_dev, const float *const *vbar_dev, float *const *p_dev,
+                                  float *const *q_dev, int dx, int dy, int dz, int nd, float sigma_p, float sigma_q, float r1,
+                                  float r0, void *stream)
+{
+    if (int rc = require_volume("PDHG", device, dx, dy, dz, nd)) return rc;
+    const int nq = nd == 3 ? 6 : 3;
+    TOMO_REQUIRE(positive_finite(sigma_p) && positive_finite(sigma_q), "PDHG: the step sizes sigma_P and sigma_Q must be positive");
+    TOMO_REQUIRE(positive_finite(r1) && positive_finite(r0), "PDHG: the radii lambda alpha1 and lambda alpha0 must be positive");
+    TOMO_REQUIRE(xbar_dev && all_given(vbar_dev, nd) && all_given(p_dev, nd) && all_given(q_dev, nq), "NULL data pointer");
+    TgvDualArgs a{};
+    a.xb = xbar_dev;
+    for (int c = 0; c < nd; ++c) { a.vb[c] = vbar_dev[c]; a.p[c] = p_dev[c]; }
+    for (int k = 0; k < nq; ++k) a.q[k] = q_dev[k];
+    TOMO_REQUIRE(distinct({a.xb, a.vb[0], a.vb[1], a.vb[2], a.p[0], a.p[1], a.p[2], a.q[0], a.q[1], a.q[2], a.q[3], a.q[4], a.q[5]}),
+                 "PDHG: the dual fields P and Q must not alias each other, x-bar or v-bar");
+    TOMO_ON_DEVICE(device);
+    a.dx = dx; a.dy = dy; a.dz = dz;
+    a.sigma_p = sigma_p; a.sigma_q = sigma_q; a.r1 = r1; a.r0 = r0;
+    hipStream_t st = as_stream(stream);
+    return nd == 3 ? pdhg_tgv_dual_launch<3>(a, st) : pdhg_tgv_dual_launch<2>(a, st);
+}
+
+// what tomo_pdhg_tgv_primal and tomo_pdhg_tgv_primal_diag share: the checks and the choice of the instantiation; `tau_dev`,
+// where given, is one more array the launch reads
+template <class Update>
+static int pdhg_tgv_primal_run(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *tau_dev,
+                               float *const *v_dev, float *const *vbar_dev, const float *const *p_dev, const float *const *q_dev,
+                               int dx, int dy, int dz, int nd, float tau_v, Update update, void *stream)
+{
+    const int nq = nd == 3 ? 6 : 3;
+    TOMO_REQUIRE(positive_finite(tau_v), "PDHG: the step size tau_v must be positive");
+    TOMO_REQUIRE(all_given(v_dev, nd) && all_given(vbar_dev, nd) && all_given(p_dev, nd) && all_given(q_dev, nq), "NULL data pointer");
+    TgvPrimalArgs a{};
+    a.x = x_dev; a.xb = xbar_dev; a.g = g_dev;
+    for (int c = 0; c < nd; ++c) { a.v[c] = v_dev[c]; a.vb[c] = vbar_dev[c]; a.p[c] = p_dev[c]; }
+    for (int k = 0; k < nq; ++k) a.q[k] = q_dev[k];
+    TOMO_REQUIRE(distinct({a.x, a.xb, a.g, tau_dev, a.v[0], a.v[1], a.v[2], a.vb[0], a.vb[1], a.vb[2], a.p[0], a.p[1], a.p[2],
+                           a.q[0], a.q[1], a.q[2], a.q[3], a.q[4], a.q[5]}),
+                 "PDHG: x, x-bar, g, the step array, v, v-bar, P and Q must not alias");
+    TOMO_ON_DEVICE(device);
+    a.dx = dx; a.dy = dy; a.dz = dz;
+    a.tau_v = tau_v;
+    hipStream_t st = as_stream(stream);
+    return nd == 3 ? pdhg_tgv_primal_launch<3>(a, update, st) : pdhg_tgv_primal_launch<2>(a, update, st);
+}
+
+extern "C" int tomo_pdhg_tgv_primal(int device, float *x_dev, float *xbar_dev, const float *g_dev, float *const *v_dev,
+                                    float *const *vbar_dev, const float *const *p_dev, const float *const *q_dev, int dx, int dy,
+                                    int dz, int nd, float tau_x, float tau_v, int nonneg, void *stream)
+{
+    if (int rc = require_volume("PDHG", device, dx, dy, dz, nd)) return rc;
+    TOMO_REQUIRE(positive_finite(tau_x), "PDHG: the step size tau_x must be positive");
+    TOMO_REQUIRE(x_dev && xbar_dev && g_dev, "NULL data pointer");
+    return pdhg_tgv_primal_run(device, x_dev, xbar_dev, g_dev, nullptr, v_dev, vbar_dev, p_dev, q_dev, dx, dy, dz, nd, tau_v,
+                               PdhgUpdate{tau_x, nonneg ? 1 : 0}, stream);
+}
+
+extern "C" int tomo_pdhg_tgv_primal_diag(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *tau_dev,
+                                         float *const *v_dev, float *const *vbar_dev, const float *const *p_dev,
+                                         const float *const *q_dev, int dx, int dy, int dz, int nd, float tau_v, int nonneg,
+                                         void *stream)
+{
+    if (int rc = require_volume("PDHG", device, dx, dy, dz, nd)) return rc;
+    TOMO_REQUIRE(x_dev && xbar_dev && g_dev && tau_dev, "NULL data pointer");
+    return pdhg_tgv_primal_run(device, x_dev, xbar_dev, g_dev, tau_dev, v_dev, vbar_dev, p_dev, q_dev, dx, dy, dz, nd, tau_v,
+                               PdhgDiagUpdate{tau_dev, nonneg ? 1 : 0}, stream);
 }
 
 // ------------------------------------------------------------------------------------------ C-ABI: SPDHG

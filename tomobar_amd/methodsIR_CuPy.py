@@ -415,6 +415,8 @@ class RecToolsIRCuPy:
         ``_data_["data_fidelity"]`` is "LS", "KL" or "L1" -- the non-smooth terms exactly, no re-weighting and no clamp of
         Ax --, ``_regularisation_["method"]`` None or "PD_TV": the TV term sits in the dual of the outer problem, so an
         iteration is one forward projection, one matched back projection and one stencil pass, with no inner loop.
+        ``"PD_TGV"`` puts the second-order TGV term lambda min_v (alpha1 |grad x - v| + alpha0 |E v|) there instead
+        (``regul_param``, ``TGV_alpha1``, ``TGV_alpha2``): one TGV dual and one TGV primal launch per iteration.
         ``_algorithm_["PDHG_ratio"]`` is sigma / tau (default 1).  Needs ``adjoint="matched"``; no ordered subsets, no
         z-slabs.  Returns the float32 volume ``[detY, N, N]``."""
         (d, a, r, x, _, _) = self.__common_initialisation(_data_, _algorithm_, _regularisation_, "PDHG")
@@ -422,12 +424,15 @@ class RecToolsIRCuPy:
         b = d["projection_data"]
         fid = self.data_fidelity
         nonneg = bool(a["nonnegativity"])
-        has_tv = r.get("method") is not None
+        has_tgv = r.get("method") == "PD_TGV"   # dicts_check lets nothing but None, "PD_TV" and "PD_TGV" through
+        has_tv = r.get("method") is not None and not has_tgv
         nd = 3 if A.vol_shape()[0] > 1 else 2
 
         diag = a["PDHG_preconditioner"] == "diagonal"
         rho = float32(a["PDHG_ratio"])
-        lam = float32(r["regul_param"]) if has_tv else None
+        lam = float32(r["regul_param"]) if has_tv or has_tgv else None
+        if has_tgv:   # the radii of the two balls: r1 = lambda alpha1, r0 = lambda alpha0
+            r1, r0 = lam * float32(r["TGV_alpha1"]), lam * float32(r["TGV_alpha2"])
         if diag:
             # Pock and Chambolle's diagonal steps (alpha = 1), float32 throughout: sigma_i = c rho / (A 1)_i for the
             # sinogram block, c rho / 2 for the TV block (a forward-difference row has the absolute sum 2),
@@ -435,23 +440,36 @@ class RecToolsIRCuPy:
             c = float32(0.95)
             numer_sigma, numer_tau = c * rho, c / rho
             sigma = numer_sigma / float32(2)
-            col_add = float32(2 * nd) if has_tv else float32(0)
+            col_add = float32(2 * nd) if has_tv or has_tgv else float32(0)
+            # the TGV block: a P row holds a forward difference and -I (absolute sum 3), a Q row sums to 2; a v_d column
+            # meets -I once, Q_dd's difference and, for each e != d, the two rows Q_de stands for: 1 + 2 + 2 (nd - 1)
+            sigma_p, sigma_q, tau_v = numer_sigma / float32(3), sigma, numer_tau / float32(2 * nd + 1)
         else:
-            # the step sizes, float32 throughout: sigma tau L_K = 0.95^2 with L_K = |A|^2 + |grad|^2 <= L_A + 4 nd
+            # the step sizes, float32 throughout: sigma tau L_K = 0.95^2 with L_K = |A|^2 + |grad|^2 <= L_A + 4 nd; the TGV
+            # block [[grad, -I], [0, E]] has the squared norm <= 12 (2D), 16 (3D)
             L_K = float32(a["lipschitz_const"])
             if has_tv:
                 L_K = L_K + float32(4 * nd)
+            if has_tgv:
+                L_K = L_K + float32(16 if nd == 3 else 12)
             s = float32(0.95) / np.sqrt(L_K)
             sigma, tau = s * rho, s / rho
+            sigma_p, sigma_q, tau_v = sigma, sigma, tau
 
-        # x-bar, g = A^T y and the TV dual (and the steps per voxel) live in a placed block of their own; the projector calls
-        # see ordinary tensors
-        if diag:
+        # x-bar, g = A^T y and the duals (with TGV: v and v-bar too; with the preconditioner: the steps per voxel) live in a
+        # placed block of their own; the projector calls see ordinary tensors
+        tgv_p = tgv_q = v = vbar = ()
+        if has_tgv:
+            xbar, g, tgv_p, tgv_q, v, vbar, *rest = ops.pdhg_tgv_work_arrays(A.vol_shape(), A._device, tau=diag)
+            if diag:
+                tau = rest[0]
+            q = []
+        elif diag:
             xbar, g, q, tau, _ = ops.pdhg_work_arrays(A.vol_shape(), A._device, has_tv, tau=True)
         else:
             xbar, g, q, _ = ops.pdhg_work_arrays(A.vol_shape(), A._device, has_tv)
         xbar.copy_(x)
-        for field in q:
+        for field in (*q, *tgv_p, *tgv_q, *v, *vbar):
             ops.fill(field, 0.0)
         y = torch.empty_like(b)
         ops.fill(y, 0.0)
@@ -465,6 +483,8 @@ class RecToolsIRCuPy:
             planar_volume("planar")
         mon = _RunMonitor(self, "PDHG", a, x)
         self.last_run["preconditioner"] = "diagonal" if diag else None
+        if has_tgv:
+            self.last_run["regulariser"] = "PD_TGV"
         try:
             if diag:   # the row and column sums of A; g and proj hold the ones, the loop overwrites both before it reads them
                 ops.fill(g, 1.0)
@@ -482,7 +502,10 @@ class RecToolsIRCuPy:
                 A.backward(y, None, out=g)
                 if has_tv:
                     ops.pdhg_tv_dual(xbar, q, sigma, lam, r["methodTV"])
-                if diag:
+                if has_tgv:
+                    ops.pdhg_tgv_dual(xbar, vbar, tgv_p, tgv_q, sigma_p, sigma_q, r1, r0)
+                    ops.pdhg_tgv_primal(x, xbar, g, v, vbar, tgv_p, tgv_q, tau, tau_v, nonneg)
+                elif diag:
                     ops.pdhg_primal_diag(x, xbar, g, q, tau, nonneg)
                 else:
                     ops.pdhg_primal(x, xbar, g, q, tau, nonneg)
@@ -511,7 +534,8 @@ class RecToolsIRCuPy:
         A = self.Atools
         fid = self.data_fidelity
         nonneg = bool(a["nonnegativity"])
-        has_tv = r.get("method") is not None
+        has_tgv = r.get("method") == "PD_TGV"   # dicts_check lets nothing but None, "PD_TV" and "PD_TGV" through
+        has_tv = r.get("method") is not None and not has_tgv
         nd = 3 if A.vol_shape()[0] > 1 else 2
         m = self.OS_number
         blocks = 2 * m if has_tv else m          # E: the block updates of one epoch

@@ -447,8 +447,69 @@ def pdhg_primal_diag(x, xbar, g, q, tau, nonneg=False):
                                               int(bool(nonneg)), stream_ptr(x)))
 
 
+# ---- PDHG with the second-order TGV term in its dual ("PD_TGV", docs/kernels/pdhg.md)
+def pdhg_tgv_work_arrays(shape, device, tau: bool = False):
+    """The work arrays of one PDHG call with the TGV block on a volume of `shape` ([nz, ny, nx]), uninitialised, from the
+    placed block of ``PDHG_SLOT``: (x-bar, g, [P_1 .. P_nd], [Q11, Q22, Q12 (, Q33, Q13, Q23)], [v_1 .. v_nd],
+    [v-bar_1 .. v-bar_nd]) and the lease token of ``placed_empty``; nd = 3 if nz > 1 else 2.  The block has the size
+    ``tomo_pdhg_tgv_scratch_bytes`` states.  `tau` (the diagonal preconditioner): one more array behind the others, the steps
+    per voxel, returned in front of the lease; the block then has the size ``tomo_pdhg_tgv_diag_scratch_bytes`` states."""
+    nd = 3 if shape[0] > 1 else 2
+    nq = 6 if nd == 3 else 3
+    count = 2 + 3 * nd + nq
+    arrays, lease = placed_empty([(tuple(shape), torch.float32)] * (count + bool(tau)), device, slot=PDHG_SLOT)
+    p, q = arrays[2:2 + nd], arrays[2 + nd:2 + nd + nq]
+    v, vbar = arrays[2 + nd + nq:2 + 2 * nd + nq], arrays[2 + 2 * nd + nq:count]
+    if tau:
+        return arrays[0], arrays[1], p, q, v, vbar, arrays[count], lease
+    return arrays[0], arrays[1], p, q, v, vbar, lease
+
+
+def _pdhg_tgv_fields(x, groups, q):
+    """(dx, dy, dz, nd) of `_pdhg_fields` for the nd-field `groups`, and `q` holds the 3 (nd = 2) or 6 (nd = 3) Q fields"""
+    dx, dy, dz, nd = _pdhg_fields(x, groups)
+    nq = 6 if nd == 3 else 3
+    if len(q) != nq:
+        raise ValueError(f"a volume of {dz} plane{'s' if dz > 1 else ''} takes {nq} Q fields, got {len(q)}")
+    _pdhg_like(x, [(f"q{k + 1}", t) for k, t in enumerate(q)])
+    return dx, dy, dz, nd
+
+
+def _ptr_array(group):
+    """the host array of device pointers the tomo_pdhg_tgv_* entry points take for one group of fields"""
+    return (C.c_void_p * len(group))(*[t.data_ptr() for t in group])
+
+
+def pdhg_tgv_dual(xbar, vbar, p, q, sigma_p, sigma_q, r1, r0):
+    """Step 4 of a PDHG iteration with the TGV block (tomo_pdhg_tgv_dual): P_d <- P_d + sigma_p (F_d(x-bar) - v-bar_d),
+    projected onto the ball of radius `r1`; Q <- Q + sigma_q E(v-bar), projected onto the ball of radius `r0`; in place.
+    `vbar` and `p` hold nd fields like `xbar`, `q` 3 (Q11, Q22, Q12) or 6 (..., Q33, Q13, Q23)."""
+    dx, dy, dz, nd = _pdhg_tgv_fields(xbar, [("vbar", vbar), ("p", p)], q)
+    with _on(xbar):
+        L.check(L.lib().tomo_pdhg_tgv_dual(xbar.device.index, ptr(xbar), _ptr_array(vbar), _ptr_array(p), _ptr_array(q), dx, dy, dz,
+                                           nd, float(sigma_p), float(sigma_q), float(r1), float(r0), stream_ptr(xbar)))
+
+
+def pdhg_tgv_primal(x, xbar, g, v, vbar, p, q, tau_x, tau_v, nonneg=False):
+    """Step 5 of a PDHG iteration with the TGV block (tomo_pdhg_tgv_primal, tomo_pdhg_tgv_primal_diag): x' = x - tau_x (g -
+    div P), clamped at 0 with `nonneg`; x-bar <- 2 x' - x, x <- x'; v'_d = v_d + tau_v (P_d + the backward differences of
+    Q's row d), v-bar_d <- 2 v'_d - v_d, v_d <- v'_d; in place.  `tau_x`: a float32 scalar, or an array like `x` (a step per
+    voxel); `tau_v` a scalar."""
+    dx, dy, dz, nd = _pdhg_tgv_fields(x, [("v", v), ("vbar", vbar), ("p", p)], q)
+    per_voxel = isinstance(tau_x, torch.Tensor)
+    _pdhg_like(x, [("xbar", xbar), ("g", g)] + ([("tau_x", tau_x)] if per_voxel else []))
+    groups = (_ptr_array(v), _ptr_array(vbar), _ptr_array(p), _ptr_array(q))
+    with _on(x):
+        if per_voxel:
+            L.check(L.lib().tomo_pdhg_tgv_primal_diag(x.device.index, ptr(x), ptr(xbar), ptr(g), ptr(tau_x), *groups, dx, dy, dz, nd,
+                                                      float(tau_v), int(bool(nonneg)), stream_ptr(x)))
+        else:
+            L.check(L.lib().tomo_pdhg_tgv_primal(x.device.index, ptr(x), ptr(xbar), ptr(g), *groups, dx, dy, dz, nd, float(tau_x),
+                                                 float(tau_v), int(bool(nonneg)), stream_ptr(x)))
+
+
 # ----------------------------------------------------------------------------- SPDHG (docs/kernels/spdhg.md)
-SPDHG_SLOT = 6   # the placed block of the SPDHG driver's work arrays
+SPDHG_SLOT = 6  # the placed block of the SPDHG driver's work arrays
 
 
 def spdhg_work_arrays(shape, device, tv: bool = True):

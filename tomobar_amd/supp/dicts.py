@@ -95,7 +95,8 @@ def _pdhg_keys(_algorithm_: dict, _regularisation_: dict, name: str = "PDHG") ->
     default, or "diagonal"; SPDHG takes None only), for SPDHG ``SPDHG_seed`` (the seed
     of the block draws, default 0, a non-negative int), and a regulariser that is None or exactly "PD_TV" -- the same TV
     semi-norm, solved jointly in the dual, so only ``regul_param`` and ``methodTV`` are read (and filled); no prox runs,
-    hence no slice-wise or half-precision form."""
+    hence no slice-wise or half-precision form.  PDHG alone also takes exactly "PD_TGV", the second-order TGV term in its
+    dual: ``regul_param``, ``TGV_alpha1`` (1.0) and ``TGV_alpha2`` (2.0), all positive, and nothing else."""
     _algorithm_.setdefault("PDHG_ratio", 1.0)
     if not float(_algorithm_["PDHG_ratio"]) > 0.0:
         raise ValueError("_algorithm_['PDHG_ratio'] (sigma / tau) must be positive")
@@ -112,13 +113,22 @@ def _pdhg_keys(_algorithm_: dict, _regularisation_: dict, name: str = "PDHG") ->
     method = _regularisation_.get("method")
     if method is None:
         return
-    if method != "PD_TV":
-        raise ValueError(f"{name} takes _regularisation_['method'] = None or 'PD_TV' (the TV term in its dual), not {method!r}")
+    tgv = name == "PDHG" and method == "PD_TGV"
+    if method != "PD_TV" and not tgv:
+        also = " or 'PD_TGV' (the TGV term in its dual)" if name == "PDHG" else ""
+        raise ValueError(f"{name} takes _regularisation_['method'] = None or 'PD_TV' (the TV term in its dual){also}, not {method!r}")
     if _regularisation_.get("slicewise", False) is not False:
         raise ValueError(f"{name} does not support slicewise=True")
     if _regularisation_.get("half_precision", False):
         raise ValueError(f"{name} does not support half_precision=True")
     _regularisation_.setdefault("regul_param", 0.001)
+    if tgv:   # lambda min_v (alpha1 |grad x - v| + alpha0 |E v|): the weights of the TGV prox by their names there, nothing else
+        _regularisation_.setdefault("TGV_alpha1", 1.0)
+        _regularisation_.setdefault("TGV_alpha2", 2.0)
+        for key in ("regul_param", "TGV_alpha1", "TGV_alpha2"):
+            if not float(_regularisation_[key]) > 0.0:
+                raise ValueError(f"_regularisation_['{key}'] must be positive")
+        return
     _regularisation_.setdefault("methodTV", 0)
     if not float(_regularisation_["regul_param"]) > 0.0:
         raise ValueError("_regularisation_['regul_param'] must be positive")

@@ -1,9 +1,12 @@
 """Timing of RecToolsIRCuPy.PDHG (docs/kernels/pdhg.md: per iteration one forward projection, the sinogram dual, one matched
 back projection, the TV dual and the primal) on synthetic data.
 
-usage: python tools/pdhg_bench.py [--shapes 512:360,1024:900] [--fidelity LS] [--preconditioner diagonal] [--power-method]
-                                  [--reps 5] [--short 4] [--long 14] [--out FILE]
-       python tools/pdhg_bench.py --kernel-db RESULTS.db [--preconditioner diagonal] [--out FILE]
+usage: python tools/pdhg_bench.py [--shapes 512:360,1024:900] [--fidelity LS] [--regulariser tv|tgv] [--preconditioner diagonal]
+                                  [--power-method] [--reps 5] [--short 4] [--long 14] [--out FILE]
+       python tools/pdhg_bench.py --kernel-db RESULTS.db [--regulariser tv|tgv] [--preconditioner diagonal] [--out FILE]
+
+--regulariser tgv times PD_TGV, the second-order TGV term in the dual (two marches of 88 + 88 B per voxel in 3D, 92 B for the
+primal with a step per voxel, in place of the TV pair); its lines go to profiles/pdhg_tgv_bench.jsonl.
 
 --preconditioner diagonal times the diagonally preconditioned driver (steps from A 1 and A^T 1 at the set-up of every call,
 20 B per sample and 32 B per voxel in the split); --power-method leaves lipschitz_const out of the scalar run, so that
@@ -33,11 +36,16 @@ sys.path.insert(0, ROOT)
 COPY_RATE_GBPS = 6200.0
 # regular expressions on the kernel names of csrc/pdhg_kernels.hip, which SPDHG's launches share: the functor names the launch,
 # the dual march's third template argument says whether it also writes e (SPDHG) or not (PDHG)
-GROUPS = (("PdhgSino", "sino_dual"), (r"tv_dual_march<\d, \w+, false,", "tv_dual"), ("PdhgUpdate", "primal"),
+GROUPS = (("pdhg_tgv_dual_march", "tgv_dual"), ("pdhg_tgv_primal_march", "tgv_primal"),   # in front of the functor names they carry
+          ("PdhgSino", "sino_dual"), (r"tv_dual_march<\d, \w+, false,", "tv_dual"), ("PdhgUpdate", "primal"),
           ("PdhgDiagUpdate", "primal"), ("DiagSteps", "diag_steps"), ("bp_", "bp"),
           ("fp_", "fp"), ("transpose64", "fp"))   # the in-plane transpose in front of the forward projector
 # algorithmic bytes per voxel / per sample of (TV dual, primal, sinogram dual): the diagonal launches read one more array
 BYTES = {None: (28, 28, 16), "diagonal": (28, 32, 20)}
+# the same for (TGV dual, TGV primal, sinogram dual)
+TGV_BYTES = {None: (88, 88, 16), "diagonal": (88, 92, 20)}
+REGULARISERS = {"tv": {"method": "PD_TV", "regul_param": 0.5, "methodTV": 0},
+                "tgv": {"method": "PD_TGV", "regul_param": 0.5, "TGV_alpha1": 1.0, "TGV_alpha2": 2.0}}
 
 
 def bench(n, na, args):
@@ -47,7 +55,7 @@ def bench(n, na, args):
     rt = RecToolsIRCuPy(n, 0, n, 0.0, np.linspace(0, np.pi, na, endpoint=False), n, 0, None, adjoint="matched")
     gen = torch.Generator(device="cuda").manual_seed(3)
     sino = torch.rand((n, na, n), device="cuda", generator=gen) * (0.5 * n)
-    reg = {"method": "PD_TV", "regul_param": 0.5, "methodTV": 0}
+    reg = REGULARISERS[args.regulariser]
     out = [None]
 
     algo = {"nonnegativity": True, "recon_mask_radius": None}
@@ -72,7 +80,7 @@ def bench(n, na, args):
         calls.append(tl)
         set_up.append(ts - args.short * per_iter[-1])   # what a call costs beside its iterations
     from tomobar_amd import ops
-    return {"op": "pdhg", "fidelity": args.fidelity, "preconditioner": args.preconditioner,
+    return {"op": "pdhg", "fidelity": args.fidelity, "regulariser": reg["method"], "preconditioner": args.preconditioner,
             "steps_from": "A1 and AT1" if args.preconditioner else ("power method" if args.power_method else "given"),
             "n": n, "nz": n, "nu": n, "angles": na, "reps": args.reps,
             "device": torch.cuda.get_device_name(0), "ms_per_iteration": round(statistics.median(per_iter), 3),
@@ -83,7 +91,7 @@ def bench(n, na, args):
             "finite": bool(torch.isfinite(out[0]).all()), "placement": ops.placement_last()}
 
 
-def split(db_path, n, na, preconditioner=None):
+def split(db_path, n, na, preconditioner=None, regulariser="tv"):
     """the launch groups of a profiled run: calls, mean ms per launch, ms per iteration, share of the kernel time; rates of
     the three new launches"""
     import sqlite3
@@ -94,14 +102,15 @@ def split(db_path, n, na, preconditioner=None):
         c, t = agg.get(group, (0, 0.0))
         agg[group] = (c + calls, t + total / 1e6)
     whole = sum(t for _, t in agg.values()) or 1.0
-    iterations = agg.get("primal", (1, 0.0))[0]   # one primal launch per iteration
-    line = {"op": "pdhg_split", "preconditioner": preconditioner, "n": n, "angles": na, "iterations": iterations,
+    dual, primal = ("tgv_dual", "tgv_primal") if regulariser == "tgv" else ("tv_dual", "primal")
+    iterations = agg.get(primal, (1, 0.0))[0]   # one primal launch per iteration
+    line = {"op": "pdhg_split", "regulariser": REGULARISERS[regulariser]["method"], "preconditioner": preconditioner, "n": n, "angles": na, "iterations": iterations,
             "groups": {g: {"calls": c, "mean_ms": round(t / c, 4), "ms_per_iteration": round(t / iterations, 3),
                            "share": round(t / whole, 4)} for g, (c, t) in sorted(agg.items())}}
-    new = sum(agg.get(g, (0, 0.0))[1] for g in ("sino_dual", "tv_dual", "primal"))
+    new = sum(agg.get(g, (0, 0.0))[1] for g in ("sino_dual", dual, primal))
     line["share_of_the_three_new_launches"] = round(new / whole, 4)
-    per_dual, per_primal, per_sample = BYTES[preconditioner]
-    nbytes = {"tv_dual": per_dual * n ** 3, "primal": per_primal * n ** 3, "sino_dual": per_sample * n * n * na}
+    per_dual, per_primal, per_sample = (TGV_BYTES if regulariser == "tgv" else BYTES)[preconditioner]
+    nbytes = {dual: per_dual * n ** 3, primal: per_primal * n ** 3, "sino_dual": per_sample * n * n * na}
     for g, b in nbytes.items():
         if g in agg:
             rate = b / (agg[g][1] / agg[g][0] * 1e-3) / 1e9
@@ -113,14 +122,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="512:360,1024:900")
     ap.add_argument("--fidelity", default="LS", choices=("LS", "L1", "KL"))
+    ap.add_argument("--regulariser", default="tv", choices=tuple(REGULARISERS), help="PD_TV (the default) or PD_TGV in the dual")
     ap.add_argument("--preconditioner", default=None, choices=("diagonal",), help="_algorithm_['PDHG_preconditioner']")
     ap.add_argument("--power-method", action="store_true", help="scalar steps without a given lipschitz_const: every call runs the power method")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--short", type=int, default=4)
     ap.add_argument("--long", type=int, default=14)
     ap.add_argument("--kernel-db", default=None, help="summarise the kernels table of a rocprofv3 --kernel-trace --stats run instead")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pdhg_bench.jsonl"))
+    ap.add_argument("--out", default=None, help="default: profiles/pdhg_bench.jsonl, profiles/pdhg_tgv_bench.jsonl with --regulariser tgv")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "pdhg_tgv_bench.jsonl" if args.regulariser == "tgv" else "pdhg_bench.jsonl")
     if not 0 < args.short < args.long or args.reps < 1:
         ap.error("need 0 < --short < --long and --reps >= 1")
     shapes = [tuple(int(v) for v in item.split(":")) for item in args.shapes.split(",")]
@@ -128,7 +140,7 @@ def main():
     if args.kernel_db:
         if len(shapes) != 1:
             ap.error("--kernel-db needs --shapes with the one shape the profiled run used")
-        lines.append(split(args.kernel_db, *shapes[0], args.preconditioner))
+        lines.append(split(args.kernel_db, *shapes[0], args.preconditioner, args.regulariser))
         print(json.dumps(lines[-1]), flush=True)
     else:
         import torch

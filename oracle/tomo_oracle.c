@@ -329,6 +329,132 @@ int orc_pdtv(const float *in, float *out, int dx, int dy, int dz, int nd,
     return 0;
 }
 
+/* ---------------------------- PD-TV, relaxed float32 arithmetic ------------------------------------
+ * A model of what the shipped float32-dual kernels compute (pd_dual_t / pd_primal_t with FAST = 1 in
+ * tomobar_amd/csrc/tv_kernels.hip, pd_dual2 / pd_primal2 in tv_slices.hip), not of the reference: the projection multiplies by
+ * ONE reciprocal square root (v_rsq_f32, 1 ulp) where the reference divides by a square root, and the primal step multiplies
+ * by inv1lt = RN(1 / (1 + lt)) where the reference divides.  Every other operation is the same fmaf / product /
+ * difference in the same order.  The hardware's v_rsq_f32 is modelled as RN(1 / sqrt(x)) moved by `off` in {-1, 0, +1}
+ * units in the last place (|off| up to 3 is accepted so that a wider candidate set can be tried). */
+static inline float rsq_off(float x, int off)
+{
+    float r = (float)(1.0 / sqrt((double)x));
+    int32_t b;
+    memcpy(&b, &r, 4);
+    b += off; /* x > 1: r is a positive normal number below 1, so its neighbours are the neighbouring bit patterns */
+    memcpy(&r, &b, 4);
+    return r;
+}
+
+/* offset in {-1, 0, +1} of (voxel, iteration) under `seed`: a 64-bit mix (splitmix64's finaliser) reduced modulo 3 */
+static inline int rlx_hash_off(uint64_t idx, uint32_t it, uint32_t seed)
+{
+    uint64_t h = idx * 0x9E3779B97F4A7C15ull + (((uint64_t)seed << 32) | it);
+    h ^= h >> 30; h *= 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 27; h *= 0x94D049BB133111EBull;
+    h ^= h >> 31;
+    return (int)(h % 3u) - 1;
+}
+
+/* returns 1 if the voxel took the nrm > 1 branch (isotropic only) */
+static inline int pd_dual_relaxed(float *p, const float *g, int nd, float sigma, int methodTV, int off)
+{
+    int sat = 0;
+    for (int c = 0; c < nd; ++c)
+        p[c] = fmaf(sigma, g[c], p[c]);
+    if (!methodTV) {
+        float nrm = p[0] * p[0];
+        for (int c = 1; c < nd; ++c)
+            nrm = fmaf(p[c], p[c], nrm);
+        sat = nrm > 1.0f;
+        const float r = sat ? rsq_off(nrm, off) : 1.0f;
+        for (int c = 0; c < nd; ++c)
+            p[c] *= r;
+    } else {
+        for (int c = 0; c < nd; ++c) {
+            float v = fabsf(p[c]);
+            if (v < 1.0f) v = 1.0f;
+            p[c] /= v;
+        }
+    }
+    return sat;
+}
+
+static inline float pd_primal_relaxed(float u_in, float input, float div, float tau, float lt, float inv1lt, float theta,
+                                      int clip)
+{
+    const float u = (clip && u_in < 0.0f) ? 0.0f : u_in;
+    float t = fmaf(-tau, div, u);
+    t = fmaf(lt, input, t);
+    const float nu_ = t * inv1lt;
+    return fmaf(theta, nu_ - u, nu_);
+}
+
+/* orc_pdtv with the relaxed arithmetic.  mode: 0 = every rsq offset 0, 1 = all -1, 2 = all +1, 3 = drawn per (voxel,
+ * iteration) from a hash of `seed`.  counts[4] (may be NULL) receives the voxel-iterations that took nrm > 1 / did not /
+ * were clipped / were not.  fault_idx >= 0: the non-negativity clip is SKIPPED at that voxel in iteration fault_it -- a
+ * deliberately wrong model, for the tests of the tests. */
+int orc_pdtv_relaxed(const float *in, float *out, int dx, int dy, int dz, int nd,
+                     float sigma, float tau, float lt, float theta,
+                     int iters, int methodTV, int nonneg, int mode, uint32_t seed, long long *counts,
+                     long long fault_idx, int fault_it)
+{
+    if (nd == 2) dz = 1;
+    if (mode < 0 || mode > 3) return -1;
+    const size_t sx = 1, sy = (size_t)dx, sz = (size_t)dx * dy;
+    const size_t nvox = sz * (size_t)dz;
+    float *U[2], *P[3];
+    U[0] = (float *)malloc(nvox * sizeof(float));
+    U[1] = (float *)calloc(nvox, sizeof(float));
+    for (int c = 0; c < 3; ++c) P[c] = (float *)calloc(nvox, sizeof(float));
+    memcpy(U[0], in, nvox * sizeof(float));
+    const float inv1lt = 1.0f / (1.0f + lt);
+    long long n_sat = 0, n_clip = 0;
+    for (int it = 0; it < iters; ++it) {
+        const float *Ui = U[it & 1];
+        float *Uo = U[(it + 1) & 1];
+        /* a voxel's dual depends on its own old dual only: the update can be done in place */
+#pragma omp parallel for collapse(2) schedule(static) reduction(+ : n_sat)
+        for (int z = 0; z < dz; ++z)
+            for (int y = 0; y < dy; ++y)
+                for (int x = 0; x < dx; ++x) {
+                    size_t idx = (size_t)x + sy * y + sz * z;
+                    float g[3] = {0.0f, 0.0f, 0.0f}, p[3] = {0.0f, 0.0f, 0.0f};
+                    g[0] = pd_fwd(Ui, idx, x, dx, sx);
+                    g[1] = pd_fwd(Ui, idx, y, dy, sy);
+                    if (nd == 3) g[2] = pd_fwd(Ui, idx, z, dz, sz);
+                    for (int c = 0; c < nd; ++c) p[c] = P[c][idx];
+                    const int off = mode == 0 ? 0 : mode == 1 ? -1 : mode == 2 ? 1 : rlx_hash_off(idx, (uint32_t)it, seed);
+                    n_sat += pd_dual_relaxed(p, g, nd, sigma, methodTV, off);
+                    for (int c = 0; c < nd; ++c) P[c][idx] = p[c];
+                }
+#pragma omp parallel for collapse(2) schedule(static) reduction(+ : n_clip)
+        for (int z = 0; z < dz; ++z)
+            for (int y = 0; y < dy; ++y)
+                for (int x = 0; x < dx; ++x) {
+                    size_t idx = (size_t)x + sy * y + sz * z;
+                    float pv1 = -(P[0][idx] - (x > 0 ? P[0][idx - sx] : 0.0f));
+                    float pv2 = -(P[1][idx] - (y > 0 ? P[1][idx - sy] : 0.0f));
+                    float div = pv1 + pv2;
+                    if (nd == 3) {
+                        float pv3 = -(P[2][idx] - (z > 0 ? P[2][idx - sz] : 0.0f));
+                        div = div + pv3;
+                    }
+                    const int clip = nonneg && !((long long)idx == fault_idx && it == fault_it);
+                    n_clip += (nonneg && Ui[idx] < 0.0f);
+                    Uo[idx] = pd_primal_relaxed(Ui[idx], in[idx], div, tau, lt, inv1lt, theta, clip);
+                }
+    }
+    memcpy(out, U[iters & 1], nvox * sizeof(float));
+    if (counts) {
+        const long long total = (long long)nvox * iters;
+        counts[0] = n_sat; counts[1] = total - n_sat; counts[2] = n_clip; counts[3] = total - n_clip;
+    }
+    free(U[0]); free(U[1]);
+    for (int c = 0; c < 3; ++c) free(P[c]);
+    return 0;
+}
+
 /* ---------------------------- ROF-TV --------------------------------------------- */
 static inline float rof_minmod_sq(float n0, float n1)
 {
@@ -455,6 +581,50 @@ void orc_pdtv_step(const float *in, const float *Ui, float *Uo, const float *P1i
                 float nu_ = t / (1.0f + lt);
                 Uo[idx] = fmaf(theta, nu_ - u, nu_);
                 for (int c = 0; c < 3; ++c) Po[c][idx] = store_dual(Pn[c][idx], half);
+            }
+    for (int c = 0; c < 3; ++c) free(Pn[c]);
+}
+
+/* orc_pdtv_step with the relaxed arithmetic of orc_pdtv_relaxed (float32 duals only).  offs (may be NULL = all 0): the rsq
+ * offset of every voxel of the slab, [planes][dy][dx]; sat (may be NULL) receives 1 where the voxel took nrm > 1, for the
+ * planes whose duals are formed (zlo .. out_end). */
+void orc_pdtv_step_relaxed(const float *in, const float *Ui, float *Uo, const float *P1i, const float *P2i, const float *P3i,
+                           float *P1o, float *P2o, float *P3o, int dx, int dy, int planes, int out_begin, int out_end,
+                           int first_edge, int last_edge, float sigma, float tau, float lt, float theta, int methodTV,
+                           int nonneg, const int8_t *offs, int8_t *sat)
+{
+    const size_t sy = (size_t)dx, sz = (size_t)dx * dy;
+    const float *Pi[3] = {P1i, P2i, P3i};
+    float *Po[3] = {P1o, P2o, P3o};
+    const int zlo = out_begin > 0 ? out_begin - 1 : 0;
+    const float inv1lt = 1.0f / (1.0f + lt);
+    float *Pn[3];
+    for (int c = 0; c < 3; ++c) Pn[c] = (float *)calloc(sz * (size_t)planes, sizeof(float));
+    (void)first_edge;
+    for (int z = zlo; z < out_end; ++z)
+        for (int y = 0; y < dy; ++y)
+            for (int x = 0; x < dx; ++x) {
+                size_t idx = (size_t)x + sy * y + sz * z;
+                float g[3], p[3];
+                g[0] = pd_fwd(Ui, idx, x, dx, 1);
+                g[1] = pd_fwd(Ui, idx, y, dy, sy);
+                if (z == planes - 1 && last_edge) g[2] = ((z > 0) ? Ui[idx - sz] : 0.0f) - Ui[idx];
+                else g[2] = Ui[idx + sz] - Ui[idx];
+                for (int c = 0; c < 3; ++c) p[c] = Pi[c][idx];
+                const int s = pd_dual_relaxed(p, g, 3, sigma, methodTV, offs ? offs[idx] : 0);
+                if (sat) sat[idx] = (int8_t)s;
+                for (int c = 0; c < 3; ++c) Pn[c][idx] = p[c];
+            }
+    for (int z = out_begin; z < out_end; ++z)
+        for (int y = 0; y < dy; ++y)
+            for (int x = 0; x < dx; ++x) {
+                size_t idx = (size_t)x + sy * y + sz * z;
+                float pv1 = -(Pn[0][idx] - (x > 0 ? Pn[0][idx - 1] : 0.0f));
+                float pv2 = -(Pn[1][idx] - (y > 0 ? Pn[1][idx - sy] : 0.0f));
+                float pv3 = -(Pn[2][idx] - (z > 0 ? Pn[2][idx - sz] : 0.0f));
+                float div = (pv1 + pv2) + pv3;
+                Uo[idx] = pd_primal_relaxed(Ui[idx], in[idx], div, tau, lt, inv1lt, theta, nonneg);
+                for (int c = 0; c < 3; ++c) Po[c][idx] = Pn[c][idx];
             }
     for (int c = 0; c < 3; ++c) free(Pn[c]);
 }

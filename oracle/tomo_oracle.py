@@ -254,6 +254,51 @@ def pd_tv(data, regularisation_parameter=1e-5, iterations=1000, methodTV=0, nonn
     return np.expand_dims(out, axis) if is2d else out
 
 
+RELAXED_MODES = {"model": 0, "down": 1, "up": 2, "seeded": 3}
+
+
+def pd_tv_relaxed(data, regularisation_parameter=1e-5, iterations=1000, methodTV=0, nonneg=0, lipschitz_const=8.0,
+                  mode="model", seed=0, scalars=None, squeeze=True, return_counts=False, fault=None):
+    """A model of the SHIPPED float32-dual PD_TV arithmetic (orc_pdtv_relaxed), not of the reference: one reciprocal square
+    root in the projection and a multiplication by RN(1 / (1 + lt)) in the primal step.  `mode`: where the reciprocal square
+    root lies relative to RN(1 / sqrt(x)) -- "model" (on it), "down" / "up" (one ulp below / above everywhere) or "seeded"
+    (-1 / 0 / +1 per voxel and iteration from a hash of `seed`).  `scalars`: (sigma, tau, lt, theta) instead of the two
+    parameters; `squeeze=False` runs a 3D array as the 3D operator whatever its shape (pd_tv squeezes a singleton axis, as
+    the reference does).  `return_counts`: also a dict of the voxel-iterations that took each branch.  `fault` = (flat voxel
+    index, iteration): the clip is skipped there -- a wrong model on purpose, for the tests of the tests.  binary16 duals are
+    not modelled: they run the reference's roundings."""
+    if data.dtype != np.float32:
+        raise ValueError("The input data should be float32 data type")
+    axis, is2d = 0, data.ndim == 2
+    if squeeze:
+        data, is2d, axis = _squeeze_2d(data)
+    data = np.ascontiguousarray(data)
+    sigma, tau, lt, theta = scalars if scalars is not None else pd_scalars(regularisation_parameter, lipschitz_const)
+    out = np.empty_like(data)
+    if is2d:
+        dy, dx = data.shape
+        dz, nd = 1, 2
+    else:
+        dz, dy, dx = data.shape
+        nd = 3
+    L = lib()
+    L.orc_pdtv_relaxed.argtypes = ([C.POINTER(C.c_float)] * 2 + [C.c_int] * 4 + [C.c_float] * 4 + [C.c_int] * 4 +
+                                   [C.c_uint32, C.POINTER(C.c_longlong), C.c_longlong, C.c_int])
+    L.orc_pdtv_relaxed.restype = C.c_int
+    counts = (C.c_longlong * 4)()
+    fidx, fit = (-1, -1) if fault is None else fault
+    rc = L.orc_pdtv_relaxed(_fptr(data), _fptr(out), dx, dy, dz, nd, sigma, tau, lt, theta, int(iterations),
+                            int(bool(methodTV)), int(bool(nonneg)), RELAXED_MODES[mode], int(seed) & 0xFFFFFFFF, counts,
+                            int(fidx), int(fit))
+    assert rc == 0
+    if is2d and squeeze:   # as pd_tv: a 2D result comes back with the singleton axis
+        out = np.expand_dims(out, axis)
+    if return_counts:
+        return out, dict(saturated=int(counts[0]), unsaturated=int(counts[1]), clipped=int(counts[2]),
+                         unclipped=int(counts[3]))
+    return out
+
+
 def rof_tv(data, regularisation_parameter=1e-5, iterations=3000, time_marching_parameter=0.001,
            half_precision=False):
     if data.dtype != np.float32:
@@ -294,6 +339,37 @@ def pd_step_slab(inp, u_in, u_out, p_in, p_out, dx, dy, nzl, has_lo, has_hi, sig
                     int(bool(nonneg)), int(bool(half)))
     for c in range(3):
         p_out[c][lo:lo + nzl] = torch.from_numpy(pout[c][lo:lo + nzl]).to(p_out[c].dtype)
+
+
+def pd_step_relaxed(inp, u_in, p_in, sigma, tau, lt, theta, methodTV, nonneg, offsets=None, has_lo=False, has_hi=False):
+    """One PD_TV iteration in the relaxed arithmetic of `pd_tv_relaxed` (orc_pdtv_step_relaxed) on float32 numpy arrays
+    [planes][dy][dx] that carry a ghost plane below / above where has_lo / has_hi.  `offsets`: int8 array of the slab's
+    shape, the reciprocal square root's distance from RN(1 / sqrt(x)) at every voxel (None: 0 everywhere).  Returns
+    (u_out, [p1, p2, p3], saturated): arrays of the slab's shape whose ghost planes are zero; `saturated` is 1 where the
+    voxel's dual left the unit ball and was projected."""
+    L = lib()
+    fp = C.POINTER(C.c_float)
+    i8 = C.POINTER(C.c_int8)
+    L.orc_pdtv_step_relaxed.argtypes = [fp] * 9 + [C.c_int] * 7 + [C.c_float] * 4 + [C.c_int] * 2 + [i8, i8]
+    L.orc_pdtv_step_relaxed.restype = None
+    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (inp, u_in, *p_in)]
+    planes, dy, dx = arrs[0].shape
+    assert all(a.shape == arrs[0].shape for a in arrs), [a.shape for a in arrs]
+    lo = 1 if has_lo else 0
+    out_end = planes - (1 if has_hi else 0)
+    offs_p = None
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.int8)
+        assert offsets.shape == arrs[0].shape, offsets.shape
+        offs_p = offsets.ctypes.data_as(i8)
+    u_out = np.zeros_like(arrs[0])
+    p_out = [np.zeros_like(arrs[0]) for _ in range(3)]
+    sat = np.zeros(arrs[0].shape, np.int8)
+    L.orc_pdtv_step_relaxed(*[_fptr(a) for a in arrs[:2]], _fptr(u_out), *[_fptr(a) for a in arrs[2:]],
+                            *[_fptr(a) for a in p_out], dx, dy, planes, lo, out_end, 0 if has_lo else 1,
+                            0 if has_hi else 1, sigma, tau, lt, theta, int(bool(methodTV)), int(bool(nonneg)), offs_p,
+                            sat.ctypes.data_as(i8))
+    return u_out, p_out, sat
 
 
 def pd_pair_slab(inp, u_in, u_out, p_in, p_out, dx, dy, nzl, lo, hi, sigma, tau, lt, theta, methodTV, nonneg, half,

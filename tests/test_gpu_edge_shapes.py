@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import _edge_shapes as E  # noqa: E402
 import _march_gpu as G  # noqa: E402
+import _pd_relaxed as R  # noqa: E402
 import _tgv_oracle as T  # noqa: E402
 from _march_gpu import same_bits  # noqa: E402
 
@@ -149,6 +150,7 @@ def test_pdtv_edges(oracle, pd_arith, launch, group, kind):
     march (2D: pd_rows2d at k = 3, 2 and 1); both dual types, both TV norms, with and without the non-negativity clip"""
     from tomobar_amd import ops
     scal = oracle.pd_scalars(0.04, 8.0)
+    mark = len(R.STATS)
     for case in E.cases(launch, group):
         for nn in (0, 1):
             for label, x in _tv_inputs(kind, case.shape, shifted=bool(nn)):
@@ -159,6 +161,11 @@ def test_pdtv_edges(oracle, pd_arith, launch, group, kind):
                             got = _run(lambda a, out: ops.pdtv(a, out, *scal, iters, mtv, nn, half), x)
                             pd_arith.check(got, want, half=half,
                                            what=f"{launch} {group} {case.shape} {label} x{iters} half={int(half)} mtv={mtv} nn={nn}")
+                            if not (pd_arith.exact or half):   # the shipped default, element for element (tests/_pd_relaxed.py)
+                                R.check_elementwise(got, x, R.Params(scal, iters, mtv, nn),
+                                                    what=f"{launch} {group} {case.shape} {label} x{iters} mtv={mtv} nn={nn}")
+    if not pd_arith.exact:
+        print(R.summary(mark, f"{launch} {group} {kind}"))
 
 
 # ------------------------------------------------------------------------------------------------ chunked z-slabs

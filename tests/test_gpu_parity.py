@@ -680,6 +680,11 @@ def test_pdtv_2d_large_images(oracle, ops, shape, iters, pd_arith):
         want = oracle.pd_tv(x, 0.03, iters, mtv, nn, 12.0, half)
         got = host(PD_TV_cupy(dev(x), 0.03, iters, mtv, nn, 12.0, 0, half))
         pd_arith.check(got, want, half=half, what=f"2D {shape} x{iters}")
+        if not (pd_arith.exact or half):   # the shipped default, element for element (tests/_pd_relaxed.py)
+            import _pd_relaxed as R
+            mark = len(R.STATS)
+            R.check_elementwise(got, x, R.params(0.03, iters, mtv, nn, 12.0), what=f"2D {shape} x{iters}")
+            print(R.summary(mark, f"2D {shape} x{iters}"))
 
 
 @pytest.mark.parametrize("flavour", ["shipped", pytest.param("dev", marks=DEV)])
@@ -714,6 +719,11 @@ def test_tv_random_shapes(oracle, ops, seed, flavour):
     if flavour == "shipped" and half:
         assert np.array_equal(got, want_pd), ("pd default, binary16 duals", shape, iters, mtv, nn)
     assert rel(got, want_pd) < (2e-4 if half else 1e-5), ("pd relaxed", shape, iters, half, mtv, nn, rel(got, want_pd))
+    if flavour == "shipped" and not half:   # the shipped default, element for element (tests/_pd_relaxed.py)
+        import _pd_relaxed as R
+        mark = len(R.STATS)
+        R.check_elementwise(got, x, R.params(lam, iters, mtv, nn, 8.0), what=f"random {shape} x{iters} mtv={mtv} nn={nn} lam={lam}")
+        print(R.summary(mark, f"random {shape} x{iters} mtv={mtv} nn={nn} lam={lam}"))
 
 
 def test_residual_buffer_must_match_the_contexts_layout(oracle):

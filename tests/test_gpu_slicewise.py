@@ -16,6 +16,7 @@ torch = pytest.importorskip("torch")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import _pd_relaxed as R  # noqa: E402
 import _slicewise_cases as S  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,17 @@ def rof(x, slicewise=False, out=None, tolerance=0.0, **kw):
     from tomobar_amd.regularisersCuPy import ROF_TV_cupy
     return ROF_TV_cupy(x, kw["regularisation_parameter"], kw["iterations"], kw["time_marching_parameter"], 0,
                        kw["half_precision"], out=out, tolerance=tolerance, slicewise=slicewise)
+
+
+def _elementwise(pd_arith, got, vol, kw, what):
+    """the shipped default with float32 duals, element for element against the relaxed model (tests/_pd_relaxed.py): bit
+    equality where the model has no hardware-dependent operation, else within four times the family's envelope"""
+    if pd_arith.exact or kw["half_precision"]:
+        return
+    mark = len(R.STATS)
+    R.check_elementwise(got, vol, R.params(kw["regularisation_parameter"], kw["iterations"], kw["methodTV"], kw["nonneg"],
+                                           kw["lipschitz_const"], slices=True), what=what)
+    print(R.summary(mark, what))
 
 
 def per_slice(fn, x, **kw):
@@ -80,6 +92,7 @@ def test_pd_tv_equals_the_2d_path_and_the_oracle_per_slice(case, half, pd_arith)
     same_bits(got, per_slice(pd, x, **kw), "2D path per slice")
     want = S.oracle_slices("PD_TV", vol, **kw)
     r = pd_arith.check(got, want, half=half, what=f"slicewise PD_TV {shape} x{iters}")
+    _elementwise(pd_arith, got, vol, kw, f"slicewise PD_TV {shape} x{iters}")
     print(f"PD_TV {shape} x{iters} {pd_arith.name} half={half}: rel-L2 vs oracle {r:.3e}")
     if shape in S.DISTINCT_SHAPES and iters == 7:   # 0.13-0.16 on the oracle
         gap = float(np.abs(S.oracle_3d("PD_TV", vol, **kw) - want).max())
@@ -99,6 +112,7 @@ def test_pd_tv_flags(case, methodTV, nonneg, half, pd_arith):
     same_bits(got, per_slice(pd, x, **kw), "2D path per slice")
     want = S.oracle_slices("PD_TV", vol, **kw)
     pd_arith.check(got, want, half=half, what=f"slicewise PD_TV {shape} x{iters} methodTV={methodTV} nonneg={nonneg}")
+    _elementwise(pd_arith, got, vol, kw, f"slicewise PD_TV {shape} x{iters} methodTV={methodTV} nonneg={nonneg}")
     if nonneg:   # the switch is live on this input: slice 0 is noise around zero
         assert not np.array_equal(want, S.oracle_slices("PD_TV", vol, **dict(kw, nonneg=0)))
 
@@ -238,6 +252,10 @@ def test_pd_tv_tolerance_is_one_decision_over_the_whole_stack(name, pd_arith):
     # relaxed float32 arithmetic is held to 1e-5 of the oracle, which moves d by at most about 2e-5 (tests/_tolerance_cases.py)
     _tolerance_case(name, lambda got, want, what: pd_arith.check(got, want, half=half, what=what),
                     _sum_margin if (half or pd_arith.exact) else (lambda d: 4e-5))
+    if not (half or pd_arith.exact):
+        # the run that stopped equals the run of that many iterations bit for bit (_tolerance_case): that one, element for element
+        full = dict(S.pd_kwargs(S.tol_plan(name)[1]), **S.TOL_CASES[name][1])
+        _elementwise(pd_arith, host(pd(dev(S.tol_input()), slicewise=True, **full)), S.tol_input(), full, f"slicewise tol {name}")
 
 
 @pytest.mark.parametrize("name", [n for n in sorted(S.TOL_CASES) if S.TOL_CASES[n][0] == "ROF_TV"])

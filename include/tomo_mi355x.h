@@ -773,6 +773,13 @@ int tomo_fbp_filter(int device, float *data_dev, size_t rows, int nu, float cuto
 int tomo_fourier_inv(int device, const float *data_dev, float *out_dev, int nz, int out_z, int nproj, int raw_n,
                      int n, int ne, int unpad_m, int out_size, const float *w_host, const float *theta_host,
                      int m, float mu, int center_size, void *stream);
+/* libtomo_mi355x_dev.so alone also exports tomo_fourier_gather, the gathering launch of the pipeline above on the caller's
+ * arrays (deliberately not declared: the shipped library has no such symbol; tomobar_amd/_lib.py DEV_SIGNATURES binds it where
+ * it exists).  Arguments, in order: int device; const float *g_dev, the polar samples as float2 [nproj][n][64] with the
+ * slice pair fastest; float *f_dev, the frequency grid as float2 [zc][2n][2n], every element of which is written (checkerboard
+ * sign of the first 2D shift included); int zc in 1..64; int nproj, n, m; float mu; int center_size; const float
+ * *theta_host; void *stream.  Same checks, same host tables (cosf / sinf, stable sort, in the scratch arena) and same launch
+ * as tomo_fourier_inv: one function each in csrc/fourier_inv.hip, called by both.  Synchronises the stream. */
 
 /* kernel-variant selector (per calling host thread): name in {"bp","fp","pdtv","roftv"}; variant 0 = the default of every
  * class.  The shipped library accepts two other values: "fp" 5 = the default kernels, but tomo_ctx_volume_zquad_ok answers no,

@@ -181,6 +181,11 @@ SIGNATURES = {
     "tomo_profile_enable": (_i, [_i]),
     "tomo_profile_read": (_i, [C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(_d)]),
 }
+# entry points of libtomo_mi355x_dev.so alone (described, not declared, in include/tomo_mi355x.h): bound where the loaded
+# library exports them, absent from the shipped one
+DEV_SIGNATURES = {
+    "tomo_fourier_gather": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),
+}
 
 LIB_PATHS = {"shipped": LIB_PATH, "dev": os.path.join(_HERE, "libtomo_mi355x_dev.so")}
 _handles = {}
@@ -209,6 +214,11 @@ def _load(flavour: str):
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in DEV_SIGNATURES.items():
+        if hasattr(handle, name):
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
     if handle.tomo_abi_version() != ABI_VERSION:
         raise ImportError(f"{os.path.basename(path)} has ABI version {handle.tomo_abi_version()}, this package binds "
                           f"version {ABI_VERSION}: rebuild it (make -C tomobar_amd/csrc all)")

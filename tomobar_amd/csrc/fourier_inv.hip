@@ -471,6 +471,43 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherArgs a, int zc)
     }
 }
 
+// ---- host side of the gathering: the angle tables and the launch (shared by tomo_fourier_inv and, in the dev flavour,
+// tomo_fourier_gather)
+struct GatherTables {
+    std::vector<float> ct, sn, sth;
+    std::vector<int> order;
+};
+
+// cos / sin per angle, angles sorted ascending (stable) with their original indices; uploads are enqueued on `st`, the
+// host copies in `t` must outlive them (the caller synchronises)
+int gather_tables_upload(GatherTables &t, const float *theta_host, int nproj, float *ct, float *sn, float *sth, int *order,
+                         hipStream_t st)
+{
+    int rc = TOMO_OK;
+    t.ct.resize(nproj); t.sn.resize(nproj); t.sth.resize(nproj); t.order.resize(nproj);
+    for (int i = 0; i < nproj; ++i) { t.ct[i] = cosf(theta_host[i]); t.sn[i] = sinf(theta_host[i]); t.order[i] = i; }
+    std::stable_sort(t.order.begin(), t.order.end(), [&](int p, int q) { return theta_host[p] < theta_host[q]; });
+    for (int i = 0; i < nproj; ++i) t.sth[i] = theta_host[t.order[i]];
+    TOMO_HIPG(hipMemcpyAsync(ct, t.ct.data(), nproj * sizeof(float), hipMemcpyHostToDevice, st));
+    TOMO_HIPG(hipMemcpyAsync(sn, t.sn.data(), nproj * sizeof(float), hipMemcpyHostToDevice, st));
+    TOMO_HIPG(hipMemcpyAsync(sth, t.sth.data(), nproj * sizeof(float), hipMemcpyHostToDevice, st));
+    TOMO_HIPG(hipMemcpyAsync(order, t.order.data(), nproj * sizeof(int), hipMemcpyHostToDevice, st));
+done:
+    return rc;
+}
+
+void gather_launch(const float2 *g, float2 *f, const float *ct, const float *sn, const float *sth, const int *order, int nproj,
+                   int n, int m, float mu, int center_size, int zc, hipStream_t st)
+{
+    GatherArgs ga;
+    ga.g = g; ga.f = f; ga.ct = ct; ga.st = sn; ga.sth = sth; ga.order = order;
+    ga.nproj = nproj; ga.n = n; ga.m = m; ga.mu = mu;
+    ga.center_size = center_size;
+    ga.use_center = center_size >= 192 ? 1 : 0;  // _CENTER_SIZE_MIN, methodsDIR_CuPy.py:23
+    dim3 grid(ceil_div(2 * n, 4 * GP), 2 * n);
+    gather_kernel<<<grid, 256, 0, st>>>(ga, zc);
+}
+
 // ---- unpadding: second c2dfftshift, 1/(2n)^2 of the unnormalised inverse transform, phi, slice un-pairing -----------
 // out[slice0 + 2z (+1)][ry][rx] from f[z][ky][kx]   (unpadding_mul_phi, fft_us_kernels.cu:605-658)
 __global__ __launch_bounds__(256) void unpad_kernel(const float2 *__restrict__ f, float *__restrict__ out, int n, int um, int size,
@@ -552,12 +589,8 @@ extern "C" int tomo_fourier_inv(int device, const float *data_dev, float *out_de
         float *sn = ct + nproj, *sth = sn + nproj;
         int *order = (int *)(sth + nproj);
 
-        // host-side tables: cos / sin per angle, angles sorted ascending (stable) with their original indices
-        std::vector<float> h_ct(nproj), h_sn(nproj), h_sth(nproj);
-        std::vector<int> h_order(nproj);
-        for (int i = 0; i < nproj; ++i) { h_ct[i] = cosf(theta_host[i]); h_sn[i] = sinf(theta_host[i]); h_order[i] = i; }
-        std::stable_sort(h_order.begin(), h_order.end(), [&](int p, int q) { return theta_host[p] < theta_host[q]; });
-        for (int i = 0; i < nproj; ++i) h_sth[i] = theta_host[h_order[i]];
+        GatherTables tabs;  // host copies: alive until the synchronisation below
+        if ((rc = gather_tables_upload(tabs, theta_host, nproj, ct, sn, sth, order, st)) != TOMO_OK) goto done;
         // Hermitian extension of the half-spectrum filter table: W[ne - k] = conj(W[k])
         std::vector<float2> h_w(ne);
         for (int k = 0; k < nh; ++k) h_w[k] = make_float2(w_host[2 * k], w_host[2 * k + 1]);
@@ -565,10 +598,6 @@ extern "C" int tomo_fourier_inv(int device, const float *data_dev, float *out_de
         h_w[0].y = 0.0f;       // a real inverse transform ignores the imaginary part of the DC and Nyquist bins
         h_w[ne / 2].y = 0.0f;  // (irfft, methodsDIR_CuPy.py:533): keep the two slices of a pair separate there too
         TOMO_HIPG(hipMemcpyAsync(w_dev, h_w.data(), (size_t)ne * sizeof(float2), hipMemcpyHostToDevice, st));
-        TOMO_HIPG(hipMemcpyAsync(ct, h_ct.data(), nproj * sizeof(float), hipMemcpyHostToDevice, st));
-        TOMO_HIPG(hipMemcpyAsync(sn, h_sn.data(), nproj * sizeof(float), hipMemcpyHostToDevice, st));
-        TOMO_HIPG(hipMemcpyAsync(sth, h_sth.data(), nproj * sizeof(float), hipMemcpyHostToDevice, st));
-        TOMO_HIPG(hipMemcpyAsync(order, h_order.data(), nproj * sizeof(int), hipMemcpyHostToDevice, st));
         TOMO_HIPG(hipStreamSynchronize(st));  // host vectors go out of scope at the end of this block only; be explicit
 
         const int pad_m = ne / 2 - raw_n / 2, crop_m = ne / 2 - n / 2;
@@ -596,15 +625,7 @@ extern "C" int tomo_fourier_inv(int device, const float *data_dev, float *out_de
                 transpose_scale_kernel<<<grid, 256, 0, st>>>(datac, g, zc, nproj, n, 4.0f / (float)n);
             }
             // ---- STEP 2: gathering on the 2n x 2n frequency grid (methodsDIR_CuPy.py:760-836)
-            {
-                GatherArgs ga;
-                ga.g = g; ga.f = f; ga.ct = ct; ga.st = sn; ga.sth = sth; ga.order = order;
-                ga.nproj = nproj; ga.n = n; ga.m = m; ga.mu = mu;
-                ga.center_size = center_size;
-                ga.use_center = center_size >= 192 ? 1 : 0;  // _CENTER_SIZE_MIN, methodsDIR_CuPy.py:23
-                dim3 grid(ceil_div(two_n, 4 * GP), two_n);
-                gather_kernel<<<grid, 256, 0, st>>>(ga, zc);
-            }
+            gather_launch(g, f, ct, sn, sth, order, nproj, n, m, mu, center_size, zc, st);
             // ---- STEP 3: 2D inverse FFT (methodsDIR_CuPy.py:851-897); the shifts live in the neighbouring kernels
             TOMO_FFT(hipfftExecC2C(p_2d, (hipfftComplex *)f, (hipfftComplex *)f, HIPFFT_BACKWARD));
             // ---- STEP 4: unpadding x phi (methodsDIR_CuPy.py:920-967)
@@ -621,3 +642,35 @@ done:
     if (rc != TOMO_OK) (void)hipStreamSynchronize(st);
     return rc;
 }
+
+#if TOMO_DEV
+// The gathering launch of tomo_fourier_inv alone, on the caller's arrays (tests/test_gpu_fourier_gather.py): g_dev is
+// float2 [nproj][n][64] (slice pair fastest), f_dev float2 [zc][2n][2n]; the same table set-up and the same launch.
+extern "C" int tomo_fourier_gather(int device, const float *g_dev, float *f_dev, int zc, int nproj, int n, int m, float mu,
+                                   int center_size, const float *theta_host, void *stream)
+{
+    TOMO_REQUIRE(device >= 0 && g_dev && f_dev && theta_host, "NULL argument");
+    TOMO_REQUIRE(n >= 2 && n % 2 == 0 && zc >= 1 && zc <= FZ, "the detector size must be even and 1 <= zc <= 64");
+    TOMO_REQUIRE(nproj >= 1 && m >= 1 && m <= 64 && mu > 0.0f, "bad Fourier reconstruction parameters");
+    TOMO_REQUIRE(center_size >= 0 && center_size <= 2 * n, "bad centre size");
+    TOMO_REQUIRE(2L * n <= 32768, "detector too wide for the Fourier reconstruction grid");
+    TOMO_ON_DEVICE(device);
+    hipStream_t st = as_stream(stream);
+    int rc = TOMO_OK;
+    void *base = nullptr;
+    rc = tomo_arena_get(device, st, ARENA_MAIN, (size_t)nproj * 3 * sizeof(float) + (size_t)nproj * sizeof(int) + 1024, &base);
+    if (rc != TOMO_OK) return rc;
+    {
+        float *ct = (float *)base, *sn = ct + nproj, *sth = sn + nproj;
+        int *order = (int *)(sth + nproj);
+        GatherTables tabs;
+        if ((rc = gather_tables_upload(tabs, theta_host, nproj, ct, sn, sth, order, st)) != TOMO_OK) goto done;
+        gather_launch((const float2 *)g_dev, (float2 *)f_dev, ct, sn, sth, order, nproj, n, m, mu, center_size, zc, st);
+        TOMO_HIPG(hipGetLastError());
+        TOMO_HIPG(hipStreamSynchronize(st));  // the tables' host copies and the arena are released on return
+    }
+done:
+    if (rc != TOMO_OK) (void)hipStreamSynchronize(st);
+    return rc;
+}
+#endif  // TOMO_DEV

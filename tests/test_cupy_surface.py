@@ -92,11 +92,20 @@ def test_cupy_in_cupy_out_zero_copy(monkeypatch, oracle):
     assert np.array_equal(bck.get(), dr.BACKPROJ(torch.from_dlpack(fwd)).cpu().numpy())
 
 
+@pytest.fixture(scope="module")
+def sleep_calibrated():
+    import _on_stream
+    _on_stream.calibrate()
+    return _on_stream
+
+
 @pytest.mark.gpu
-def test_cupy_caller_on_its_own_stream(monkeypatch):
+def test_cupy_caller_on_its_own_stream(monkeypatch, sleep_calibrated):
     """INTEGRATION.md, stream rule: the classes order their work on torch's CURRENT stream.  A CuPy caller that computes on
     a non-default stream hands that stream to torch (``torch.cuda.ExternalStream(cupy_stream.ptr)``) -- then the library's
-    launches are ordered behind the caller's own kernels without any synchronisation."""
+    launches are ordered behind the caller's own kernels without any synchronisation.  The caller's stream is busy with a delay
+    and its data arrive behind it (tests/_on_stream.py): a launch that is not ordered on that stream sees NaN."""
+    S = sleep_calibrated
     cupy = _cupy_standin.install(monkeypatch)
     from tomobar_amd.regularisersCuPy import PD_TV_cupy
     side = torch.cuda.Stream()                                  # stands for cupy.cuda.Stream(non_blocking=True)
@@ -104,8 +113,12 @@ def test_cupy_caller_on_its_own_stream(monkeypatch):
     vol = torch.rand((12, 64, 64), device="cuda")
     want = PD_TV_cupy(vol * 2.0, 0.05, 6)
     torch.cuda.synchronize()
+    vol_host = vol.cpu().numpy()
     with torch.cuda.stream(ext):
-        x = vol * 2.0                                           # the caller's own kernel, queued on its stream ...
+        PD_TV_cupy(cupy.ndarray(vol * 2.0), 0.05, 6)            # warm: this stream's scratch arena
+        ext.synchronize()
+        late = S.Late(side, asynchronous=False, label="cupy caller")
+        x = late.ro(vol_host).view * 2.0                        # the caller's own kernel, queued on its stream behind the delay ...
         got = PD_TV_cupy(cupy.ndarray(x), 0.05, 6)              # ... and the proximal step right behind it, no sync between
     ext.synchronize()
     assert type(got) is cupy.ndarray and np.array_equal(got.get(), want.cpu().numpy())

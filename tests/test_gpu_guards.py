@@ -65,6 +65,10 @@ class Arrays:
     def out(self, shape, shift=None, **kw):
         return self.rw(tuple(shape), shift, **kw)
 
+    def done(self):
+        """a call that returns its result to the host has returned (the late provider of tests/_on_stream.py starts the
+        next call behind a new delay; here there is nothing to do)"""
+
     def check(self, what):
         for k, g in enumerate(self.all):
             g.check((what, "array", k), read_only=any(g is r for r in self.read_only))
@@ -124,11 +128,15 @@ def _nsel(P, s):
 def test_projector_pair_and_matched_adjoint(oracle, g):
     """tomo_fp3d, tomo_bp3d, tomo_bp3d_matched: bit for bit against the oracles of tests/test_gpu_parity.py and
     tests/test_gpu_matched_bp.py, every subset"""
+    case_projector_pair_and_matched_adjoint(Arrays, oracle, g)
+
+
+def case_projector_pair_and_matched_adjoint(mk, oracle, g):
     P, PM, H = _pair(oracle, g)
     rng = np.random.default_rng(2)
     vol = rng.standard_normal((P.nz, P.n, P.n)).astype(np.float32)
     for s in _subsets(P):
-        A = Arrays()
+        A = (mk or Arrays)()
         v, sino_out = A.ro(vol), A.out(H.sino_shape(s))
         assert H.forward(v.view, s, out=sino_out.view) is sino_out.view
         same_bits(sino_out.host(), P.fp(vol, s), (g, s, "fp"))
@@ -156,6 +164,10 @@ def test_fused_residuals(oracle, g, layout):
     """tomo_fp3d_residual (LS / PWLS / KL) and tomo_fp3d_residual_robust in both residual layouts, the residual buffer of
     exactly tomo_ctx_residual_elems floats; tomo_fp3d_residual_ring (planar only: it refuses the quad layout).  Expected values
     as tests/test_gpu_parity.py::test_fused_residual_and_gradient_steps and tests/test_robust_terms.py form them."""
+    case_fused_residuals(Arrays, oracle, g, layout)
+
+
+def case_fused_residuals(mk, oracle, g, layout):
     from _cpu_backend import OracleTools3D
     P, _, H = _pair(oracle, g)
     rng = np.random.default_rng(3)
@@ -183,7 +195,7 @@ def test_fused_residuals(oracle, g, layout):
             wants = [("LS", None, stated("LS")), ("PWLS", None, raw), ("KL", None, stated("KL")),
                      ("PWLS", ("huber", 3.0), oracle.robust_weight(raw, huber=3.0)),
                      ("PWLS", ("studentst", 2.0), oracle.robust_weight(raw, studentst=2.0))]
-            A = Arrays()
+            A = (mk or Arrays)()
             xd, bd, wd = A.ro(x), A.ro(b), A.ro(w)
             for fid, robust, want in wants:
                 res = A.out(shape, planes=4 * na_s * P.nu)
@@ -210,6 +222,10 @@ def test_fused_residuals(oracle, g, layout):
 def test_fused_epilogues_of_both_adjoints(oracle, g, adjoint, shift):
     """tomo_bp3d[_matched]_fista / _fista_momentum / _admm with every volume array at `shift`: the oracle's gradient pushed
     through the one restatement of tests/test_gpu_bp_epilogues.py, array_equal"""
+    case_fused_epilogues_of_both_adjoints(Arrays, oracle, g, adjoint, shift)
+
+
+def case_fused_epilogues_of_both_adjoints(mk, oracle, g, adjoint, shift):
     import test_gpu_bp_epilogues as EP
     P, PM, H = _pair(oracle, g)
     H.adjoint = adjoint
@@ -219,7 +235,7 @@ def test_fused_epilogues_of_both_adjoints(oracle, g, adjoint, shift):
     for s in _subsets(P):
         r = rng.standard_normal((P.nz, _nsel(P, s), P.nu)).astype(np.float32)
         grad = (PM if adjoint == "matched" else P).bp(r, s)
-        A = Arrays(shift)
+        A = (mk or Arrays)(shift)
         rd = A.ro(r, shift=0)
         for nonneg in (False, True):
             (X,) = EP.restate("fista", grad, x, nonneg=nonneg)
@@ -242,15 +258,19 @@ def test_fused_epilogues_of_both_adjoints(oracle, g, adjoint, shift):
 def test_volume_zquad_producers(oracle):
     """tomo_volume_to_zquad and tomo_momentum_transposed (both layouts) on the 64-wide geometry, X_t of exactly
     tomo_ctx_volume_elems floats; expected as tests/test_gpu_volume_zquad.py forms it"""
+    case_volume_zquad_producers(Arrays, oracle)
+
+
+def case_volume_zquad_producers(mk, oracle, pair=None):
     from test_gpu_volume_zquad import _relay
     g = GEOMS[2]
-    P, _, H = _pair(oracle, g)
+    P, _, H = pair or _pair(oracle, g)      # (a context's transposed-volume scratch grows, once, with the first quad-interleaved call)
     rng = np.random.default_rng(22)
     vshape = (P.nz, P.n, P.n)
     x, xold = (rng.standard_normal(vshape).astype(np.float32) for _ in range(2))
     beta = F32(0.7391357421875)
     want = x + beta * (x - xold)
-    A = Arrays()
+    A = (mk or Arrays)()
     xd, xo = A.ro(x), A.ro(xold)
     try:
         assert int(lib().tomo_ctx_volume_elems(H._ctx)) == int(np.prod(vshape))
@@ -278,13 +298,17 @@ def test_volume_zquad_producers(oracle):
 def test_slicewise_tv(oracle, pd_arith):
     """tomo_pdtv_slices / tomo_roftv_slices on an all-odd stack and the smallest stack of tests/_slicewise_cases.py (a slice-wise
     operator has no 2D input), against the oracle per slice as tests/test_gpu_slicewise.py compares them"""
+    case_slicewise_tv(Arrays, oracle, pd_arith)
+
+
+def case_slicewise_tv(mk, oracle, pd_arith):
     import _slicewise_cases as S
     from test_gpu_slicewise import pd, rof
     for shape, iters in (((3, 9, 59), 7), ((2, 2, 2), 7)):
         assert (shape, iters) in S.PD_CASES and (shape, iters) in S.ROF_CASES
         vol = S.volume(shape)
         for half in (False, True):
-            A = Arrays()
+            A = (mk or Arrays)()
             x, out = A.ro(vol), A.out(shape)
             kw = S.rof_kwargs(iters, half)
             rof(x.view, slicewise=True, out=out.view, **kw)
@@ -301,6 +325,10 @@ def test_slicewise_tv(oracle, pd_arith):
 def test_wavelets(shape):
     """tomo_wavelet_shrink / _forward / _inverse, the pyramid of exactly wavelet_pyramid_floats floats (tomo_wavelet_forward and
     tomo_wavelet_inverse through the C entry: the wrapper of the first allocates its own pyramid)"""
+    case_wavelets(Arrays, shape)
+
+
+def case_wavelets(mk, shape):
     from test_gpu_wavelets import mix_of, want
     from _tgv_oracle import phantom
     from tomobar_amd import ops
@@ -309,7 +337,7 @@ def test_wavelets(shape):
     m_host = mix_of(shape)
     dz, dy, dx = (1, *shape) if len(shape) == 2 else shape
     nd, plane = len(shape), shape[-1] * shape[-2]
-    A = Arrays()
+    A = (mk or Arrays)()
     x, m, out, mixed = A.ro(f), A.ro(m_host), A.out(shape), A.out(shape)
     ops.wavelet_shrink(x.view, F32(t), out=out.view)
     same_bits(out.host(), w, (shape, "shrink"))
@@ -331,12 +359,16 @@ def test_wavelets(shape):
 def test_patch_select_and_nltv(shape, params):
     """tomo_patch_select (C entry: the wrapper allocates its tables) and tomo_nltv with the uint16 tables and the weights
     guarded, against tests/_nltv_oracle.py as tests/test_gpu_nltv.py compares them"""
+    case_patch_select_and_nltv(Arrays, shape, params)
+
+
+def case_patch_select_and_nltv(mk, shape, params):
     import test_gpu_nltv as TN
     from tomobar_amd import ops
     img, tables = TN.oracle_tables("noisy", shape, params)
     S_, P_, K = params
     dz, dy, dx = (1, *shape) if len(shape) == 2 else shape
-    A = Arrays()
+    A = (mk or Arrays)()
     x = A.ro(np.array(img))
     hi, hj = (A.out((K, *shape), dtype=np.uint16, fill=0xFFFF) for _ in range(2))
     wt = A.out((K, *shape))
@@ -357,10 +389,14 @@ def test_patch_select_and_nltv(shape, params):
 @pytest.mark.parametrize("nu", [45, 64])
 def test_fbp_filter_in_place(oracle, nu):
     """tomo_fbp_filter in place on 7 rows, at the bound of tests/test_fbp.py"""
+    case_fbp_filter_in_place(Arrays, oracle, nu)
+
+
+def case_fbp_filter_in_place(mk, oracle, nu):
     from test_fbp import rel
     rows, cutoff = 7, 0.6
     x = np.random.default_rng(3).random((rows, 1, nu)).astype(np.float32)
-    A = Arrays()
+    A = (mk or Arrays)()
     d = A.rw(x)
     ok(lib().tomo_fbp_filter(0, vp(d.view), rows, nu, cutoff, 1.0 / rows / nu, stream()))
     want = oracle.fbp_filter(x, cutoff)
@@ -372,13 +408,17 @@ def test_fourier_inv(monkeypatch):
     """tomo_fourier_inv at the smallest case of tests/test_fourier.py (even sizes: the driver hands its input straight to
     the entry point).  The driver prepares the arguments; the entry point runs first on the guarded input with a guarded
     output in place of the driver's own, and that output is held to the bounds of test_FOURIER_INV_vs_oracle_and_fixture."""
+    case_fourier_inv(Arrays, monkeypatch)
+
+
+def case_fourier_inv(mk, monkeypatch):
     import test_fourier as TF
     from oracle import fourier_oracle as FO
     golden = np.load(os.path.join(TF.HERE, "golden", "fourier_golden.npz"))
     case = min(TF.CASES, key=lambda c: golden[c[0] + "_sino"].size)
     name, nz, nproj, dn, rs, cor, span, kw = case
     assert nz % 2 == 0 and dn % 2 == 0 and "data_axes_labels_order" not in kw and "recon_mask_radius" not in kw
-    A = Arrays()
+    A = (mk or Arrays)()
     src = A.ro(np.ascontiguousarray(golden[name + "_sino"], np.float32))
     real, outs = lib().tomo_fourier_inv, []
 
@@ -446,13 +486,13 @@ EW = {
 }
 
 
-def _ew_case(oracle, name, n, in_shift, out_shift, seed=7):
+def _ew_case(oracle, name, n, in_shift, out_shift, seed=7, mk=None):
     ins_of, initial, call, want_of = EW[name]
     rng = np.random.default_rng(seed + n)
     x, y, z = (rng.standard_normal(n).astype(np.float32) for _ in range(3))
     want = oracle.pwls_weights(x) if want_of is None else want_of(x, y, z)
     assert want.dtype == np.float32
-    A = Arrays()
+    A = (mk or Arrays)()
     ins = [A.ro(a, shift=in_shift) for a in ins_of(x, y, z)]
     out = A.out((n,), shift=out_shift) if initial is None else A.rw({"x": x, "y": y}[initial], shift=out_shift)
     ok(call(lib(), [g.view for g in ins], out.view, n))
@@ -470,24 +510,29 @@ def test_elementwise_entries(oracle, name):
     _ew_case(oracle, name, 4099, 0, 1)
 
 
-def _reductions(n, shift, what):
+def _reductions(n, shift, what, mk=None):
     """tomo_norm2 / tomo_dot at the tolerances of test_glue_kernels; tomo_max / tomo_pwls_max exactly (the maximum of float32
     values is one of them: no rounding takes part)"""
     rng = np.random.default_rng(70 + n)
     x, y = (rng.standard_normal(n).astype(np.float32) for _ in range(2))
-    A = Arrays(shift)
+    A = (mk or Arrays)(shift)
     xd, yd = A.ro(x), A.ro(y)
     out, outf = C.c_double(0.0), C.c_float(0.0)
     ok(lib().tomo_norm2(vp(xd.view), n, C.byref(out), stream()))
+    A.done()
     np.testing.assert_allclose(out.value, np.linalg.norm(x.astype(np.float64)), rtol=1e-12)
     ok(lib().tomo_dot(vp(xd.view), vp(yd.view), n, C.byref(out), stream()))
+    A.done()
     np.testing.assert_allclose(out.value, np.dot(x.astype(np.float64), y.astype(np.float64)), rtol=1e-9, atol=1e-12)
     ok(lib().tomo_max(vp(xd.view), n, C.byref(outf), stream()))
+    A.done()
     assert outf.value == float(x.max()), (what, n, shift, "max")
     ok(lib().tomo_pwls_max(vp(xd.view), n, C.byref(outf), stream()))
+    A.done()
     assert outf.value == float(np.maximum(x, F32(1e-6)).max()), (what, n, shift, "pwls_max")
     small = A.ro(-np.abs(x))       # nothing above the clamp: the clamp itself is the maximum
     ok(lib().tomo_pwls_max(vp(small.view), n, C.byref(outf), stream()))
+    A.done()
     assert outf.value == float(F32(1e-6))
     A.check((what, n, shift))
 
@@ -498,12 +543,12 @@ def test_reductions():
             _reductions(n, shift, "reductions")
 
 
-def _rel_change(n, shifts, mode, x_h, r_h, want):
+def _rel_change(n, shifts, mode, x_h, r_h, want, mk=None):
     """one tomo_rel_change call at the bound of tests/test_gpu_tolerance.py::test_rel_change_kernel"""
     import _tolerance_cases as T
     from tomobar_amd import ops
     sx, sr, sk = shifts
-    A = Arrays()
+    A = (mk or Arrays)()
     x, ref = A.ro(x_h, shift=sx), A.rw(r_h, shift=sr)
     keep = A.out((n,), shift=sk) if mode == "separate" else None
     got = ops.rel_change(x.view, ref.view, None if mode == "absent" else (ref.view if mode == "aliasing" else keep.view))
@@ -537,8 +582,12 @@ def test_rel_change():
 # ================================================================================================ glue: pre / post
 def test_pad_crop_mask_permute(oracle):
     """the four pre / post kernels at the shapes of tests/test_gpu_parity.py::test_pad_crop_mask_permute, outputs passed in"""
+    case_pad_crop_mask_permute(Arrays, oracle)
+
+
+def case_pad_crop_mask_permute(mk, oracle):
     rng = np.random.default_rng(8)
-    A = Arrays()
+    A = (mk or Arrays)()
     b = rng.random((3, 7, 10)).astype(np.float32)
     bd, out = A.ro(b), A.out((3, 7, 18))
     ok(lib().tomo_pad_edge(vp(bd.view), vp(out.view), 3 * 7, 10, 4, stream()))
@@ -585,12 +634,15 @@ def _seam(**kw):
 def test_shift_rows_residual_ring_robust(oracle):
     """tomo_shift_rows, tomo_sino_residual, tomo_sino_add_ring, tomo_sino_robust against the formulas the oracle and the CPU
     stand-in of the projector (tests/_cpu_backend.py) state, bit for bit as the driver tests hold them"""
+    case_shift_rows_residual_ring_robust(Arrays, oracle)
+
+
+def case_shift_rows_residual_ring_robust(mk, oracle):
     from _cpu_backend import OracleTools3D
     from tomobar_amd import _lib as L
     res, full, wfull, ring = _sino_terms_inputs()
-    A = Arrays()
+    A = (mk or Arrays)()
     src = A.ro(SRC)
-    assert src.view.dtype == torch.int32
     # shift_rows, both signs: integer, fractional, negative shifts and one that leaves the detector
     shift = np.array([0.0, 1.0, 0.25, -0.75, 2.5, -3.5, 0.999], np.float32)
     ns = types.SimpleNamespace(nz=NZ, na=NA_S, vshift=shift, subsets=None)
@@ -628,16 +680,21 @@ def test_shift_rows_residual_ring_robust(oracle):
         io = A.rw(raw)
         ok(lib().tomo_sino_robust(vp(io.view), raw.size, L.ROBUST[mode], delta, stream()))
         same_bits(io.host(), oracle.robust_weight(raw, **{mode: delta}), ("sino_robust", mode))
+    assert src.view.dtype == torch.int32
     A.check("sinogram terms")
 
 
 def test_ring_terms():
     """tomo_ring_gh_reduce (with and without PWLS weights), tomo_ring_gh_update, tomo_swls_apply at (nz, na_s, nu) = (3, 7, 45)
     with an index table into 19 angles, against the formulas of tests/_cpu_backend.py"""
+    case_ring_terms(Arrays)
+
+
+def case_ring_terms(mk):
     from _cpu_backend import OracleTools3D
     res, full, wfull, ring = _sino_terms_inputs()
     l_inv, lam, beta = F32(1 / 300.0), F32(0.3), F32(0.37)
-    A = Arrays()
+    A = (mk or Arrays)()
     src, wd, rx = A.ro(SRC), A.ro(wfull), A.ro(ring)
     for weights in (None, wfull):
         want_res, want_r = torch.from_numpy(res.copy()), torch.empty((NZ, NU), dtype=torch.float32)
@@ -675,6 +732,10 @@ def test_halo_staging():
     """tomo_halo_pack / _unpack / _pack2 / _pull2 with the blocks of tests/test_gpu_slab.py::test_halo_pack_unpack_round_trip
     (odd byte counts, starts that are not 4-byte aligned), every block a slice of a guarded byte buffer and the staging
     buffer of exactly tomo_halo_staging_bytes bytes"""
+    case_halo_staging(Arrays)
+
+
+def case_halo_staging(mk):
     from tomobar_amd.slab import _halo_staging_bytes
     rng = np.random.default_rng(3)
     u = rng.random((7, 13, 37)).astype(np.float32).view(np.uint8).ravel()                  # 1924 B per plane
@@ -689,7 +750,7 @@ def test_halo_staging():
     for (a, lo, hi), nb in zip(cuts, nbytes):
         image[off:off + nb] = a[lo:hi]
         off += (nb + 15) // 16 * 16
-    A = Arrays()
+    A = (mk or Arrays)()
     srcs = {id(a): A.ro(a) for a in (u, p, b)}
     blocks = [srcs[id(a)].view[lo:hi] for a, lo, hi in cuts]
     assert any(t.data_ptr() % 4 for t in blocks) and any(nb % 2 for nb in nbytes)
@@ -764,6 +825,10 @@ def test_grid_stride_elementwise_and_rel_change(oracle, n, shift):
 def test_grid_stride_stream_kernels(n, shift):
     """pdhg_sino_dual, spdhg_sino_dual, spdhg_primal (stream3_kernel) against tests/_pdhg_oracle.py / tests/_spdhg_oracle.py,
     bit for bit as tests/test_gpu_pdhg.py and tests/test_gpu_spdhg.py hold them"""
+    case_stream_kernels(Arrays, n, shift)
+
+
+def case_stream_kernels(mk, n, shift):
     import _pdhg_oracle as P
     import _spdhg_oracle as S
     from test_gpu_pdhg import _sino_inputs
@@ -772,7 +837,7 @@ def test_grid_stride_stream_kernels(n, shift):
     y, r, b = _sino_inputs((n,))
     sigma = F32(0.4)
     for fidelity in P.FIDELITIES:
-        A = Arrays(shift)
+        A = mk(shift)
         yd, rd, bd = A.rw(y), A.ro(r), A.ro(b)
         ops.pdhg_sino_dual(yd.view, rd.view, bd.view, fidelity, sigma)
         same_bits(yd.host(), P.sino_dual(y, r, b, fidelity, sigma), ("pdhg_sino_dual", n, fidelity))
@@ -785,7 +850,7 @@ def test_grid_stride_stream_kernels(n, shift):
     x, z, delta = _primal_inputs((n,))
     tau, w = F32(0.05), F32(4.0)
     for nonneg in (0, 1):
-        A = Arrays(shift)
+        A = mk(shift)
         xd, zd, dd = A.rw(x), A.rw(z), A.ro(delta)
         ops.spdhg_primal(xd.view, zd.view, dd.view, tau, w, nonneg)
         want_x, want_z = S.primal_step(x, z, delta, tau, w, nonneg)

@@ -163,6 +163,20 @@ def test_errors_match_reference(geom):
         RecToolsIRCuPy(16, 0, 4, 0.0, geom["angles"], 16, OS_number=0)
 
 
+def sirt_with_the_oracle(oracle, geom, iterations):
+    """the SIRT loop (methodsIR_CuPy.py:176-232 of the reference) written with the oracle's operators (also the expected value
+    of tests/test_gpu_streams.py)"""
+    sino, nz, n = geom["sino"], geom["nz"], geom["n"]
+    P = oracle.Projector(nz, n, n, geom["angles"])
+    with np.errstate(divide="ignore"):
+        R = np.nan_to_num(np.float32(1) / P.fp(np.ones((nz, n, n), np.float32)), nan=1.0, posinf=1.0, neginf=1.0)
+        Cm = np.nan_to_num(np.float32(1) / P.bp(np.ones_like(sino)), nan=1.0, posinf=1.0, neginf=1.0)
+    x = np.ones((nz, n, n), np.float32)
+    for _ in range(iterations):
+        x = x + Cm * P.bp(R * (sino - P.fp(x)))
+    return x
+
+
 def test_simple_iterative_methods_vs_oracle(oracle, geom):
     """Landweber / SIRT / CGLS loops (methodsIR_CuPy.py:128-309 of the reference) on the HIP operators vs the same
     loops written with the oracle's operators."""
@@ -175,14 +189,8 @@ def test_simple_iterative_methods_vs_oracle(oracle, geom):
     got = host(make(geom).Landweber(data_dict(geom), {"iterations": 5, "tau_step_lanweber": 1e-3, "recon_mask_radius": None}))
     assert rel(got, x) < TOL
     # SIRT
-    with np.errstate(divide="ignore"):
-        R = np.nan_to_num(np.float32(1) / P.fp(np.ones((nz, n, n), np.float32)), nan=1.0, posinf=1.0, neginf=1.0)
-        Cm = np.nan_to_num(np.float32(1) / P.bp(np.ones_like(sino)), nan=1.0, posinf=1.0, neginf=1.0)
-    x = np.ones((nz, n, n), np.float32)
-    for _ in range(4):
-        x = x + Cm * P.bp(R * (sino - P.fp(x)))
     got = host(make(geom).SIRT(data_dict(geom), {"iterations": 4, "recon_mask_radius": None}))
-    assert rel(got, x) < TOL
+    assert rel(got, sirt_with_the_oracle(oracle, geom, 4)) < TOL
     # CGLS
     x = np.zeros(nz * n * n, np.float32)
     d = P.bp(sino).ravel()

@@ -27,8 +27,18 @@ def test_pdtv_slabs_equal_whole_volume(world, half, variant):
     run_pdtv_slabs(world, half, variant)
 
 
-def run_pdtv_slabs(world, half, variant, shape=(23, 37, 150), iters_list=(7, 4), methodTV=0, nonneg=1, seed=9):
-    """(also driven over random shapes / splits / iteration counts by tools/fuzz_campaign.py --slabs)"""
+def _to_device(vol):
+    return torch.from_numpy(vol).cuda()
+
+
+def _to_host(t):
+    return t.cpu().numpy()
+
+
+def run_pdtv_slabs(world, half, variant, shape=(23, 37, 150), iters_list=(7, 4), methodTV=0, nonneg=1, seed=9,
+                   to_device=_to_device, to_host=_to_host):
+    """(also driven over random shapes / splits / iteration counts by tools/fuzz_campaign.py --slabs; tests/test_gpu_streams.py
+    passes its own `to_device` / `to_host`: the volume arrives late on a side stream and is read back on it)"""
     ranges = variant == "ranges"  # the overlapped schedule of pd_tv_slab: edge planes first, then the interior
     variant = 0 if ranges else variant
     from tomobar_amd import ops
@@ -39,12 +49,11 @@ def run_pdtv_slabs(world, half, variant, shape=(23, 37, 150), iters_list=(7, 4),
         nz, dy, dx = shape
         rng = np.random.default_rng(seed)
         vol = (rng.random((nz, dy, dx)) * 0.3 + (np.indices((nz, dy, dx))[2] > dx // 2) - 0.5).astype(np.float32)
-        vd = torch.from_numpy(vol).cuda()
+        vd = to_device(vol)
         tau = np.float32(0.04 * 0.1)
         sigma = np.float32(1.0 / (8.0 * tau))
         lt = np.float32(tau / 0.04)
         for iters in iters_list:  # pairs + an odd trailing iteration / pairs only
-            want = PD_TV_cupy(vd, 0.04, iters, methodTV, nonneg, 8.0, 0, half).cpu().numpy()
             states = []
             for r in range(world):
                 z0, z1 = slab_bounds(nz, world, r)
@@ -75,7 +84,8 @@ def run_pdtv_slabs(world, half, variant, shape=(23, 37, 150), iters_list=(7, 4),
                     else:
                         s.single(*args)
                 _copy_halos(states, states[0].cur)
-            got = torch.cat([s.result() for s in states]).cpu().numpy()
+            got = to_host(torch.cat([s.result() for s in states]))
+            want = to_host(PD_TV_cupy(vd, 0.04, iters, methodTV, nonneg, 8.0, 0, half))
             assert np.array_equal(got, want), (shape, world, iters, np.abs(got - want).max())
     finally:
         ops.set_variant("pdtv", 0)
@@ -87,14 +97,13 @@ def test_roftv_slabs_equal_whole_volume(world, half):
     run_roftv_slabs(world, half)
 
 
-def run_roftv_slabs(world, half, shape=(19, 21, 90), iters=6, seed=10):
+def run_roftv_slabs(world, half, shape=(19, 21, 90), iters=6, seed=10, to_device=_to_device, to_host=_to_host):
     from tomobar_amd.regularisersCuPy import ROF_TV_cupy
     from tomobar_amd.slab import RofSlab, _hip_rof_step, slab_bounds
     nz, dy, dx = shape
     rng = np.random.default_rng(seed)
     vol = (rng.random((nz, dy, dx)) * 0.3 + (np.indices((nz, dy, dx))[2] > dx // 2)).astype(np.float32)
-    vd = torch.from_numpy(vol).cuda()
-    want = ROF_TV_cupy(vd, 0.05, iters, 0.005, 0, half).cpu().numpy()
+    vd = to_device(vol)
     states = []
     for r in range(world):
         z0, z1 = slab_bounds(nz, world, r)
@@ -112,7 +121,8 @@ def run_roftv_slabs(world, half, shape=(19, 21, 90), iters=6, seed=10):
         for s in states:
             s.step(it, np.float32(0.05), np.float32(0.005))
         _copy_halos(states, (it + 1) & 1)
-    got = torch.cat([s.local(s.U[iters & 1]) for s in states]).cpu().numpy()
+    got = to_host(torch.cat([s.local(s.U[iters & 1]) for s in states]))
+    want = to_host(ROF_TV_cupy(vd, 0.05, iters, 0.005, 0, half))
     assert np.array_equal(got, want), (shape, world, iters, np.abs(got - want).max())
 
 

@@ -417,8 +417,10 @@ class RecToolsIRCuPy:
         iteration is one forward projection, one matched back projection and one stencil pass, with no inner loop.
         ``"PD_TGV"`` puts the second-order TGV term lambda min_v (alpha1 |grad x - v| + alpha0 |E v|) there instead
         (``regul_param``, ``TGV_alpha1``, ``TGV_alpha2``): one TGV dual and one TGV primal launch per iteration.
-        ``_algorithm_["PDHG_ratio"]`` is sigma / tau (default 1).  Needs ``adjoint="matched"``; no ordered subsets, no
-        z-slabs.  Returns the float32 volume ``[detY, N, N]``."""
+        ``_algorithm_["PDHG_ratio"]`` is sigma / tau (default 1).  ``_data_["stripe_lambda"]`` = mu (default None: off) adds a
+        stripe variable against ring artefacts: min_{x, s} F(Ax + Ss) + lambda R(x) + mu |s|_1 with one offset s[z, u] per
+        detector pixel, added to every angle; ``last_run["stripes"]`` returns it as ``[detY, detX]``.  Needs
+        ``adjoint="matched"``; no ordered subsets, no z-slabs.  Returns the float32 volume ``[detY, N, N]``."""
         (d, a, r, x, _, _) = self.__common_initialisation(_data_, _algorithm_, _regularisation_, "PDHG")
         A = self.Atools
         b = d["projection_data"]
@@ -431,6 +433,9 @@ class RecToolsIRCuPy:
         diag = a["PDHG_preconditioner"] == "diagonal"
         rho = float32(a["PDHG_ratio"])
         lam = float32(r["regul_param"]) if has_tv or has_tgv else None
+        # the stripe variable s (one offset per detector pixel, added to every angle; mu |s|_1): off unless the key is given
+        stripes = d.get("stripe_lambda") is not None
+        n_angles = int(b.shape[1])
         if has_tgv:   # the radii of the two balls: r1 = lambda alpha1, r0 = lambda alpha0
             r1, r0 = lam * float32(r["TGV_alpha1"]), lam * float32(r["TGV_alpha2"])
         if diag:
@@ -444,10 +449,14 @@ class RecToolsIRCuPy:
             # the TGV block: a P row holds a forward difference and -I (absolute sum 3), a Q row sums to 2; a v_d column
             # meets -I once, Q_dd's difference and, for each e != d, the two rows Q_de stands for: 1 + 2 + 2 (nd - 1)
             sigma_p, sigma_q, tau_v = numer_sigma / float32(3), sigma, numer_tau / float32(2 * nd + 1)
+            # with the stripe variable a row of [A S] gains one entry 1 and a column of S sums to the number of angles
+            tau_s = numer_tau / float32(n_angles)
         else:
             # the step sizes, float32 throughout: sigma tau L_K = 0.95^2 with L_K = |A|^2 + |grad|^2 <= L_A + 4 nd; the TGV
             # block [[grad, -I], [0, E]] has the squared norm <= 12 (2D), 16 (3D)
             L_K = float32(a["lipschitz_const"])
+            if stripes:   # |[A S]|^2 <= |A|^2 + |S|^2 and |S|^2 is the number of angles, exactly
+                L_K = L_K + float32(n_angles)
             if has_tv:
                 L_K = L_K + float32(4 * nd)
             if has_tgv:
@@ -455,6 +464,9 @@ class RecToolsIRCuPy:
             s = float32(0.95) / np.sqrt(L_K)
             sigma, tau = s * rho, s / rho
             sigma_p, sigma_q, tau_v = sigma, sigma, tau
+            tau_s = tau
+        if stripes:
+            theta = tau_s * float32(d["stripe_lambda"])
 
         # x-bar, g = A^T y and the duals (with TGV: v and v-bar too; with the preconditioner: the steps per voxel) live in a
         # placed block of their own; the projector calls see ordinary tensors
@@ -475,6 +487,11 @@ class RecToolsIRCuPy:
         ops.fill(y, 0.0)
         proj = torch.empty_like(b)
         sigma_rows = torch.empty_like(b) if diag else None   # the steps per sample
+        if stripes:   # s, s-bar [nz, nu] and the segments' partial sums of y along the angles
+            s, sbar = (torch.empty((b.shape[0], b.shape[2]), dtype=torch.float32, device=b.device) for _ in range(2))
+            part = torch.empty((ops.pdhg_stripe_segments(n_angles), b.shape[0], b.shape[2]), dtype=torch.float32, device=b.device)
+            for field in (s, sbar, part):
+                ops.fill(field, 0.0)
 
         planar_volume = getattr(A, "set_volume_layout", None)
         A.invalidate()
@@ -489,13 +506,19 @@ class RecToolsIRCuPy:
             if diag:   # the row and column sums of A; g and proj hold the ones, the loop overwrites both before it reads them
                 ops.fill(g, 1.0)
                 A.forward(g, None, out=sigma_rows)
-                ops.pdhg_diag_steps(sigma_rows, sigma_rows, numer_sigma)
+                if stripes:
+                    ops.pdhg_diag_steps(sigma_rows, sigma_rows, numer_sigma, float32(1))
+                else:
+                    ops.pdhg_diag_steps(sigma_rows, sigma_rows, numer_sigma)
                 ops.fill(proj, 1.0)
                 A.backward(proj, None, out=tau)
                 ops.pdhg_diag_steps(tau, tau, numer_tau, col_add)
             for k in range(a["iterations"]):
                 A.forward(xbar, None, out=proj)
-                if diag:
+                if stripes:   # step 2 on A x-bar + S s-bar, the sums of y along the angles in the same pass; then step 6
+                    ops.pdhg_sino_dual_stripe(y, proj, b, sbar, part, fid, sigma_rows if diag else sigma)
+                    ops.pdhg_stripe_update(s, sbar, part, n_angles, tau_s, theta)
+                elif diag:
                     ops.pdhg_sino_dual_diag(y, proj, b, sigma_rows, fid)
                 else:
                     ops.pdhg_sino_dual(y, proj, b, fid, sigma)
@@ -518,6 +541,9 @@ class RecToolsIRCuPy:
             if planar_volume is not None:
                 planar_volume("planar")
             A.invalidate()
+        if stripes:   # without the detector-padding columns, in the caller's array library
+            pad = A.detectors_x_pad
+            self.last_run["stripes"] = ops.like(ops.contiguous(s[:, pad:s.shape[1] - pad]), getattr(self, "_given", None))
         return self._finalise(x, a)
 
     # ------------------------------------------------------------------ SPDHG

@@ -447,6 +447,54 @@ def pdhg_primal_diag(x, xbar, g, q, tau, nonneg=False):
                                               int(bool(nonneg)), stream_ptr(x)))
 
 
+# ---- PDHG with the stripe variable (_data_["stripe_lambda"], docs/kernels/pdhg.md; include/tomo_mi355x_stripe.h)
+def pdhg_stripe_segments(na: int) -> int:
+    """n_seg = ceil(na / 64): the segments the angles are cut into for the sum of y along them"""
+    return (int(na) + L.PDHG_STRIPE_SEG - 1) // L.PDHG_STRIPE_SEG
+
+
+def _pdhg_stripe_like(first, named):
+    """every (name, array, shape) is float32, contiguous, of that shape and on the device of `first`"""
+    for name, t, shape in named:
+        _chk_f32(t, name)
+        if tuple(t.shape) != tuple(shape) or t.device != first.device:
+            raise ValueError(f"{name} must have the shape {tuple(shape)} and the device of the first array")
+
+
+def pdhg_sino_dual_stripe(y, r, b, sbar, part, fidelity: str, sigma):
+    """Step 2 of a PDHG iteration with the stripe variable (tomo_pdhg_sino_dual_stripe): `pdhg_sino_dual` on e = r + s-bar,
+    s-bar[z, u] added to every angle, `y` [nz, angles, nu] in place; in the same pass `part`[k, z, u] <- the sum of the new
+    y[z, a, u] over the 64 angles of segment k.  `sigma`: a float32 scalar, or an array like `y` (a step per sample)."""
+    if fidelity not in L.PDHG_FID:
+        raise ValueError(f"unknown PDHG data term {fidelity!r}: LS, L1 and KL are supported")
+    per_sample = isinstance(sigma, torch.Tensor)
+    _chk_f32(y, "y")
+    if y.dim() != 3:
+        raise ValueError("the stripe launches take the sinogram dual as a [nz, angles, nu] array")
+    nz, na, nu = y.shape
+    _pdhg_stripe_like(y, [("r", r, y.shape), ("b", b, y.shape)] + ([("sigma", sigma, y.shape)] if per_sample else [])
+                      + [("sbar", sbar, (nz, nu)), ("part", part, (pdhg_stripe_segments(na), nz, nu))])
+    with _on(y):
+        L.check(L.lib().tomo_pdhg_sino_dual_stripe(ptr(y), ptr(r), ptr(b), ptr(sigma if per_sample else None), ptr(sbar), ptr(part),
+                                                   nz, na, nu, L.PDHG_FID[fidelity], 0.0 if per_sample else float(sigma),
+                                                   stream_ptr(y)))
+    return y
+
+
+def pdhg_stripe_update(s, sbar, part, na, tau_s, theta):
+    """Step 6 of a PDHG iteration with the stripe variable (tomo_pdhg_stripe_update): c = the sum of `part` over its
+    segments, s' = the soft threshold of s - tau_s c at theta; s-bar <- 2 s' - s, s <- s', in place.  `s`, `sbar`: [nz, nu];
+    `part`: [ceil(na / 64), nz, nu], `na` the number of angles it was summed over."""
+    _chk_f32(s, "s")
+    if s.dim() != 2:
+        raise ValueError("the stripe variable is a [nz, nu] array")
+    nz, nu = s.shape
+    _pdhg_stripe_like(s, [("sbar", sbar, (nz, nu)), ("part", part, (pdhg_stripe_segments(na), nz, nu))])
+    with _on(s):
+        L.check(L.lib().tomo_pdhg_stripe_update(ptr(s), ptr(sbar), ptr(part), nz, int(na), nu, float(tau_s), float(theta),
+                                                stream_ptr(s)))
+
+
 # ---- PDHG with the second-order TGV term in its dual ("PD_TGV", docs/kernels/pdhg.md)
 def pdhg_tgv_work_arrays(shape, device, tau: bool = False):
     """The work arrays of one PDHG call with the TGV block on a volume of `shape` ([nz, ny, nx]), uninitialised, from the

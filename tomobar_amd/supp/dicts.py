@@ -191,6 +191,14 @@ def dicts_check(self, _data_: dict, _algorithm_: Optional[dict] = None, _regular
                 raise ValueError(f"_data_['{key}'] must be a positive threshold")
     if _data_["huber_threshold"] is not None and _data_["studentst_threshold"] is not None:
         raise ValueError("give either 'huber_threshold' or 'studentst_threshold', not both")
+    # the stripe variable of PDHG (docs/kernels/pdhg.md): mu of mu |s|_1, one offset s per detector pixel added to every
+    # angle.  Read, never filled: absent means off, and the dictionaries of every other call stay what they were
+    stripe = _data_.get("stripe_lambda")
+    if stripe is not None:
+        if method_run != "PDHG":
+            raise ValueError("_data_['stripe_lambda'] is available in PDHG only")
+        if not float(stripe) > 0.0:
+            raise ValueError("_data_['stripe_lambda'] (the weight mu of the stripe variable's L1 norm) must be positive")
 
     if self.OS_number > 1 and method_run in _NO_OS_METHODS:
         raise NameError(

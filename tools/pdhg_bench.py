@@ -4,6 +4,13 @@ back projection, the TV dual and the primal) on synthetic data.
 usage: python tools/pdhg_bench.py [--shapes 512:360,1024:900] [--fidelity LS] [--regulariser tv|tgv] [--preconditioner diagonal]
                                   [--power-method] [--reps 5] [--short 4] [--long 14] [--out FILE]
        python tools/pdhg_bench.py --kernel-db RESULTS.db [--regulariser tv|tgv] [--preconditioner diagonal] [--out FILE]
+       python tools/pdhg_bench.py --stripe [--stripe-shapes 1024:900:1024,1:1800:2560] [--fidelity LS] [--rounds 3] [--reps 20]
+
+--stripe times the fused launch of the stripe variable (tomo_pdhg_sino_dual_stripe: step 2 on r + s-bar and the sums of y along
+the angles, 16.06 B per sample) against the plain sinogram dual (tomo_pdhg_sino_dual, 16 B) on the same arrays of nz:angles:nu
+samples, alternately: `rounds` rounds of `reps` plain launches, then `reps` fused ones, each timed with device events; per round
+the medians and their ratio, and the plain launch's own spread between the rounds, which is what a ratio can be read against.
+Its lines go to profiles/pdhg_stripe_bench.jsonl.
 
 --regulariser tgv times PD_TGV, the second-order TGV term in the dual (two marches of 88 + 88 B per voxel in 3D, 92 B for the
 primal with a step per voxel, in place of the TV pair); its lines go to profiles/pdhg_tgv_bench.jsonl.
@@ -91,6 +98,49 @@ def bench(n, na, args):
             "finite": bool(torch.isfinite(out[0]).all()), "placement": ops.placement_last()}
 
 
+def stripe_bench(nz, na, nu, args):
+    """the fused launch against the plain sinogram dual on the same y, r, b: alternately, `rounds` times"""
+    import torch
+    from tomobar_amd import ops
+    gen = torch.Generator(device="cuda").manual_seed(4)
+    y, r, b = (torch.rand((nz, na, nu), device="cuda", generator=gen) for _ in range(3))
+    sbar = torch.rand((nz, nu), device="cuda", generator=gen)
+    s = torch.zeros((nz, nu), device="cuda")
+    part = torch.empty((ops.pdhg_stripe_segments(na), nz, nu), device="cuda")
+    sigma = 0.25
+    launches = {"plain": lambda: ops.pdhg_sino_dual(y.view(-1), r.view(-1), b.view(-1), args.fidelity, sigma),
+                "fused": lambda: ops.pdhg_sino_dual_stripe(y, r, b, sbar, part, args.fidelity, sigma),
+                "update": lambda: ops.pdhg_stripe_update(s, sbar, part, na, 0.01, 0.5)}
+
+    def median_ms(fn):
+        times = []
+        for _ in range(args.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1))
+        return statistics.median(times)
+
+    for fn in launches.values():   # warm-up: code objects
+        fn()
+    torch.cuda.synchronize()
+    rounds = [{name: round(median_ms(fn), 4) for name, fn in launches.items()} for _ in range(args.rounds)]
+    plain = [q["plain"] for q in rounds]
+    fused = [q["fused"] for q in rounds]
+    samples = nz * na * nu
+    byte_ratio = (16.0 * samples + 4.0 * nz * nu * (1 + part.shape[0])) / (16.0 * samples)
+    best = min(fused)
+    return {"op": "pdhg_stripe", "fidelity": args.fidelity, "nz": nz, "angles": na, "nu": nu, "rounds": rounds, "reps": args.reps,
+            "device": torch.cuda.get_device_name(0), "ms_fused_min_max": [min(fused), max(fused)],
+            "ms_plain_min_max": [min(plain), max(plain)], "ratio_per_round": [round(f / p, 4) for f, p in zip(fused, plain)],
+            "plain_spread_between_rounds": round(max(plain) / min(plain) - 1.0, 4), "byte_ratio": round(byte_ratio, 4),
+            "fused_algorithmic_GBps": round(16.0 * samples * byte_ratio / (best * 1e-3) / 1e9, 1),
+            "fused_ratio_to_copy_rate_6200_GBps": round(16.0 * samples * byte_ratio / (best * 1e-3) / 1e9 / COPY_RATE_GBPS, 3),
+            "finite": bool(torch.isfinite(part).all())}
+
+
 def split(db_path, n, na, preconditioner=None, regulariser="tv"):
     """the launch groups of a profiled run: calls, mean ms per launch, ms per iteration, share of the kernel time; rates of
     the three new launches"""
@@ -129,15 +179,30 @@ def main():
     ap.add_argument("--short", type=int, default=4)
     ap.add_argument("--long", type=int, default=14)
     ap.add_argument("--kernel-db", default=None, help="summarise the kernels table of a rocprofv3 --kernel-trace --stats run instead")
-    ap.add_argument("--out", default=None, help="default: profiles/pdhg_bench.jsonl, profiles/pdhg_tgv_bench.jsonl with --regulariser tgv")
+    ap.add_argument("--stripe", action="store_true", help="time the stripe variable's fused launch against the plain sinogram dual")
+    ap.add_argument("--stripe-shapes", default="1024:900:1024,1:1800:2560", help="nz:angles:nu of --stripe")
+    ap.add_argument("--rounds", type=int, default=3, help="rounds of --stripe")
+    ap.add_argument("--out", default=None, help="default: profiles/pdhg_bench.jsonl, profiles/pdhg_tgv_bench.jsonl with --regulariser tgv, "
+                                                "profiles/pdhg_stripe_bench.jsonl with --stripe")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "pdhg_tgv_bench.jsonl" if args.regulariser == "tgv" else "pdhg_bench.jsonl")
+        name = "pdhg_stripe_bench.jsonl" if args.stripe else "pdhg_tgv_bench.jsonl" if args.regulariser == "tgv" else "pdhg_bench.jsonl"
+        args.out = os.path.join(ROOT, "profiles", name)
     if not 0 < args.short < args.long or args.reps < 1:
         ap.error("need 0 < --short < --long and --reps >= 1")
     shapes = [tuple(int(v) for v in item.split(":")) for item in args.shapes.split(",")]
     lines = []
-    if args.kernel_db:
+    if args.stripe:
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("pdhg_bench needs a GPU (there is no CPU path)")
+        if args.rounds < 2:
+            ap.error("--stripe needs --rounds >= 2: the plain launch's spread between rounds is part of the result")
+        for item in args.stripe_shapes.split(","):
+            lines.append(stripe_bench(*(int(v) for v in item.split(":")), args))
+            print(json.dumps(lines[-1]), flush=True)
+            torch.cuda.empty_cache()
+    elif args.kernel_db:
         if len(shapes) != 1:
             ap.error("--kernel-db needs --shapes with the one shape the profiled run used")
         lines.append(split(args.kernel_db, *shapes[0], args.preconditioner, args.regulariser))

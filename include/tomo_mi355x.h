@@ -35,7 +35,7 @@ extern "C" {
  * tomo_nltv, and the five entry points of the private volume layout (TOMO_VOLUME_ZQUAD below), and the four tomo_pdhg_* entry
  * points (tests/test_matched_bp_oracle.py pins the number 10 as well), and the five tomo_spdhg_* entry points, and the four
  * entry points of PDHG's diagonal preconditioner (tomo_pdhg_diag_*, tomo_pdhg_*_diag), and the five tomo_pdhg_tgv_* entry
- * points. */
+ * points, and tomo_pdhg_sino_dual_stripe and tomo_pdhg_stripe_update. */
 #define TOMO_ABI_VERSION 10
 
 enum {
@@ -469,6 +469,29 @@ int tomo_pdhg_tgv_primal(int device, float *x_dev, float *xbar_dev, const float 
 int tomo_pdhg_tgv_primal_diag(int device, float *x_dev, float *xbar_dev, const float *g_dev, const float *tau_dev,
                               float *const *v_dev, float *const *vbar_dev, const float *const *p_dev, const float *const *q_dev,
                               int dx, int dy, int dz, int nd, float tau_v, int nonneg, void *stream);
+/* PDHG with a stripe variable for ring artefacts (RecToolsIRCuPy.PDHG with _data_["stripe_lambda"]; docs/kernels/pdhg.md,
+ * "The stripe variable"): min_{x, s} F(A x + S s; b) + lambda R(x) + mu |s|_1, s[z][u] one offset per detector pixel,
+ * (S s)[z][a][u] = s[z][u].  The sinogram is [nz][na][nu], u fastest; the angles are cut into n_seg = ceil(na /
+ * TOMO_PDHG_STRIPE_SEG) segments of TOMO_PDHG_STRIPE_SEG rows, so that the sum of y over the angles is deterministic and
+ * still parallel along them.  No reference counterpart: tests/_pdhg_stripe_oracle.py restates both launches in numpy and
+ * they equal its float32 form bit for bit (one rounding per operation, no FMA contraction).
+ *   tomo_pdhg_sino_dual_stripe: step 2 of a PDHG iteration with the stripe variable.  Per sample e = r + sbar[z][u], then
+ *     the prox of tomo_pdhg_sino_dual with e in place of r (TOMO_PDHG_LS, TOMO_PDHG_L1, TOMO_PDHG_KL), y in place; and
+ *     part[k][z][u] = the sum of the new y[z][a][u] over the rows a of segment k, ascending from +0.  sigma_dev NULL: the
+ *     scalar step `sigma`; else one step per sample (an array like y; `sigma` is not read).  About 16 B per sample (20 with
+ *     sigma_dev).  16-byte accesses where nu % 4 == 0 and y, r, b (and sigma_dev) are 16-byte aligned, scalar ones otherwise.
+ *     TOMO_E_INVALID: an unknown term, nz, na or nu below 1, a non-positive sigma with sigma_dev NULL, NULL, y or part
+ *     aliasing another array of the call.
+ *   tomo_pdhg_stripe_update: step 6.  Per (z, u): c = the sum of part[k][z][u] over k ascending from +0; w = s - tau_s c;
+ *     s' = w > theta ? w - theta : (w < -theta ? w + theta : +0); sbar <- (s' + s') - s; s <- s'.  `na` is the number of
+ *     angles the partial sums were taken over (it fixes n_seg).  TOMO_E_INVALID: nz, na or nu below 1, a non-positive tau_s, a
+ *     negative theta, NULL, aliasing arrays. */
+#define TOMO_PDHG_STRIPE_SEG 64
+int tomo_pdhg_sino_dual_stripe(float *y_dev, const float *r_dev, const float *b_dev, const float *sigma_dev,
+                               const float *sbar_dev, float *part_dev, int nz, int na, int nu, int fidelity, float sigma,
+                               void *stream);
+int tomo_pdhg_stripe_update(float *s_dev, float *sbar_dev, const float *part_dev, int nz, int na, int nu, float tau_s,
+                            float theta, void *stream);
 /* The launches of SPDHG (stochastic PDHG over ordered subsets: one block update touches one subset of angles or the TV
  * block) beside the per-subset forward projector and the subset form of the matched back projector: a subset update of
  * RecToolsIRCuPy.SPDHG runs tomo_fp3d on x, tomo_spdhg_sino_dual, tomo_bp3d_matched, tomo_spdhg_primal; a TV update runs

@@ -48,6 +48,7 @@ CASES = {
     "pdhg_marches": (ASYNC, ["tomo_pdhg_tv_dual", "tomo_pdhg_primal"]),
     "pdhg_diag": (ASYNC, ["tomo_pdhg_diag_steps", "tomo_pdhg_sino_dual_diag", "tomo_pdhg_primal_diag"]),
     "pdhg_tgv": (ASYNC, ["tomo_pdhg_tgv_dual", "tomo_pdhg_tgv_primal", "tomo_pdhg_tgv_primal_diag"]),
+    "pdhg_stripe": (ASYNC, ["tomo_pdhg_sino_dual_stripe", "tomo_pdhg_stripe_update"]),
     "spdhg_tv": (ASYNC, ["tomo_spdhg_tv_dual", "tomo_spdhg_tv_primal"]),
     "reserve_scratch": (ASYNC, ["tomo_reserve_scratch"]),
     "placed_scratch": (ASYNC, ["tomo_placed_scratch"]),

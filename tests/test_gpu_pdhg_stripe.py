@@ -1,9 +1,8 @@
-"""MI355X tests of PDHG's stripe variable (``_data_["stripe_lambda"]``; docs/kernels/pdhg.md): the two launches of
-include/tomo_mi355x_stripe.h and the driver against the float32 numpy restatement tests/_pdhg_stripe_oracle.py, bit for bit
-(there is no reference implementation: formula-level parity, unpinned), on the inputs of tests/_pdhg_stripe_cases.py and the
-geometries of tests/_pdhg_driver_geometries.py; both entry points on a side stream behind a delay (tests/_on_stream.py; a
-`@stream_case` names the prototype, tests/test_pdhg_stripe_surface.py holds the header to these names); one case past 2^31
-samples."""
+"""MI355X tests of PDHG's stripe variable (``_data_["stripe_lambda"]``; docs/kernels/pdhg.md): the two stripe launches of
+include/tomo_mi355x.h and the driver against the float32 numpy restatement tests/_pdhg_stripe_oracle.py, bit for bit (there
+is no reference implementation: formula-level parity, unpinned), on the inputs of tests/_pdhg_stripe_cases.py and the
+geometries of tests/_pdhg_driver_geometries.py; one case past 2^31 samples.  Both entry points run on a side stream behind a
+delay in tests/test_gpu_streams.py (case "pdhg_stripe"): this file creates no stream."""
 import os
 import sys
 
@@ -19,18 +18,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _cupy_standin  # noqa: E402
 from _guarded import guarded  # noqa: E402
 import _large_index as LI  # noqa: E402
-import _on_stream as OS  # noqa: E402
 import _pdhg_driver_geometries as GEO  # noqa: E402
 import _pdhg_oracle as P  # noqa: E402
 import _pdhg_stripe_cases as SC  # noqa: E402
 import _pdhg_stripe_oracle as S  # noqa: E402
 
 F32 = np.float32
-
-
-def stream_case(name):
-    """marks the test that runs the entry point `name` of include/tomo_mi355x_stripe.h on a side stream"""
-    return lambda fn: fn
 
 
 def host(t):
@@ -136,92 +129,6 @@ def test_launches_refuse_what_they_cannot_run():
         update(na=64)           # one segment where the array holds two
     torch.cuda.synchronize()
     assert all(torch.equal(t, k) for t, k in zip((y, s, sbar, part), keep)), "a refused call launched"
-
-
-# ------------------------------------------------------------------------------------------------ streams
-@pytest.fixture(scope="module")
-def side():
-    """The side stream of this file's two cases -- and the streams tests/_on_stream.py makes for its calibration and for
-    staging -- are HIP streams this fixture creates and destroys itself, and the state of tests/_on_stream.py is put back.
-    A process opens a handful of hardware queues and the runtime places every further stream that is used on one of them for
-    as long as the stream lives; a stream of torch's pool is never destroyed.  Taken from the pool, the streams of this file
-    would move the streams of every later file (tests/test_gpu_streams.py) to other queues, where one of them may share the
-    queue of the null stream: its stand-in, which relies on the null stream running beside a delayed side stream, then fails.
-    Destroyed streams give their place back, and the pool hands the later files the streams it always handed them."""
-    import ctypes as C
-    from tomobar_amd import _lib
-    hip = _lib.lib()      # the HIP runtime the library is linked against: dlsym finds its symbols through the handle
-    create, destroy = hip.hipStreamCreateWithFlags, hip.hipStreamDestroy
-    create.restype = destroy.restype = C.c_int
-    create.argtypes, destroy.argtypes = [C.POINTER(C.c_void_p), C.c_uint], [C.c_void_p]
-    handles = []
-
-    def own_stream():
-        h = C.c_void_p()
-        assert create(C.byref(h), 1) == 0 and h.value      # 1 = hipStreamNonBlocking, as the streams of torch's pool
-        handles.append(h)
-        return torch.cuda.ExternalStream(h.value)
-
-    keep = (OS.side_stream, OS._staging, OS._cycles_per_ms, len(OS.ENQUEUE_LOG))
-    OS.side_stream, OS._staging = own_stream, None
-    try:
-        OS.calibrate()
-        yield OS.side_stream()
-    finally:
-        torch.cuda.synchronize()
-        OS.side_stream, OS._staging, OS._cycles_per_ms = keep[:3]
-        del OS.ENQUEUE_LOG[keep[3]:]
-        torch.cuda.empty_cache()      # the blocks the allocator cached under these streams go before the streams do
-        for h in handles:
-            assert destroy(h) == 0
-
-
-def _run_late(body, side, label):
-    """`body(provider)` warm on the side stream, then behind the delay on arrays that arrive late; the entry points are
-    asynchronous, so the first read-back after the call asserts that the delay is still pending"""
-    with torch.cuda.stream(side):
-        W = OS.Late(side, delayed=False, label=label)
-        body(W)
-        side.synchronize()
-        W.close()
-        A = OS.Late(side, delayed=True, asynchronous=True, label=label)
-        body(A)
-    assert A.asserted > 0, "the case never looked at the stream after a call"
-    side.synchronize()
-
-
-@stream_case("tomo_pdhg_sino_dual_stripe")
-@pytest.mark.parametrize("per_sample", [False, True], ids=["scalar", "per sample"])
-def test_fused_dual_on_a_side_stream(side, per_sample):
-    from tomobar_amd import ops
-    y0, r, b, sig, sbar = SC.kernel_inputs(3, 130, 260)
-    want_y, want_part = S.sino_dual_stripe(y0, r, b, sbar, "KL", sig if per_sample else SC.KERNEL_SIGMA)
-
-    def body(A):
-        y, rd, bd, sb, part = A.rw(y0), A.ro(r), A.ro(b), A.ro(sbar), A.out(want_part.shape)
-        sg = A.ro(sig) if per_sample else None
-        ops.pdhg_sino_dual_stripe(y.view, rd.view, bd.view, sb.view, part.view, "KL", sg.view if per_sample else SC.KERNEL_SIGMA)
-        _same_bits(y.host(), want_y, "y")          # (the first read-back asserts `still_busy`)
-        _same_bits(part.host(), want_part, "part")
-        A.check("fused dual")
-
-    _run_late(body, side, "pdhg_sino_dual_stripe")
-
-
-@stream_case("tomo_pdhg_stripe_update")
-def test_stripe_update_on_a_side_stream(side):
-    from tomobar_amd import ops
-    s0, part0 = SC.update_inputs(3, 130, 260)
-    want_s, want_sbar = S.stripe_update(s0, part0, SC.KERNEL_TAU_S, SC.KERNEL_THETA)
-
-    def body(A):
-        s, part, sbar = A.rw(s0), A.ro(part0), A.out(s0.shape)
-        ops.pdhg_stripe_update(s.view, sbar.view, part.view, 130, SC.KERNEL_TAU_S, SC.KERNEL_THETA)
-        _same_bits(s.host(), want_s, "s")
-        _same_bits(sbar.host(), want_sbar, "s-bar")
-        A.check("stripe update")
-
-    _run_late(body, side, "pdhg_stripe_update")
 
 
 # ------------------------------------------------------------------------------------------------ past 2^31 samples

@@ -557,6 +557,37 @@ def test_pdhg_tgv(side):
     run_late(body, side, "pdhg_tgv")
 
 
+@case("pdhg_stripe")
+def test_pdhg_stripe(side):
+    """3 planes, 130 angles (three segments, the last one of 2 rows), 260 columns (one full 256-column block and a tail)"""
+    import _pdhg_stripe_cases as SC
+    import _pdhg_stripe_oracle as SO
+    from tomobar_amd import ops
+    y0, r, b, sig, sbar = SC.kernel_inputs(3, 130, 260)
+    s0, part0 = SC.update_inputs(3, 130, 260)
+    want_s, want_sbar = SO.stripe_update(s0, part0, SC.KERNEL_TAU_S, SC.KERNEL_THETA)
+
+    for per_sample in (False, True):
+        want_y, want_part = SO.sino_dual_stripe(y0, r, b, sbar, "KL", sig if per_sample else SC.KERNEL_SIGMA)
+
+        def dual(A):
+            y, rd, bd, sb, part = A.rw(y0), A.ro(r), A.ro(b), A.ro(sbar), A.out(want_part.shape)
+            sg = A.ro(sig) if per_sample else None
+            ops.pdhg_sino_dual_stripe(y.view, rd.view, bd.view, sb.view, part.view, "KL", sg.view if per_sample else SC.KERNEL_SIGMA)
+            same_bits(y.host(), want_y, "y")          # (the first read-back asserts `still_busy`)
+            same_bits(part.host(), want_part, "part")
+            A.check("fused dual")
+        run_late(dual, side, "pdhg_stripe", "pdhg_sino_dual_stripe, " + ("per sample" if per_sample else "scalar"))
+
+    def update(A):
+        s, part, sb = A.rw(s0), A.ro(part0), A.out(s0.shape)
+        ops.pdhg_stripe_update(s.view, sb.view, part.view, 130, SC.KERNEL_TAU_S, SC.KERNEL_THETA)
+        same_bits(s.host(), want_s, "s")
+        same_bits(sb.host(), want_sbar, "s-bar")
+        A.check("stripe update")
+    run_late(update, side, "pdhg_stripe", "pdhg_stripe_update")
+
+
 @case("spdhg_tv")
 def test_spdhg_tv(side):
     import _pdhg_cases as K

@@ -1,9 +1,8 @@
-"""No GPU: the surface of PDHG's stripe variable (``_data_["stripe_lambda"]``; docs/kernels/pdhg.md).  The two entry points live
-in a header of their own, include/tomo_mi355x_stripe.h, bound through ``_lib.EXT_SIGNATURES``; this file holds that header to the
-two rules tests/test_host_logic.py and tests/test_stream_coverage.py hold the main header to -- every declared name is bound
-and exported, every prototype with a stream is run on a side stream by a case of tests/test_gpu_pdhg_stripe.py -- and checks
-the refusals of the C-ABI, the key in all eight drivers, and that without the key ``RecToolsIRCuPy.PDHG`` makes the calls it
-always made."""
+"""No GPU: the surface of PDHG's stripe variable (``_data_["stripe_lambda"]``; docs/kernels/pdhg.md).  The two entry points are
+declared in include/tomo_mi355x.h and bound through ``_lib.SIGNATURES`` like every other; this file checks what is their own --
+both declared, bound and exported by both libraries with the stated types, the segment length in step across header, binding
+and oracle --, the refusals of the C-ABI, the key in all eight drivers, and that without the key ``RecToolsIRCuPy.PDHG`` makes
+the calls it always made.  Their streams are held by tests/test_gpu_streams.py (case "pdhg_stripe")."""
 import ctypes as C
 import os
 import re
@@ -17,8 +16,11 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
 import _pdhg_stripe_oracle as S  # noqa: E402,F401  (the restatement imports without a GPU)
+from test_stream_coverage import header_prototypes  # noqa: E402  (the header's parser; read, not collected from here)
 
-HEADER = ("include", "tomo_mi355x_stripe.h")
+HEADER = ("include", "tomo_mi355x.h")
+NAMES = {"tomo_pdhg_sino_dual_stripe": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
+         "tomo_pdhg_stripe_update": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float, C.c_float, C.c_void_p])}
 DRIVERS = ("PDHG", "SPDHG", "FISTA", "ADMM", "OSEM", "SIRT", "CGLS", "Landweber")
 
 
@@ -28,60 +30,42 @@ def _read(*parts):
 
 
 # ------------------------------------------------------------------------------------------------ the header and the binding
-def _prototypes():
-    """{name: parameter list} of every function prototype of the new header, comments removed"""
-    text = re.sub(r"/\*.*?\*/", " ", _read(*HEADER), flags=re.S)
-    text = re.sub(r"//[^\n]*", " ", text)
-    return {m.group(1): " ".join(m.group(2).split()) for m in re.finditer(r"\b(tomo_\w+)\s*\(([^;{}()]*)\)\s*;", text)}
-
-
 def test_the_header_declares_what_the_binding_binds_and_both_libraries_export_it():
     from tomobar_amd import _lib
-    declared = set(re.findall(r"\b(tomo_[a-z0-9_]+)\s*\(", _read(*HEADER)))      # comments included, as tests/test_host_logic.py reads
-    assert declared == set(_lib.EXT_SIGNATURES) == set(_prototypes()) and len(declared) == 2
-    assert not set(_lib.EXT_SIGNATURES) & set(_lib.SIGNATURES)
+    main = _read(*HEADER)
+    declared = set(re.findall(r"\b(tomo_[a-z0-9_]+)\s*\(", main))      # comments included, as tests/test_host_logic.py reads
+    protos = header_prototypes()
+    assert set(NAMES) <= declared and set(NAMES) <= set(protos) and set(NAMES) <= set(_lib.SIGNATURES)
     for flavour in ("shipped", "dev"):
         with _lib.use_flavour(flavour) as handle:
-            for name, (res, args) in _lib.EXT_SIGNATURES.items():
+            for name, (res, args) in NAMES.items():
                 assert hasattr(handle, name), f"{name} declared in {'/'.join(HEADER)} but not exported ({flavour})"
                 fn = getattr(handle, name)
                 assert fn.restype is res and list(fn.argtypes) == list(args)
-    for name, params in _prototypes().items():      # one ctypes argument per parameter, pointers as void pointers
-        kinds = [C.c_void_p if "*" in p else {"int": C.c_int, "float": C.c_float}[p.split()[0]] for p in params.split(",")]
-        assert kinds == list(_lib.EXT_SIGNATURES[name][1]), name
-    main = _read("include", "tomo_mi355x.h")
-    assert not any(re.search(re.escape(name) + r"\s*\(", main) for name in declared), "the main header's tests read its comments too"
+                assert _lib.SIGNATURES[name][0] is res and list(_lib.SIGNATURES[name][1]) == list(args)
+    for name in NAMES:      # one ctypes argument per parameter, pointers as void pointers
+        kinds = [C.c_void_p if "*" in p else {"int": C.c_int, "float": C.c_float}[p.split()[0]] for p in protos[name].split(",")]
+        assert kinds == list(_lib.SIGNATURES[name][1]), name
     assert re.search(r"#define\s+TOMO_ABI_VERSION\s+10\b", main) and _lib.ABI_VERSION == 10
-    seg = int(re.search(r"#define\s+TOMO_PDHG_STRIPE_SEG\s+(\d+)", _read(*HEADER)).group(1))
+    seg = int(re.search(r"#define\s+TOMO_PDHG_STRIPE_SEG\s+(\d+)", main).group(1))
     assert seg == _lib.PDHG_STRIPE_SEG == S.SEG == 64
+    doc = " ".join(_read("INTEGRATION.md").split())
+    assert all(f"`{n}`" in doc for n in NAMES)
 
 
 def test_a_library_without_the_new_symbols_is_stale(monkeypatch):
     from tomobar_amd import _lib
-    monkeypatch.setitem(_lib.EXT_SIGNATURES, "tomo_pdhg_no_such_entry", (C.c_int, []))
+    monkeypatch.setitem(_lib.SIGNATURES, "tomo_pdhg_no_such_entry", (C.c_int, []))
     with pytest.raises(ImportError, match="stale.*tomo_pdhg_no_such_entry"):
         _lib._load("shipped")
-
-
-def test_every_prototype_with_a_stream_has_a_case_on_a_side_stream():
-    want = sorted(name for name, params in _prototypes().items() if re.search(r"\bvoid\s*\*\s*stream\b", params))
-    assert len(want) == 2, want
-    text = _read("tests", "test_gpu_pdhg_stripe.py")
-    cases = re.findall(r'^@stream_case\("(\w+)"\)\n(?:@[^\n]*\n)*def (\w+)\(side', text, flags=re.M)
-    assert sorted(n for n, _ in cases) == want, cases
-    for _, fn in cases:      # the case is one that delays the stream and looks at it after the call
-        body = text.split(f"def {fn}(", 1)[1].split("\n\n\n", 1)[0]
-        assert "_run_late(body, side" in body, fn
-    assert "asynchronous=True" in text and "A.asserted > 0" in text
-    doc = " ".join(_read("INTEGRATION.md").split())
-    assert all(f"`{n}`" in doc for n in want) and "tomo_mi355x_stripe.h" in doc
 
 
 def test_the_new_source_is_built_into_both_libraries():
     make = _read("tomobar_amd", "csrc", "Makefile")
     assert re.search(r"^SRCS\s*:=.*\bpdhg_stripe\.hip\b", make, flags=re.M)
     src = _read("tomobar_amd", "csrc", "pdhg_stripe.hip")
-    assert '#include "tomo_mi355x_stripe.h"' in src and "__global__" in src
+    assert '#include "tomo_common.h"' in src and "__global__" in src      # tomo_common.h includes the public header
+    assert '#include "tomo_mi355x.h"' in _read("tomobar_amd", "csrc", "tomo_common.h")
 
 
 # ------------------------------------------------------------------------------------------------ C-ABI

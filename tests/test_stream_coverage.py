@@ -38,7 +38,7 @@ def test_the_parser_sees_the_header():
 
 def test_every_prototype_with_a_stream_has_a_case():
     want = stream_prototypes()
-    assert len(want) == 83, len(want)      # a new entry point raises the figure together with its case
+    assert len(want) == 85, len(want)      # a new entry point raises the figure together with its case
     missing = [n for n in want if n not in ST.TABLE]
     assert not missing, ("no case of tests/test_gpu_streams.py runs", missing)
 

@@ -129,6 +129,8 @@ SIGNATURES = {
     "tomo_pdhg_tgv_dual": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp]),
     "tomo_pdhg_tgv_primal": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "tomo_pdhg_tgv_primal_diag": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
+    "tomo_pdhg_sino_dual_stripe": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "tomo_pdhg_stripe_update": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _vp]),
     "tomo_spdhg_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "tomo_spdhg_sino_dual": (_i, [_vp, _vp, _vp, _sz, _i, _f, _vp]),
     "tomo_spdhg_primal": (_i, [_vp, _vp, _vp, _sz, _f, _f, _i, _vp]),
@@ -181,13 +183,7 @@ SIGNATURES = {
     "tomo_profile_enable": (_i, [_i]),
     "tomo_profile_read": (_i, [C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(_d)]),
 }
-# the entry points of include/tomo_mi355x_stripe.h (PDHG's stripe variable): required in both flavours and checked at load
-# like SIGNATURES; a table of their own because that header is one (tests/test_pdhg_stripe_surface.py keeps the two in step)
-EXT_SIGNATURES = {
-    "tomo_pdhg_sino_dual_stripe": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "tomo_pdhg_stripe_update": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _vp]),
-}
-PDHG_STRIPE_SEG = 64   # TOMO_PDHG_STRIPE_SEG of include/tomo_mi355x_stripe.h
+PDHG_STRIPE_SEG = 64   # TOMO_PDHG_STRIPE_SEG of include/tomo_mi355x.h
 # entry points of libtomo_mi355x_dev.so alone (described, not declared, in include/tomo_mi355x.h): bound where the loaded
 # library exports them, absent from the shipped one
 DEV_SIGNATURES = {
@@ -213,11 +209,11 @@ def _load(flavour: str):
             f"{path} not found: the HIP extension is required (no CPU fallback). "
             f"Build it with `make -C tomobar_amd/csrc{' dev' if flavour == 'dev' else ''}` or `__graft_entry__.build()`.")
     handle = C.CDLL(path)
-    missing = [name for name in (*SIGNATURES, *EXT_SIGNATURES) if not hasattr(handle, name)]
+    missing = [name for name in SIGNATURES if not hasattr(handle, name)]
     if missing:
         raise ImportError(f"{path} is stale: it does not export {missing[:4]}{'...' if len(missing) > 4 else ''}; "
                           "rebuild it (make -C tomobar_amd/csrc all)")
-    for name, (res, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args

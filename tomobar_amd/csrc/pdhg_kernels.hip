@@ -29,26 +29,14 @@
 // traffic in 3D: the dual march 4 + 3 x 8 = 28 B (with e: 4 + 3 x 12 = 40 B), the primal march 3 x 4 + 8 + 8 = 28 B per voxel
 // (PdhgDiagUpdate: + 4 = 32 B).
 #include "zmarch_common.h"
+#include "pdhg_data_term.h"
 #include <initializer_list>
 
 namespace {
 
 // ------------------------------------------------------------------------------------------ the data term
-// the prox of the conjugate of the data term at y + sigma r (step 2 of both algorithms)
-template <int MODE>
-__device__ __forceinline__ float data_prox(float y, float r, float b, float sigma, float one_sigma, float c4)
-{
-    if (MODE == TOMO_PDHG_LS) return (y + sigma * (r - b)) / one_sigma;
-    if (MODE == TOMO_PDHG_L1) {
-        const float v = y + sigma * (r - b);
-        return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
-    }
-    const float v = y + sigma * r;
-    const float t = v - 1.0f;
-    const float bp = b > 0.0f ? b : 0.0f;
-    return 0.5f * ((1.0f + v) - sqrtf(t * t + c4 * bp));
-}
-
+// data_prox<MODE>, the prox of the conjugate of the data term at y + sigma r (step 2 of both algorithms): pdhg_data_term.h
+//
 // The per-element functors of stream3_kernel: op(a, b, c) updates a, and b where WRITES_B says so.  STEP_ARRAY: the functor
 // carries a fourth array, `step`, read beside the three, and is called as op(a, b, c, step[i]).
 template <int MODE>
@@ -495,8 +483,6 @@ static int require_volume(const char *op, int device, int dx, int dy, int &dz, i
     return TOMO_OK;
 }
 
-static bool positive_finite(float v) { return v > 0.0f && std::isfinite(v); }
-
 // no two of the pointers are equal (null pointers excepted)
 static bool distinct(std::initializer_list<const float *> ptrs)
 {
@@ -505,8 +491,6 @@ static bool distinct(std::initializer_list<const float *> ptrs)
             if (*i && *i == *k) return false;
     return true;
 }
-
-static bool known_fidelity(int f) { return f == TOMO_PDHG_LS || f == TOMO_PDHG_L1 || f == TOMO_PDHG_KL; }
 
 #include "pdhg_tgv.inl"
 

@@ -1,4 +1,4 @@
-// The two launches PDHG's stripe variable adds (docs/kernels/pdhg.md, "The stripe variable"; include/tomo_mi355x_stripe.h):
+// The two launches PDHG's stripe variable adds (docs/kernels/pdhg.md, "The stripe variable"; include/tomo_mi355x.h):
 //     min_{x, s} F(A x + S s; b) + lambda R(x) + mu |s|_1,     (S s)[z][a][u] = s[z][u],
 // one offset per detector pixel, constant along the angles -- the ring artefact of a defective pixel, kept out of the image.
 //   sino_dual_stripe_kernel   step 2 with e = r + s-bar in place of r, and in the same pass the sum of the new y along the
@@ -6,13 +6,13 @@
 //   stripe_update_kernel      step 6: c = the sum of the segments' partial sums, s' = soft(s - tau_s c, theta), s-bar = 2 s' - s
 // There is no reference implementation: tests/_pdhg_stripe_oracle.py restates both in numpy and the kernels reproduce its
 // float32 form bit for bit (one rounding per operation in the stated order, no FMA contraction: -ffp-contract=off and no
-// fmaf here; sqrtf and / are the compiler's correctly rounded ones).  The data terms are those of pdhg_kernels.hip, restated
-// here because that translation unit is not to change.
+// fmaf here; sqrtf and / are the compiler's correctly rounded ones).  The data terms are those of pdhg_kernels.hip: both
+// read them from pdhg_data_term.h.
 //
 // Traffic of the fused launch: y read and written, r and b read (with a step per sample: sigma too) = 16 (20) B per sample,
 // plus s-bar read and one partial sum written per (segment, z, u): (1 + 1) x 4 / 64 = 0.06 B per sample at full segments.
 #include "tomo_common.h"
-#include "tomo_mi355x_stripe.h"
+#include "pdhg_data_term.h"
 
 #include <algorithm>
 #include <cmath>
@@ -28,21 +28,6 @@ constexpr int SD_MAX_GRID_YZ = 65535;       // planes and segments beyond it are
 constexpr int UP_BLOCK = 256;
 
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-// the prox of the conjugate of the data term at y + sigma e (data_prox of pdhg_kernels.hip)
-template <int MODE>
-__device__ __forceinline__ float stripe_prox(float y, float e, float b, float sigma, float one_sigma, float c4)
-{
-    if (MODE == TOMO_PDHG_LS) return (y + sigma * (e - b)) / one_sigma;
-    if (MODE == TOMO_PDHG_L1) {
-        const float v = y + sigma * (e - b);
-        return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
-    }
-    const float v = y + sigma * e;
-    const float t = v - 1.0f;
-    const float bp = b > 0.0f ? b : 0.0f;
-    return 0.5f * ((1.0f + v) - sqrtf(t * t + c4 * bp));
-}
 
 // The SD_COLS values a lane owns of one row starting at `p`.  VEC: columns u[0] .. u[0] + 3, one 16-byte access; else the
 // columns u[j] that lie inside the row (ok[j]), one 4-byte access each.  NT: the array is read once and not again soon.
@@ -104,8 +89,8 @@ __global__ __launch_bounds__(SD_BLOCK) void sino_dual_stripe_kernel(StripeDualAr
 #pragma unroll
         for (int j = 0; j < SD_COLS; ++j) {
             const float e = R[j] + sb[j];
-            out[j] = DIAG ? stripe_prox<MODE>(Y[j], e, B[j], S[j], 1.0f + S[j], 4.0f * S[j])
-                          : stripe_prox<MODE>(Y[j], e, B[j], a.sigma, a.one_sigma, a.c4);
+            out[j] = DIAG ? data_prox<MODE>(Y[j], e, B[j], S[j], 1.0f + S[j], 4.0f * S[j])
+                          : data_prox<MODE>(Y[j], e, B[j], a.sigma, a.one_sigma, a.c4);
             acc[j] = acc[j] + out[j];
         }
         row_store<VEC>(a.y + off, out, u, ok);
@@ -212,8 +197,6 @@ __global__ __launch_bounds__(UP_BLOCK) void stripe_update_kernel(float *s, float
     }
 }
 
-static bool positive_finite(float v) { return v > 0.0f && std::isfinite(v); }
-
 static bool aligned16(std::initializer_list<const void *> ptrs)
 {
     uintptr_t bits = 0;
@@ -227,8 +210,7 @@ extern "C" int tomo_pdhg_sino_dual_stripe(float *y_dev, const float *r_dev, cons
                                           const float *sbar_dev, float *part_dev, int nz, int na, int nu, int fidelity,
                                           float sigma, void *stream)
 {
-    TOMO_REQUIRE(fidelity == TOMO_PDHG_LS || fidelity == TOMO_PDHG_L1 || fidelity == TOMO_PDHG_KL,
-                 "PDHG: the data term must be TOMO_PDHG_LS, TOMO_PDHG_L1 or TOMO_PDHG_KL");
+    TOMO_REQUIRE(known_fidelity(fidelity), "PDHG: the data term must be TOMO_PDHG_LS, TOMO_PDHG_L1 or TOMO_PDHG_KL");
     TOMO_REQUIRE(nz >= 1 && na >= 1 && nu >= 1, "PDHG: the stripe launches need nz, na and nu >= 1");
     TOMO_REQUIRE(sigma_dev || positive_finite(sigma), "PDHG: the step size sigma must be positive");
     TOMO_REQUIRE(y_dev && r_dev && b_dev && sbar_dev && part_dev, "NULL data pointer");

@@ -447,7 +447,7 @@ def pdhg_primal_diag(x, xbar, g, q, tau, nonneg=False):
                                               int(bool(nonneg)), stream_ptr(x)))
 
 
-# ---- PDHG with the stripe variable (_data_["stripe_lambda"], docs/kernels/pdhg.md; include/tomo_mi355x_stripe.h)
+# ---- PDHG with the stripe variable (_data_["stripe_lambda"], docs/kernels/pdhg.md; include/tomo_mi355x.h)
 def pdhg_stripe_segments(na: int) -> int:
     """n_seg = ceil(na / 64): the segments the angles are cut into for the sum of y along them"""
     return (int(na) + L.PDHG_STRIPE_SEG - 1) // L.PDHG_STRIPE_SEG

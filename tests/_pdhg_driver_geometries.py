@@ -1,7 +1,6 @@
-"""TEST INFRASTRUCTURE: the geometries the PDHG driver tests run on -- those tests/test_gpu_pdhg.py builds in its `geometries`
-fixture, restated here so that tests/test_gpu_pdhg_tgv.py does not import a test file: the 4 x 24 x 24 golden case (plain, with a
-padded detector, one plane of it) and a 5 x 48 x 48 case of two boxes with Gaussian noise.  Nothing here touches a GPU on
-import."""
+"""TEST INFRASTRUCTURE: the geometries the PDHG and SPDHG driver tests run on (tests/test_gpu_pdhg.py, _tgv, _stripe and
+tests/test_gpu_spdhg.py build their `geometries` fixture here): the 4 x 24 x 24 golden case (plain, with a padded detector,
+one plane of it) and a 5 x 48 x 48 case of two boxes with Gaussian noise.  Nothing here touches a GPU on import."""
 import os
 
 import numpy as np
@@ -29,8 +28,8 @@ class Geometry:
         return dict({"projection_data": torch.from_numpy(self.sino.copy()).cuda(), "data_axes_labels_order": list(LABELS)}, **kw)
 
 
-def build(oracle, golden_dir):
-    """name -> Geometry; `oracle`, `golden_dir`: the fixtures of tests/conftest.py"""
+def build(oracle, golden_dir, Geometry=Geometry):
+    """name -> Geometry (or the subclass given); `oracle`, `golden_dir`: the fixtures of tests/conftest.py"""
     gold = np.load(os.path.join(golden_dir, "outer_golden.npz"))
     a48 = np.linspace(0.0, np.pi, 23, endpoint=False)
     vol = np.zeros((5, 48, 48), np.float32)

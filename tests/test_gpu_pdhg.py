@@ -15,23 +15,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import _cupy_standin  # noqa: E402
+from _gpu_compare import host, same_bits  # noqa: E402
 from _guarded import guarded  # noqa: E402
-import _matched_bp_oracle as M  # noqa: E402
 import _pdhg_cases as K  # noqa: E402
+import _pdhg_driver_geometries as GEO  # noqa: E402
 import _pdhg_oracle as P  # noqa: E402
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype == np.float32 and got.shape == want.shape, what
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        raise AssertionError((what, f"{len(bad)} of {got.size} values differ, first at {tuple(bad[0])}",
-                              float(np.abs(got.astype(np.float64) - want).max())))
 
 
 # ------------------------------------------------------------------------------------------------ step 2
@@ -60,11 +48,11 @@ def test_sino_dual_equals_the_oracle(shape, fidelity, sigma):
     yg, rg, bg = guarded(y), guarded(r), guarded(b)
     yd, rd, bd = yg.view, rg.view, bg.view
     assert ops.pdhg_sino_dual(yd, rd, bd, fidelity, sigma) is yd
-    _same_bits(host(yd), want, (shape, fidelity, float(sigma)))
+    same_bits(host(yd), want, (shape, fidelity, float(sigma)))
     assert yg.intact() and rg.intact() and bg.intact() and rg.unchanged() and bg.unchanged()
     # two applications: the dual is really updated in place
     ops.pdhg_sino_dual(yd, rd, bd, fidelity, sigma)
-    _same_bits(host(yd), P.sino_dual(want, r, b, fidelity, sigma), (shape, fidelity, "second application"))
+    same_bits(host(yd), P.sino_dual(want, r, b, fidelity, sigma), (shape, fidelity, "second application"))
 
 
 @pytest.mark.parametrize("fidelity", P.FIDELITIES)
@@ -77,7 +65,7 @@ def test_sino_dual_on_arrays_that_are_not_16_byte_aligned(fidelity):
     yd, rd, bd = (t[1:] for t in full)
     assert all(t.data_ptr() % 16 == 4 and t.is_contiguous() for t in (yd, rd, bd))
     ops.pdhg_sino_dual(yd, rd, bd, fidelity, sigma)
-    _same_bits(host(yd), P.sino_dual(y[1:], r[1:], b[1:], fidelity, sigma), fidelity)
+    same_bits(host(yd), P.sino_dual(y[1:], r[1:], b[1:], fidelity, sigma), fidelity)
     assert host(full[0])[0] == y[0]
 
 
@@ -118,10 +106,10 @@ def test_tv_dual_and_primal_equal_the_oracle(shape):
                     if n in K.MARCH_COUNTS:
                         what = (shape, kind, methodTV, nonneg, n)
                         wx, wb, wq = want[n]
-                        _same_bits(host(x), wx, what + ("x",))
-                        _same_bits(host(xbar), wb, what + ("x-bar",))
+                        same_bits(host(x), wx, what + ("x",))
+                        same_bits(host(xbar), wb, what + ("x-bar",))
                         for d in range(nd):
-                            _same_bits(host(q[d]), wq[d], what + (f"q{d + 1}",))
+                            same_bits(host(q[d]), wq[d], what + (f"q{d + 1}",))
                 assert all(b.intact() for b in [xg, bg, gg] + qs), (shape, kind, "a guard was written")
                 assert gg.unchanged(), "g was written"
     # without the TV block: div q = 0
@@ -132,8 +120,8 @@ def test_tv_dual_and_primal_equal_the_oracle(shape):
         x, xbar = xg.view, bg.view
         for _ in range(3):
             ops.pdhg_primal(x, xbar, g, [], K.MARCH_TAU, nonneg)
-        _same_bits(host(x), want[0], (shape, "no TV", nonneg, "x"))
-        _same_bits(host(xbar), want[1], (shape, "no TV", nonneg, "x-bar"))
+        same_bits(host(x), want[0], (shape, "no TV", nonneg, "x"))
+        same_bits(host(xbar), want[1], (shape, "no TV", nonneg, "x-bar"))
         assert xg.intact() and bg.intact() and gg.intact() and gg.unchanged()
 
 
@@ -169,49 +157,13 @@ def test_work_arrays_come_from_one_placed_block_of_the_stated_size():
 
 
 # ------------------------------------------------------------------------------------------------ the driver
-LABELS = ["detY", "angles", "detX"]
+Geometry, LABELS = GEO.Geometry, GEO.LABELS     # under these names tests/test_gpu_streams.py builds its `golden` case
 ITERS = 12
-
-
-class Geometry:
-    def __init__(self, nz, n, angles, sino, L_A, pad=0):
-        self.nz, self.n, self.angles, self.sino, self.L_A, self.pad = nz, n, angles, sino, float(L_A), pad
-        self.size = n + 2 * pad        # the reconstruction grid grows with the padded detector
-
-    def tools(self, **kw):
-        from tomobar_amd.methodsIR_CuPy import RecToolsIRCuPy
-        return RecToolsIRCuPy(self.n, self.pad, self.nz if self.nz > 1 else None, 0.0, self.angles, self.n, 0,
-                              kw.pop("OS_number", None), adjoint=kw.pop("adjoint", "matched"))
-
-    def projector(self):
-        return M.MatchedProjector(self.nz, self.size, self.size, self.angles, 0.0)
-
-    def data(self, **kw):
-        return dict({"projection_data": torch.from_numpy(self.sino.copy()).cuda(), "data_axes_labels_order": list(LABELS)}, **kw)
 
 
 @pytest.fixture(scope="module")
 def geometries(oracle, golden_dir):
-    gold = np.load(os.path.join(golden_dir, "outer_golden.npz"))
-    a48 = np.linspace(0.0, np.pi, 23, endpoint=False)
-    vol = np.zeros((5, 48, 48), np.float32)
-    vol[:, 12:30, 16:36] = 1.0
-    vol[2:, 20:26, 18:30] = 2.5
-    rng = np.random.default_rng(43)
-    s48 = oracle.Projector(5, 48, 48, a48).fp(vol)
-    s48 = (s48 + 0.5 * rng.standard_normal(s48.shape)).astype(np.float32)
-    gsino = np.ascontiguousarray(gold["sino"], np.float32)
-    out = {"golden": Geometry(4, 24, gold["angles"], gsino, gold["L_full"]),
-           "golden_pad": Geometry(4, 24, gold["angles"], gsino, gold["L_full"], pad=4),
-           "golden_2d": Geometry(1, 24, gold["angles"], np.ascontiguousarray(gsino[1:2]), gold["L_full"]),
-           "n48": Geometry(5, 48, a48, s48, 1500.0)}
-    for g in out.values():
-        g.sino.setflags(write=False)
-    return out
-
-
-def _x0(shape):
-    return (0.05 * np.random.default_rng(47).random(shape)).astype(np.float32)
+    return GEO.build(oracle, golden_dir)
 
 
 # name -> (geometry, _data_ keys, _algorithm_ keys, _regularisation_)
@@ -231,7 +183,7 @@ DRIVER_CASES = {
 
 def _oracle_run(oracle, geo, d, a, r, iterations=ITERS, many=None):
     b = oracle.pad_detector(geo.sino, geo.pad)
-    x0 = _x0((geo.nz, geo.size, geo.size)) if a.get("initialise") == "x0" else None
+    x0 = GEO.x0((geo.nz, geo.size, geo.size)) if a.get("initialise") == "x0" else None
     kw = dict(fidelity=d.get("data_fidelity", "LS"), lam=None if r is None else r["regul_param"],
               methodTV=0 if r is None else r.get("methodTV", 0), nonneg=a.get("nonnegativity", False),
               ratio=a.get("PDHG_ratio", 1.0), x0=x0)
@@ -247,7 +199,7 @@ def _oracle_run(oracle, geo, d, a, r, iterations=ITERS, many=None):
 def _algorithm(geo, a, **kw):
     algo = dict({"iterations": ITERS, "lipschitz_const": geo.L_A, "recon_mask_radius": None}, **a)
     if algo.get("initialise") == "x0":
-        algo["initialise"] = torch.from_numpy(_x0((geo.nz, geo.size, geo.size))).cuda()
+        algo["initialise"] = torch.from_numpy(GEO.x0((geo.nz, geo.size, geo.size))).cuda()
     return dict(algo, **kw)
 
 
@@ -262,7 +214,7 @@ def test_driver_equals_the_oracle_loop(name, geometries, oracle):
     assert rt.Atools.kernel_path("bp").startswith("matched")
     assert rt.last_run["method"] == "PDHG" and rt.last_run["iterations_done"] == ITERS and not rt.last_run["converged"]
     assert np.abs(want).max() > 0
-    _same_bits(host(got), want, name)
+    same_bits(host(got), want, name)
 
 
 def test_lipschitz_constant_comes_from_the_power_method_on_the_matched_pair(geometries, oracle):
@@ -275,7 +227,7 @@ def test_lipschitz_constant_comes_from_the_power_method_on_the_matched_pair(geom
     got = rt.PDHG(geo.data(), algo, {"method": "PD_TV", "regul_param": 0.002})
     assert algo["lipschitz_const"] == L_A
     want = P.pdhg(geo.projector(), geo.sino, L_A, 3, lam=0.002)
-    _same_bits(host(got), want, "power method")
+    same_bits(host(got), want, "power method")
 
 
 def test_a_run_stopped_by_the_tolerance_is_the_run_of_that_many_iterations(geometries, oracle):
@@ -297,7 +249,7 @@ def test_a_run_stopped_by_the_tolerance_is_the_run_of_that_many_iterations(geome
     assert run["converged"] and run["iterations_done"] == stop and len(run["rel_change"]) == stop
     plain = host(geo.tools().PDHG(geo.data(**d), _algorithm(geo, a, iterations=run["iterations_done"]), dict(r)))
     assert np.array_equal(got, plain)
-    _same_bits(got, its[stop], "stopped run against the oracle")
+    same_bits(got, its[stop], "stopped run against the oracle")
 
 
 def test_refusals_on_a_real_object(geometries):

@@ -14,26 +14,13 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from _gpu_compare import host, same_bits  # noqa: E402
 from _guarded import guarded  # noqa: E402
 import _pdhg_cases as K  # noqa: E402
 import _pdhg_diag_oracle as D  # noqa: E402
 import _pdhg_oracle as P  # noqa: E402
 
 F = np.float32
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype == np.float32 and got.shape == want.shape, what
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        raise AssertionError((what, f"{len(bad)} of {got.size} values differ, first at {tuple(bad[0])}",
-                              float(np.abs(got.astype(np.float64) - want).max())))
 
 
 # ------------------------------------------------------------------------------------------------ the steps and step 2
@@ -70,10 +57,10 @@ def test_step_builder_equals_the_oracle(shape):
             assert (want == numer * F(1024)).any() and want.min() < 1e-2 and want[want < 900].max() > 1e2
         sg, og = guarded(sums), guarded(shape)
         assert ops.pdhg_diag_steps(og.view, sg.view, numer, add) is og.view
-        _same_bits(host(og.view), want, (shape, float(add), "out of place"))
+        same_bits(host(og.view), want, (shape, float(add), "out of place"))
         assert sg.intact() and og.intact() and sg.unchanged()
         assert ops.pdhg_diag_steps(sg.view, sg.view, numer, add) is sg.view      # out == in
-        _same_bits(host(sg.view), want, (shape, float(add), "in place"))
+        same_bits(host(sg.view), want, (shape, float(add), "in place"))
         assert sg.intact()
 
 
@@ -91,11 +78,11 @@ def test_sino_dual_diag_equals_the_oracle(shape, fidelity):
             assert (want == 1).any() and (want == -1).any() and (np.abs(want) < 1).any()
     yg, rg, bg, sg = guarded(y), guarded(r), guarded(b), guarded(sigma)
     assert ops.pdhg_sino_dual_diag(yg.view, rg.view, bg.view, sg.view, fidelity) is yg.view
-    _same_bits(host(yg.view), want, (shape, fidelity))
+    same_bits(host(yg.view), want, (shape, fidelity))
     assert all(g.intact() for g in (yg, rg, bg, sg)) and rg.unchanged() and bg.unchanged() and sg.unchanged()
     # two applications: the dual is really updated in place
     ops.pdhg_sino_dual_diag(yg.view, rg.view, bg.view, sg.view, fidelity)
-    _same_bits(host(yg.view), D.sino_dual(want, r, b, fidelity, sigma), (shape, fidelity, "second application"))
+    same_bits(host(yg.view), D.sino_dual(want, r, b, fidelity, sigma), (shape, fidelity, "second application"))
     assert all(g.intact() for g in (yg, rg, bg, sg)) and sg.unchanged()
 
 
@@ -110,11 +97,11 @@ def test_streams_on_arrays_that_are_not_16_byte_aligned(fidelity, shifts):
     yg, rg, bg, sg = (guarded(a, shift=k) for a, k in zip((y, r, b, sigma), shifts))
     assert [g.view.data_ptr() % 16 for g in (yg, rg, bg, sg)] == [4 * k for k in shifts]
     ops.pdhg_sino_dual_diag(yg.view, rg.view, bg.view, sg.view, fidelity)
-    _same_bits(host(yg.view), D.sino_dual(y, r, b, fidelity, sigma), (fidelity, shifts))
+    same_bits(host(yg.view), D.sino_dual(y, r, b, fidelity, sigma), (fidelity, shifts))
     assert all(g.intact() for g in (yg, rg, bg, sg)) and rg.unchanged() and bg.unchanged() and sg.unchanged()
     ug, og = guarded(sums, shift=shifts[3]), guarded((4100,), shift=shifts[0])
     ops.pdhg_diag_steps(og.view, ug.view, NUMER)
-    _same_bits(host(og.view), sigma, ("steps", shifts))
+    same_bits(host(og.view), sigma, ("steps", shifts))
     assert ug.intact() and og.intact() and ug.unchanged()
 
 
@@ -184,10 +171,10 @@ def test_primal_diag_equals_the_oracle(shape):
                     if n in K.MARCH_COUNTS:
                         what = (shape, kind, methodTV, nonneg, n)
                         wx, wb, wq = want[n]
-                        _same_bits(host(x), wx, what + ("x",))
-                        _same_bits(host(xbar), wb, what + ("x-bar",))
+                        same_bits(host(x), wx, what + ("x",))
+                        same_bits(host(xbar), wb, what + ("x-bar",))
                         for d in range(nd):
-                            _same_bits(host(q[d]), wq[d], what + (f"q{d + 1}",))
+                            same_bits(host(q[d]), wq[d], what + (f"q{d + 1}",))
                 assert all(b.intact() for b in [xg, bg, gg, tg] + qs), (shape, kind, "a guard was written")
                 assert gg.unchanged() and tg.unchanged(), "g or tau was written"
     # without the TV block: div q = 0, and the corner takes the guarded step 0.95 * 1024
@@ -200,8 +187,8 @@ def test_primal_diag_equals_the_oracle(shape):
         x, xbar = xg.view, bg.view
         for _ in range(3):
             ops.pdhg_primal_diag(x, xbar, gg.view, [], tg.view, nonneg)
-        _same_bits(host(x), want[0], (shape, "no TV", nonneg, "x"))
-        _same_bits(host(xbar), want[1], (shape, "no TV", nonneg, "x-bar"))
+        same_bits(host(x), want[0], (shape, "no TV", nonneg, "x"))
+        same_bits(host(xbar), want[1], (shape, "no TV", nonneg, "x-bar"))
         assert xg.intact() and bg.intact() and gg.intact() and tg.intact() and gg.unchanged() and tg.unchanged()
 
 
@@ -288,18 +275,18 @@ def test_driver_equals_the_oracle_loop(name, monkeypatch):
     assert "lipschitz_const" not in algo and rt.Atools.kernel_path("bp").startswith("matched")
     run = rt.last_run
     assert (run["method"], run["iterations_done"], run["converged"], run["preconditioner"]) == ("PDHG", ITERS, False, "diagonal")
-    _same_bits(host(got), want, (name, "x"))
+    same_bits(host(got), want, (name, "x"))
     assert data.intact() and data.unchanged(), "the caller's projection data must not be written"
     # the rest of the state: the steps and y through the launch the driver made, x-bar, q and tau through the placed block
-    _same_bits(host(seen["sigma"]), state["sigma"], (name, "sigma"))
-    _same_bits(host(seen["y"]), state["y"], (name, "y"))
+    same_bits(host(seen["sigma"]), state["sigma"], (name, "sigma"))
+    same_bits(host(seen["y"]), state["y"], (name, "y"))
     tv = kw["lam"] is not None
     xbar, _, q, tau, _ = ops.pdhg_work_arrays((nz, K.N, K.N), "cuda:0", tv, tau=True)
-    _same_bits(host(xbar), state["xbar"], (name, "x-bar"))
-    _same_bits(host(tau), state["tau"], (name, "tau"))
+    same_bits(host(xbar), state["xbar"], (name, "x-bar"))
+    same_bits(host(tau), state["tau"], (name, "tau"))
     assert len(q) == len(state["q"])
     for d, field in enumerate(q):
-        _same_bits(host(field), state["q"][d], (name, f"q{d + 1}"))
+        same_bits(host(field), state["q"][d], (name, f"q{d + 1}"))
 
 
 def test_without_the_key_the_driver_is_the_scalar_one():
@@ -311,7 +298,7 @@ def test_without_the_key_the_driver_is_the_scalar_one():
         rt = _tools(K.NZ)
         algo = dict({"iterations": ITERS, "lipschitz_const": K.lipschitz(), "recon_mask_radius": None}, **extra)
         got = rt.PDHG({"projection_data": torch.from_numpy(np.array(b)).cuda(), "data_axes_labels_order": list(LABELS)}, algo, _reg(kw))
-        _same_bits(host(got), want, ("scalar steps", tuple(extra)))
+        same_bits(host(got), want, ("scalar steps", tuple(extra)))
         assert rt.last_run["preconditioner"] is None and algo["PDHG_preconditioner"] is None
 
 

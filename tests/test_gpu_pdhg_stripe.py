@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import _cupy_standin  # noqa: E402
+from _gpu_compare import host, same_bits  # noqa: E402
 from _guarded import guarded  # noqa: E402
 import _large_index as LI  # noqa: E402
 import _pdhg_driver_geometries as GEO  # noqa: E402
@@ -24,20 +25,6 @@ import _pdhg_stripe_cases as SC  # noqa: E402
 import _pdhg_stripe_oracle as S  # noqa: E402
 
 F32 = np.float32
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype == np.float32 and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        raise AssertionError((what, f"{len(bad)} of {got.size} values differ, first at {tuple(bad[0])}",
-                              float(np.abs(got.astype(np.float64) - want).max())))
 
 
 # ------------------------------------------------------------------------------------------------ the two launches
@@ -63,8 +50,8 @@ def test_fused_dual_equals_the_oracle(na, nu):
                 yg, pg = guarded(y0, shift=shift), guarded(want_part.shape, shift=pshift)
                 ops.pdhg_sino_dual_stripe(yg.view, rg.view, bg.view, sbg.view, pg.view, fid, sg.view if per else SC.KERNEL_SIGMA)
                 what = (nz, na, nu, fid, "per sample" if per else "scalar", shift, pshift)
-                _same_bits(yg.host(), want_y, what + ("y",))
-                _same_bits(pg.host(), want_part, what + ("part",))
+                same_bits(yg.host(), want_y, what + ("y",))
+                same_bits(pg.host(), want_part, what + ("part",))
                 assert yg.intact() and pg.intact(), (what, "a guard was written")
             for g in (rg, bg, sg, sbg):
                 g.check((nz, na, nu, shift), read_only=True)
@@ -92,8 +79,8 @@ def test_stripe_update_equals_the_oracle(na, nu):
                 sg, bg, pg = guarded(s0, shift=shift), guarded(s0.shape, shift=shift), guarded(part, shift=pshift)
                 ops.pdhg_stripe_update(sg.view, bg.view, pg.view, na, tau_s, theta)
                 what = (nz, na, nu, float(theta), shift, pshift)
-                _same_bits(sg.host(), want_s, what + ("s",))
-                _same_bits(bg.host(), want_sbar, what + ("s-bar",))
+                same_bits(sg.host(), want_s, what + ("s",))
+                same_bits(bg.host(), want_sbar, what + ("s-bar",))
                 assert sg.intact() and bg.intact(), (what, "a guard was written")
                 pg.check(what, read_only=True)
 
@@ -248,11 +235,11 @@ def test_driver_equals_the_oracle_loop(name, geometries, oracle):
     run = rt.last_run
     assert (run["method"], run["iterations_done"], run["converged"]) == ("PDHG", ITERS, False)
     assert run["preconditioner"] == a.get("PDHG_preconditioner")
-    _same_bits(host(got), want, name)
+    same_bits(host(got), want, name)
     stripes = run["stripes"]
     assert isinstance(stripes, torch.Tensor) and stripes.dtype == torch.float32 and stripes.is_contiguous()
     assert tuple(stripes.shape) == (geo.nz, geo.n)           # [detY, detX], the padding columns dropped
-    _same_bits(host(stripes), want_s, (name, "stripes"))
+    same_bits(host(stripes), want_s, (name, "stripes"))
 
 
 def test_without_the_key_the_driver_returns_the_bits_it_returned(geometries, oracle):
@@ -263,7 +250,7 @@ def test_without_the_key_the_driver_returns_the_bits_it_returned(geometries, ora
     for more in ({}, {"stripe_lambda": None}):
         rt = geo.tools()
         got = rt.PDHG(geo.data(**more), _algorithm(geo, {"nonnegativity": True}), dict(TV))
-        _same_bits(host(got), want, ("no stripes", more))
+        same_bits(host(got), want, ("no stripes", more))
         assert "stripes" not in rt.last_run
 
 

@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import _cupy_standin  # noqa: E402
+from _gpu_compare import host, same_bits  # noqa: E402
 from _guarded import guarded  # noqa: E402
 import _pdhg_cases as K  # noqa: E402
 import _pdhg_driver_geometries as GEO  # noqa: E402
@@ -23,27 +24,13 @@ import _pdhg_tgv_oracle as G  # noqa: E402
 GROUPS = ("v", "vbar", "p", "q")
 
 
-def host(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype == np.float32 and got.shape == want.shape, what
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        raise AssertionError((what, f"{len(bad)} of {got.size} values differ, first at {tuple(bad[0])}",
-                              float(np.abs(got.astype(np.float64) - want).max())))
-
-
 def _same_fields(x, xbar, fields, want, what):
-    _same_bits(host(x), want["x"], what + ("x",))
-    _same_bits(host(xbar), want["xbar"], what + ("x-bar",))
+    same_bits(host(x), want["x"], what + ("x",))
+    same_bits(host(xbar), want["xbar"], what + ("x-bar",))
     for name in GROUPS:
         assert len(fields[name]) == len(want[name]), what + (name,)
         for k, t in enumerate(fields[name]):
-            _same_bits(host(t), want[name][k], what + (f"{name}{k + 1}",))
+            same_bits(host(t), want[name][k], what + (f"{name}{k + 1}",))
 
 
 # ------------------------------------------------------------------------------------------------ steps 4 and 5
@@ -212,18 +199,18 @@ def test_driver_equals_the_oracle_loop(name, geometries, oracle):
     assert (run["method"], run["iterations_done"], run["converged"], run["regulariser"]) == ("PDHG", ITERS, False, "PD_TGV")
     assert run["preconditioner"] == ("diagonal" if diag else None) and ("lipschitz_const" in algo) == (not diag)
     assert np.abs(want).max() > 0
-    _same_bits(host(got), want, name)
+    same_bits(host(got), want, name)
     # the rest of the state, through the placed block
     arrays = ops.pdhg_tgv_work_arrays((geo.nz, geo.size, geo.size), "cuda:0", tau=diag)
     xbar, _, p, q, v, vbar = arrays[:6]
-    _same_bits(host(xbar), state["xbar"], (name, "x-bar"))
+    same_bits(host(xbar), state["xbar"], (name, "x-bar"))
     for fields, key in ((p, "p"), (q, "q"), (v, "v"), (vbar, "vbar")):
         assert len(fields) == len(state[key])
         for k, t in enumerate(fields):
-            _same_bits(host(t), state[key][k], (name, f"{key}{k + 1}"))
+            same_bits(host(t), state[key][k], (name, f"{key}{k + 1}"))
     assert any(np.abs(c).max() > 0 for c in state["v"]) and any(np.abs(c).max() > 0 for c in state["q"]), "v or Q never moved"
     if diag:
-        _same_bits(host(arrays[6]), state["tau"], (name, "tau"))
+        same_bits(host(arrays[6]), state["tau"], (name, "tau"))
 
 
 def test_lipschitz_constant_comes_from_the_power_method_on_the_matched_pair(geometries, oracle):
@@ -236,7 +223,7 @@ def test_lipschitz_constant_comes_from_the_power_method_on_the_matched_pair(geom
     got = rt.PDHG(geo.data(), algo, {"method": "PD_TGV", "regul_param": 0.002})
     assert algo["lipschitz_const"] == L_A
     want = G.pdhg_tgv(geo.projector(), geo.sino, L_A, 3, lam=0.002)
-    _same_bits(host(got), want, "power method")
+    same_bits(host(got), want, "power method")
 
 
 def test_a_run_stopped_by_the_tolerance_is_the_run_of_that_many_iterations(geometries, oracle):
@@ -258,7 +245,7 @@ def test_a_run_stopped_by_the_tolerance_is_the_run_of_that_many_iterations(geome
     assert run["converged"] and run["iterations_done"] == stop and len(run["rel_change"]) == stop
     plain = host(geo.tools().PDHG(geo.data(**d), _algorithm(geo, a, iterations=run["iterations_done"]), dict(r)))
     assert np.array_equal(got, plain)
-    _same_bits(got, its[stop], "stopped run against the oracle")
+    same_bits(got, its[stop], "stopped run against the oracle")
 
 
 def test_refusals_on_a_real_object(geometries):

@@ -15,24 +15,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import _cupy_standin  # noqa: E402
+from _gpu_compare import host, same_bits  # noqa: E402
 from _guarded import guarded  # noqa: E402
 import _pdhg_cases as K  # noqa: E402
+import _pdhg_driver_geometries as GEO  # noqa: E402
 import _pdhg_oracle as P  # noqa: E402
 import _spdhg_cases as SK  # noqa: E402
 import _spdhg_oracle as S  # noqa: E402
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype == np.float32 and got.shape == want.shape, what
-    if not np.array_equal(got.view(np.uint32), want.view(np.uint32)):
-        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-        raise AssertionError((what, f"{len(bad)} of {got.size} values differ, first at {tuple(bad[0])}",
-                              float(np.abs(got.astype(np.float64) - want).max())))
 
 
 # ------------------------------------------------------------------------------------------------ subset step 2
@@ -62,16 +51,16 @@ def test_sino_dual_equals_the_oracle(shape, fidelity, sigma):
     yd, rd, bd = yg.view, rg.view, bg.view
     out = ops.spdhg_sino_dual(yd, rd, bd, fidelity, sigma)
     assert out[0] is yd and out[1] is rd
-    _same_bits(host(yd), want_y, (shape, fidelity, float(sigma), "y"))
-    _same_bits(host(rd), want_d, (shape, fidelity, float(sigma), "d"))
+    same_bits(host(yd), want_y, (shape, fidelity, float(sigma), "y"))
+    same_bits(host(rd), want_d, (shape, fidelity, float(sigma), "d"))
     assert yg.intact() and rg.intact() and bg.intact() and bg.unchanged()
     # a second application on a fresh projection: the dual is really updated in place
     r2 = (r[::-1] if r.ndim == 1 else r[::-1, ::-1]).copy()
     rd.copy_(torch.from_numpy(r2))
     ops.spdhg_sino_dual(yd, rd, bd, fidelity, sigma)
     want_y2, want_d2 = S.sino_step(want_y, r2, b, fidelity, sigma)
-    _same_bits(host(yd), want_y2, (shape, fidelity, "second application", "y"))
-    _same_bits(host(rd), want_d2, (shape, fidelity, "second application", "d"))
+    same_bits(host(yd), want_y2, (shape, fidelity, "second application", "y"))
+    same_bits(host(rd), want_d2, (shape, fidelity, "second application", "d"))
     assert yg.intact() and rg.intact() and bg.intact() and bg.unchanged()
 
 
@@ -86,8 +75,8 @@ def test_sino_dual_on_arrays_that_are_not_16_byte_aligned(fidelity):
     assert all(t.data_ptr() % 16 == 4 and t.is_contiguous() for t in (yd, rd, bd))
     ops.spdhg_sino_dual(yd, rd, bd, fidelity, sigma)
     want_y, want_d = S.sino_step(y, r, b, fidelity, sigma)
-    _same_bits(host(yd), want_y, (fidelity, "y"))
-    _same_bits(host(rd), want_d, (fidelity, "d"))
+    same_bits(host(yd), want_y, (fidelity, "y"))
+    same_bits(host(rd), want_d, (fidelity, "d"))
     assert yg.intact() and rg.intact() and bg.intact() and bg.unchanged()
 
 
@@ -119,13 +108,13 @@ def test_streaming_primal_equals_the_oracle(shape, nonneg, w, shift):
     xd, zd, dd = xg.view, zg.view, dg.view
     assert all(t.data_ptr() % 16 == 4 * shift for t in (xd, zd, dd))
     ops.spdhg_primal(xd, zd, dd, tau, w, nonneg)
-    _same_bits(host(xd), want_x, (shape, nonneg, float(w), "x"))
-    _same_bits(host(zd), want_z, (shape, nonneg, float(w), "z"))
+    same_bits(host(xd), want_x, (shape, nonneg, float(w), "x"))
+    same_bits(host(zd), want_z, (shape, nonneg, float(w), "z"))
     assert xg.intact() and zg.intact() and dg.intact() and dg.unchanged()
     ops.spdhg_primal(xd, zd, dd, tau, w, nonneg)
     want_x, want_z = S.primal_step(want_x, want_z, delta, tau, w, nonneg)
-    _same_bits(host(xd), want_x, (shape, nonneg, float(w), "second application", "x"))
-    _same_bits(host(zd), want_z, (shape, nonneg, float(w), "second application", "z"))
+    same_bits(host(xd), want_x, (shape, nonneg, float(w), "second application", "x"))
+    same_bits(host(zd), want_z, (shape, nonneg, float(w), "second application", "z"))
 
 
 # ------------------------------------------------------------------------------------------------ the TV update
@@ -150,16 +139,16 @@ def test_tv_pair_equals_the_oracle(shape):
                 for n in range(1, max(K.MARCH_COUNTS) + 1):
                     ops.spdhg_tv_dual(x, q, e, K.MARCH_SIGMA, lam, methodTV)
                     if n == 1:
-                        _same_bits(host(x), x0, (shape, kind, "the dual launch wrote x"))
+                        same_bits(host(x), x0, (shape, kind, "the dual launch wrote x"))
                     ops.spdhg_tv_primal(x, z, e, K.MARCH_TAU, SK.TV_W, nonneg)
                     if n in K.MARCH_COUNTS:
                         what = (shape, kind, methodTV, nonneg, n)
                         wx, wz, wq, we = want[n]
-                        _same_bits(host(x), wx, what + ("x",))
-                        _same_bits(host(z), wz, what + ("z",))
+                        same_bits(host(x), wx, what + ("x",))
+                        same_bits(host(z), wz, what + ("z",))
                         for d in range(nd):
-                            _same_bits(host(q[d]), wq[d], what + (f"q{d + 1}",))
-                            _same_bits(host(e[d]), we[d], what + (f"e{d + 1}",))
+                            same_bits(host(q[d]), wq[d], what + (f"q{d + 1}",))
+                            same_bits(host(e[d]), we[d], what + (f"e{d + 1}",))
                 assert all(b.intact() for b in [xg, zg] + qs + es), (shape, kind, "a guard was written")
 
 
@@ -240,16 +229,12 @@ def test_work_arrays_come_from_one_placed_block_of_the_stated_size():
 
 
 # ------------------------------------------------------------------------------------------------ the driver
-LABELS = ["detY", "angles", "detX"]
+LABELS = GEO.LABELS
 EPOCHS = 6
 TV = {"method": "PD_TV", "regul_param": 0.002}
 
 
-class Geometry:
-    def __init__(self, nz, n, angles, sino, L_A, pad=0):
-        self.nz, self.n, self.angles, self.sino, self.L_A, self.pad = nz, n, angles, sino, float(L_A), pad
-        self.size = n + 2 * pad        # the reconstruction grid grows with the padded detector
-
+class Geometry(GEO.Geometry):
     def tools(self, OS_number, adjoint="matched"):
         from tomobar_amd.methodsIR_CuPy import RecToolsIRCuPy
         return RecToolsIRCuPy(self.n, self.pad, self.nz if self.nz > 1 else None, 0.0, self.angles, self.n, 0,
@@ -258,30 +243,12 @@ class Geometry:
     def projector(self, m):
         return S.matched(self.nz, self.size, self.size, self.angles, m)
 
-    def data(self, **kw):
-        return dict({"projection_data": torch.from_numpy(self.sino.copy()).cuda(), "data_axes_labels_order": list(LABELS)}, **kw)
-
 
 @pytest.fixture(scope="module")
 def geometries(oracle, golden_dir):
     """the geometries of tests/test_gpu_pdhg.py: `golden` (4 x 24^2, its padded and 2D forms) and `n48` (5 x 48^2, 23 angles:
     uneven subsets, the trim rule acts); L_A bounds the whole operator, hence every subset's"""
-    gold = np.load(os.path.join(golden_dir, "outer_golden.npz"))
-    a48 = np.linspace(0.0, np.pi, 23, endpoint=False)
-    vol = np.zeros((5, 48, 48), np.float32)
-    vol[:, 12:30, 16:36] = 1.0
-    vol[2:, 20:26, 18:30] = 2.5
-    rng = np.random.default_rng(43)
-    s48 = oracle.Projector(5, 48, 48, a48).fp(vol)
-    s48 = (s48 + 0.5 * rng.standard_normal(s48.shape)).astype(np.float32)
-    gsino = np.ascontiguousarray(gold["sino"], np.float32)
-    out = {"golden": Geometry(4, 24, gold["angles"], gsino, gold["L_full"]),
-           "golden_pad": Geometry(4, 24, gold["angles"], gsino, gold["L_full"], pad=4),
-           "golden_2d": Geometry(1, 24, gold["angles"], np.ascontiguousarray(gsino[1:2]), gold["L_full"]),
-           "n48": Geometry(5, 48, a48, s48, 1500.0)}
-    for g in out.values():
-        g.sino.setflags(write=False)
-    return out
+    return GEO.build(oracle, golden_dir, Geometry)
 
 
 def _x0(shape):
@@ -345,7 +312,7 @@ def test_driver_equals_the_oracle_loop(name, geometries, oracle):
     assert run["method"] == "SPDHG" and run["iterations_done"] == EPOCHS and not run["converged"]
     assert run["block_updates"] == state["block_updates"] and sum(run["block_updates"]) == EPOCHS * S.n_blocks(os_number or 1, r is not None)
     assert np.abs(want).max() > 0
-    _same_bits(host(got), want, name)
+    same_bits(host(got), want, name)
     assert np.array_equal(host(given), geo.sino), "the caller's projection data must not be written"
     if name == "initialise":   # a condition on the input: the initial clamp acted
         assert (_x0(want.shape) < 0).any()
@@ -383,7 +350,7 @@ def test_lipschitz_constant_is_the_largest_power_method_value_of_the_subsets(geo
     got = rt.SPDHG(geo.data(), algo, dict(TV))
     assert algo["lipschitz_const"] == max(values)
     want = _oracle_run(oracle, geo, 4, {}, {}, TV, iterations=2, L=max(values))
-    _same_bits(host(got), want, "power method")
+    same_bits(host(got), want, "power method")
 
 
 def test_a_run_stopped_by_the_tolerance_is_the_run_of_that_many_epochs(geometries, oracle):
@@ -406,7 +373,7 @@ def test_a_run_stopped_by_the_tolerance_is_the_run_of_that_many_epochs(geometrie
     assert sum(run["block_updates"]) == stop * S.n_blocks(os_number, True)
     plain = host(geo.tools(os_number).SPDHG(geo.data(**d), _algorithm(geo, a, iterations=stop), dict(r)))
     assert np.array_equal(got, plain)
-    _same_bits(got, its[stop], "stopped run against the oracle")
+    same_bits(got, its[stop], "stopped run against the oracle")
 
 
 def test_refusals_on_a_real_object(geometries):

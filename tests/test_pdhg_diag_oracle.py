@@ -8,6 +8,7 @@ import types
 import numpy as np
 import pytest
 
+import _pdhg_call_log as CALLS
 import _pdhg_cases as K
 import _pdhg_diag_oracle as D
 import _pdhg_oracle as P
@@ -200,46 +201,13 @@ def test_spdhg_refuses_the_key(value):
         _dicts(algo={"PDHG_preconditioner": value}, method_run="SPDHG", me=_self(OS_number=4))
 
 
-VOL, SINO = (2, 4, 4), (2, 3, 4)
+VOL, SINO = CALLS.VOL, CALLS.SINO
 
 
 @pytest.fixture
 def driver(monkeypatch):
     """a RecToolsIRCuPy whose projector and launches are recorders on CPU tensors: (the object, the log of calls)"""
-    import torch
-    from tomobar_amd import methodsIR_CuPy as M
-    log = []
-
-    class Tools:
-        device_index, slab, detectors_x_pad, adjoint, _device = 0, None, 0, "matched", "cpu"
-        vol_geom = {"GridSliceCount": VOL[0], "GridRowCount": VOL[1], "GridColCount": VOL[2]}
-        def vol_shape(self): return VOL
-        def sino_shape(self, sub): return SINO
-        def invalidate(self): log.append("A.invalidate")
-        def set_residual_layout(self, layout): log.append(f"A.set_residual_layout {layout}")
-        def set_volume_layout(self, layout): log.append(f"A.set_volume_layout {layout}")
-        def forward(self, vol, sub, out=None): log.append("A.forward")
-        def backward(self, sino, sub, out=None): log.append("A.backward")
-
-    def work_arrays(shape, device, tv=True, tau=False):
-        log.append("pdhg_work_arrays" + (" tau" if tau else ""))
-        new = lambda: torch.zeros(shape)   # noqa: E731
-        q = [new() for _ in range(3 if tv else 0)]
-        return (new(), new(), q, new(), None) if tau else (new(), new(), q, None)
-
-    monkeypatch.setattr(M.ops, "to_device", lambda x, index: x)
-    monkeypatch.setattr(M.ops, "fill", lambda x, value: log.append(f"fill {float(value)}"))
-    monkeypatch.setattr(M.ops, "pdhg_work_arrays", work_arrays)
-    for name in ("pdhg_sino_dual", "pdhg_tv_dual", "pdhg_primal", "pdhg_diag_steps", "pdhg_sino_dual_diag", "pdhg_primal_diag"):
-        monkeypatch.setattr(M.ops, name, lambda *args, _name=name: log.append(_name), raising=False)
-
-    def no_power_method(self, data):
-        raise AssertionError("the power method ran")
-
-    monkeypatch.setattr(M.RecToolsIRCuPy, "powermethod", no_power_method)
-    rt = M.RecToolsIRCuPy.__new__(M.RecToolsIRCuPy)
-    rt.__dict__.update(Atools=Tools(), _slab=None, _OS_number=1, _objsize_user_given=None, last_run=None)
-    return rt, log
+    return CALLS.recording_driver(monkeypatch, more_ops=("pdhg_diag_steps",))
 
 
 def _data():

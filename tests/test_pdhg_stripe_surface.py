@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
+import _pdhg_call_log as CALLS  # noqa: E402
 import _pdhg_stripe_oracle as S  # noqa: E402,F401  (the restatement imports without a GPU)
 from test_stream_coverage import header_prototypes  # noqa: E402  (the header's parser; read, not collected from here)
 
@@ -153,47 +154,17 @@ def test_the_existing_refusals_keep_their_words():
 
 
 # ------------------------------------------------------------------------------------------------ the driver's calls
-VOL, SINO = (2, 4, 4), (2, 3, 4)
+VOL, SINO = CALLS.VOL, CALLS.SINO
 STRIPE_OPS = ("pdhg_sino_dual_stripe", "pdhg_stripe_update")
 
 
 @pytest.fixture
 def driver(monkeypatch):
-    """a RecToolsIRCuPy whose projector and launches are recorders on CPU tensors: (the object, the log of calls)"""
-    import torch
-    from tomobar_amd import methodsIR_CuPy as M
-    log = []
-
-    class Tools:
-        device_index, slab, detectors_x_pad, adjoint, _device = 0, None, 0, "matched", "cpu"
-        vol_geom = {"GridSliceCount": VOL[0], "GridRowCount": VOL[1], "GridColCount": VOL[2]}
-        def vol_shape(self): return VOL
-        def sino_shape(self, sub): return SINO
-        def invalidate(self): log.append("A.invalidate")
-        def set_residual_layout(self, layout): log.append(f"A.set_residual_layout {layout}")
-        def set_volume_layout(self, layout): log.append(f"A.set_volume_layout {layout}")
-        def forward(self, vol, sub, out=None): log.append("A.forward")
-        def backward(self, sino, sub, out=None): log.append("A.backward")
-
-    def work_arrays(shape, device, tv=True, tau=False):
-        log.append("pdhg_work_arrays" + (" tau" if tau else ""))
-        new = lambda: torch.zeros(shape)   # noqa: E731
-        q = [new() for _ in range(3 if tv else 0)]
-        return (new(), new(), q, new(), None) if tau else (new(), new(), q, None)
-
-    monkeypatch.setattr(M.ops, "to_device", lambda x, index: x)
-    monkeypatch.setattr(M.ops, "fill", lambda x, value: log.append(f"fill {float(value)} {tuple(x.shape)}"))
-    monkeypatch.setattr(M.ops, "pdhg_work_arrays", work_arrays)
-    for name in ("pdhg_sino_dual", "pdhg_tv_dual", "pdhg_primal", "pdhg_sino_dual_diag", "pdhg_primal_diag") + STRIPE_OPS:
-        monkeypatch.setattr(M.ops, name, lambda *args, _name=name: log.append(_name))
-    monkeypatch.setattr(M.ops, "pdhg_diag_steps", lambda *args: log.append(f"pdhg_diag_steps {len(args)}"))
-
-    def no_power_method(self, data):
-        raise AssertionError("the power method ran")
-
-    monkeypatch.setattr(M.RecToolsIRCuPy, "powermethod", no_power_method)
-    rt = M.RecToolsIRCuPy.__new__(M.RecToolsIRCuPy)
-    rt.__dict__.update(Atools=Tools(), _slab=None, _OS_number=1, _objsize_user_given=None, last_run=None)
+    """a RecToolsIRCuPy whose projector and launches are recorders on CPU tensors: (the object, the log of calls); fills are
+    logged with their shapes and the step builder with the number of its arguments"""
+    from tomobar_amd import ops
+    rt, log = CALLS.recording_driver(monkeypatch, fill_shape=True, more_ops=STRIPE_OPS)
+    monkeypatch.setattr(ops, "pdhg_diag_steps", lambda *args: log.append(f"pdhg_diag_steps {len(args)}"))
     return rt, log
 
 

@@ -18,6 +18,8 @@ in float32 exactly where the reference's NumPy-2 semantics make it float32 (``me
 
 from __future__ import annotations
 
+import collections
+import contextlib
 from typing import Optional, Union
 
 import numpy as np
@@ -26,6 +28,7 @@ from numpy import float32
 
 from . import ops
 from .convergence import check_tolerance, relative_change
+from .primal_dual_steps import pdhg_steps, spdhg_steps
 from .projector import HipTools3D, geom_size
 from .regularisersCuPy import check_prox_available, last_prox, prox_regul, reserve_prox_scratch
 from .supp.dicts import dicts_check
@@ -71,6 +74,41 @@ class _RunMonitor:
         if self.verbose:
             print(f"{self.run['method']} stopped after iteration {k}: relative change {d:.3e} < tolerance {self.tol:.3e}")
         return True
+
+
+@contextlib.contextmanager
+def _planar_layouts(A):
+    """PDHG's and SPDHG's protected region: no cached projector state, planar residuals and volumes on entry, and the same
+    again on the way out, whatever was raised inside."""
+    planar_volume = getattr(A, "set_volume_layout", None)
+    A.invalidate()
+    A.set_residual_layout("planar")
+    if planar_volume is not None:
+        planar_volume("planar")
+    try:
+        yield
+    finally:
+        A.set_residual_layout("planar")
+        if planar_volume is not None:
+            planar_volume("planar")
+        A.invalidate()
+
+
+# PDHG's work arrays: x-bar, g = A^T y, the TV duals q or the TGV fields (lists, empty where absent) and, with the preconditioner,
+# the steps per voxel (else None)
+_PdhgWork = collections.namedtuple("_PdhgWork", "xbar g q tgv_p tgv_q v vbar tau")
+
+
+def _pdhg_work(shape, device, block, diag: bool) -> _PdhgWork:
+    """One placed block of their own (the projector calls see ordinary tensors); `block` as in ``pdhg_steps``."""
+    if block == "PD_TGV":
+        xbar, g, tgv_p, tgv_q, v, vbar, *rest = ops.pdhg_tgv_work_arrays(shape, device, tau=diag)
+        return _PdhgWork(xbar, g, [], tgv_p, tgv_q, v, vbar, rest[0] if diag else None)
+    if diag:
+        xbar, g, q, tau, _ = ops.pdhg_work_arrays(shape, device, block is not None, tau=True)
+        return _PdhgWork(xbar, g, q, [], [], [], [], tau)
+    xbar, g, q, _ = ops.pdhg_work_arrays(shape, device, block is not None)
+    return _PdhgWork(xbar, g, q, [], [], [], [], None)
 
 
 class RecToolsIRCuPy:
@@ -426,121 +464,83 @@ class RecToolsIRCuPy:
         b = d["projection_data"]
         fid = self.data_fidelity
         nonneg = bool(a["nonnegativity"])
-        has_tgv = r.get("method") == "PD_TGV"   # dicts_check lets nothing but None, "PD_TV" and "PD_TGV" through
-        has_tv = r.get("method") is not None and not has_tgv
-        nd = 3 if A.vol_shape()[0] > 1 else 2
-
+        block = r.get("method")   # dicts_check lets nothing but None, "PD_TV" and "PD_TGV" through
         diag = a["PDHG_preconditioner"] == "diagonal"
-        rho = float32(a["PDHG_ratio"])
-        lam = float32(r["regul_param"]) if has_tv or has_tgv else None
         # the stripe variable s (one offset per detector pixel, added to every angle; mu |s|_1): off unless the key is given
         stripes = d.get("stripe_lambda") is not None
         n_angles = int(b.shape[1])
-        if has_tgv:   # the radii of the two balls: r1 = lambda alpha1, r0 = lambda alpha0
+        lam = float32(r["regul_param"]) if block is not None else None
+        if block == "PD_TGV":   # the radii of the two balls: r1 = lambda alpha1, r0 = lambda alpha0
             r1, r0 = lam * float32(r["TGV_alpha1"]), lam * float32(r["TGV_alpha2"])
-        if diag:
-            # Pock and Chambolle's diagonal steps (alpha = 1), float32 throughout: sigma_i = c rho / (A 1)_i for the
-            # sinogram block, c rho / 2 for the TV block (a forward-difference row has the absolute sum 2),
-            # tau_j = (c / rho) / ((A^T 1)_j + 2 nd); the arrays are built inside the loop's try, two projector calls
-            c = float32(0.95)
-            numer_sigma, numer_tau = c * rho, c / rho
-            sigma = numer_sigma / float32(2)
-            col_add = float32(2 * nd) if has_tv or has_tgv else float32(0)
-            # the TGV block: a P row holds a forward difference and -I (absolute sum 3), a Q row sums to 2; a v_d column
-            # meets -I once, Q_dd's difference and, for each e != d, the two rows Q_de stands for: 1 + 2 + 2 (nd - 1)
-            sigma_p, sigma_q, tau_v = numer_sigma / float32(3), sigma, numer_tau / float32(2 * nd + 1)
-            # with the stripe variable a row of [A S] gains one entry 1 and a column of S sums to the number of angles
-            tau_s = numer_tau / float32(n_angles)
-        else:
-            # the step sizes, float32 throughout: sigma tau L_K = 0.95^2 with L_K = |A|^2 + |grad|^2 <= L_A + 4 nd; the TGV
-            # block [[grad, -I], [0, E]] has the squared norm <= 12 (2D), 16 (3D)
-            L_K = float32(a["lipschitz_const"])
-            if stripes:   # |[A S]|^2 <= |A|^2 + |S|^2 and |S|^2 is the number of angles, exactly
-                L_K = L_K + float32(n_angles)
-            if has_tv:
-                L_K = L_K + float32(4 * nd)
-            if has_tgv:
-                L_K = L_K + float32(16 if nd == 3 else 12)
-            s = float32(0.95) / np.sqrt(L_K)
-            sigma, tau = s * rho, s / rho
-            sigma_p, sigma_q, tau_v = sigma, sigma, tau
-            tau_s = tau
-        if stripes:
-            theta = tau_s * float32(d["stripe_lambda"])
 
-        # x-bar, g = A^T y and the duals (with TGV: v and v-bar too; with the preconditioner: the steps per voxel) live in a
-        # placed block of their own; the projector calls see ordinary tensors
-        tgv_p = tgv_q = v = vbar = ()
-        if has_tgv:
-            xbar, g, tgv_p, tgv_q, v, vbar, *rest = ops.pdhg_tgv_work_arrays(A.vol_shape(), A._device, tau=diag)
-            if diag:
-                tau = rest[0]
-            q = []
-        elif diag:
-            xbar, g, q, tau, _ = ops.pdhg_work_arrays(A.vol_shape(), A._device, has_tv, tau=True)
-        else:
-            xbar, g, q, _ = ops.pdhg_work_arrays(A.vol_shape(), A._device, has_tv)
-        xbar.copy_(x)
-        for field in (*q, *tgv_p, *tgv_q, *v, *vbar):
+        # the steps: float32 host scalars (with the preconditioner the numerators; the arrays are built below)
+        nd = 3 if A.vol_shape()[0] > 1 else 2
+        st = pdhg_steps(a.get("lipschitz_const"), n_angles, nd, block, a["PDHG_ratio"], diag, stripes, d.get("stripe_lambda"))
+
+        # the work arrays and their fills
+        w = _pdhg_work(A.vol_shape(), A._device, block, diag)
+        w.xbar.copy_(x)
+        for field in (*w.q, *w.tgv_p, *w.tgv_q, *w.v, *w.vbar):
             ops.fill(field, 0.0)
         y = torch.empty_like(b)
         ops.fill(y, 0.0)
         proj = torch.empty_like(b)
-        sigma_rows = torch.empty_like(b) if diag else None   # the steps per sample
         if stripes:   # s, s-bar [nz, nu] and the segments' partial sums of y along the angles
             s, sbar = (torch.empty((b.shape[0], b.shape[2]), dtype=torch.float32, device=b.device) for _ in range(2))
             part = torch.empty((ops.pdhg_stripe_segments(n_angles), b.shape[0], b.shape[2]), dtype=torch.float32, device=b.device)
             for field in (s, sbar, part):
                 ops.fill(field, 0.0)
 
-        planar_volume = getattr(A, "set_volume_layout", None)
-        A.invalidate()
-        A.set_residual_layout("planar")
-        if planar_volume is not None:
-            planar_volume("planar")
-        mon = _RunMonitor(self, "PDHG", a, x)
-        self.last_run["preconditioner"] = "diagonal" if diag else None
-        if has_tgv:
-            self.last_run["regulariser"] = "PD_TGV"
-        try:
-            if diag:   # the row and column sums of A; g and proj hold the ones, the loop overwrites both before it reads them
-                ops.fill(g, 1.0)
-                A.forward(g, None, out=sigma_rows)
-                if stripes:
-                    ops.pdhg_diag_steps(sigma_rows, sigma_rows, numer_sigma, float32(1))
-                else:
-                    ops.pdhg_diag_steps(sigma_rows, sigma_rows, numer_sigma)
+        with _planar_layouts(A):
+            mon = _RunMonitor(self, "PDHG", a, x)
+            self.last_run["preconditioner"] = "diagonal" if diag else None
+            if block == "PD_TGV":
+                self.last_run["regulariser"] = "PD_TGV"
+            sigma_y, tau_x = st.sigma, st.tau   # the steps of y and x: one each, or with the preconditioner one per element
+            if diag:   # from the row and column sums of A; g and proj hold the ones, the loop overwrites both before it reads them
+                sigma_y, tau_x = torch.empty_like(b), w.tau
+                row_add = (float32(1),) if stripes else ()   # with the stripe variable a row of [A S] gains one entry 1
+                ops.fill(w.g, 1.0)
+                A.forward(w.g, None, out=sigma_y)
+                ops.pdhg_diag_steps(sigma_y, sigma_y, st.numer_sigma, *row_add)
                 ops.fill(proj, 1.0)
-                A.backward(proj, None, out=tau)
-                ops.pdhg_diag_steps(tau, tau, numer_tau, col_add)
+                A.backward(proj, None, out=tau_x)
+                ops.pdhg_diag_steps(tau_x, tau_x, st.numer_tau, st.col_add)
+
+            # which launches an iteration makes is settled here, once (each still looked up on `ops` when it is made)
+            if stripes:   # step 2 on A x-bar + S s-bar, the sums of y along the angles in the same pass; then step 6
+                def sino_dual():
+                    ops.pdhg_sino_dual_stripe(y, proj, b, sbar, part, fid, sigma_y)
+                    ops.pdhg_stripe_update(s, sbar, part, n_angles, st.tau_s, st.theta)
+            elif diag:
+                def sino_dual():
+                    ops.pdhg_sino_dual_diag(y, proj, b, sigma_y, fid)
+            else:
+                def sino_dual():
+                    ops.pdhg_sino_dual(y, proj, b, fid, sigma_y)
+            if block == "PD_TGV":
+                def primal():
+                    ops.pdhg_tgv_dual(w.xbar, w.vbar, w.tgv_p, w.tgv_q, st.sigma_p, st.sigma_q, r1, r0)
+                    ops.pdhg_tgv_primal(x, w.xbar, w.g, w.v, w.vbar, w.tgv_p, w.tgv_q, tau_x, st.tau_v, nonneg)
+            elif diag:
+                def primal():
+                    ops.pdhg_primal_diag(x, w.xbar, w.g, w.q, tau_x, nonneg)
+            else:
+                def primal():
+                    ops.pdhg_primal(x, w.xbar, w.g, w.q, tau_x, nonneg)
+            has_tv = block == "PD_TV"
+
             for k in range(a["iterations"]):
-                A.forward(xbar, None, out=proj)
-                if stripes:   # step 2 on A x-bar + S s-bar, the sums of y along the angles in the same pass; then step 6
-                    ops.pdhg_sino_dual_stripe(y, proj, b, sbar, part, fid, sigma_rows if diag else sigma)
-                    ops.pdhg_stripe_update(s, sbar, part, n_angles, tau_s, theta)
-                elif diag:
-                    ops.pdhg_sino_dual_diag(y, proj, b, sigma_rows, fid)
-                else:
-                    ops.pdhg_sino_dual(y, proj, b, fid, sigma)
-                A.backward(y, None, out=g)
+                A.forward(w.xbar, None, out=proj)
+                sino_dual()
+                A.backward(y, None, out=w.g)
                 if has_tv:
-                    ops.pdhg_tv_dual(xbar, q, sigma, lam, r["methodTV"])
-                if has_tgv:
-                    ops.pdhg_tgv_dual(xbar, vbar, tgv_p, tgv_q, sigma_p, sigma_q, r1, r0)
-                    ops.pdhg_tgv_primal(x, xbar, g, v, vbar, tgv_p, tgv_q, tau, tau_v, nonneg)
-                elif diag:
-                    ops.pdhg_primal_diag(x, xbar, g, q, tau, nonneg)
-                else:
-                    ops.pdhg_primal(x, xbar, g, q, tau, nonneg)
+                    ops.pdhg_tv_dual(w.xbar, w.q, st.sigma, lam, r["methodTV"])
+                primal()
                 if a["verbose"] and np.mod(k, (round)(a["iterations"] / 5) + 1) == 0:
-                    print("PDHG iteration (", k + 1, ") using", r.get("method"), "regularisation")
+                    print("PDHG iteration (", k + 1, ") using", block, "regularisation")
                 if mon.stop(k + 1, x):
                     break
-        finally:
-            A.set_residual_layout("planar")
-            if planar_volume is not None:
-                planar_volume("planar")
-            A.invalidate()
         if stripes:   # without the detector-padding columns, in the caller's array library
             pad = A.detectors_x_pad
             self.last_run["stripes"] = ops.like(ops.contiguous(s[:, pad:s.shape[1] - pad]), getattr(self, "_given", None))
@@ -560,21 +560,12 @@ class RecToolsIRCuPy:
         A = self.Atools
         fid = self.data_fidelity
         nonneg = bool(a["nonnegativity"])
-        has_tgv = r.get("method") == "PD_TGV"   # dicts_check lets nothing but None, "PD_TV" and "PD_TGV" through
-        has_tv = r.get("method") is not None and not has_tgv
-        nd = 3 if A.vol_shape()[0] > 1 else 2
+        has_tv = r.get("method") is not None     # dicts_check lets nothing but None and "PD_TV" through for SPDHG
         m = self.OS_number
         blocks = 2 * m if has_tv else m          # E: the block updates of one epoch
         draws = np.random.default_rng(a["SPDHG_seed"]).integers(0, blocks, size=a["iterations"] * blocks)
-
-        # the step sizes, float32 throughout: sigma_j tau |K_j|^2 <= 0.95^2 p_j with p = 1 / E per subset, 1 / 2 for TV
-        c, gamma = float32(0.95), float32(a["PDHG_ratio"])
-        n_A, n_G = np.sqrt(float32(a["lipschitz_const"])), np.sqrt(float32(4 * nd))
-        sigma_A, sigma_G = (c * gamma) / n_A, (c * gamma) / n_G
-        w_A, w_G = float32(blocks), float32(2)
-        tau = (c / gamma) / (w_A * n_A)
-        if has_tv:
-            tau = min(tau, (c / gamma) / (w_G * n_G))
+        nd = 3 if A.vol_shape()[0] > 1 else 2
+        sigma_A, sigma_G, tau, w_A, w_G = spdhg_steps(a["lipschitz_const"], nd, m, has_tv, a["PDHG_ratio"])
         lam = float32(r["regul_param"]) if has_tv else None
 
         # z = sum K_j^T y_j, delta and the TV fields live in a placed block of their own; b and y are held subset-major,
@@ -604,15 +595,10 @@ class RecToolsIRCuPy:
         if nonneg:
             ops.clamp_min(x, 0.0)     # SPDHG's first primal step with z-bar = 0
 
-        planar_volume = getattr(A, "set_volume_layout", None)
-        A.invalidate()
-        A.set_residual_layout("planar")
-        if planar_volume is not None:
-            planar_volume("planar")
-        mon = _RunMonitor(self, "SPDHG", a, x)
-        done = [0, 0]
-        mon.run["block_updates"] = (0, 0)
-        try:
+        with _planar_layouts(A):
+            mon = _RunMonitor(self, "SPDHG", a, x)
+            done = [0, 0]
+            mon.run["block_updates"] = (0, 0)
             for epoch in range(a["iterations"]):
                 for j in draws[epoch * blocks:(epoch + 1) * blocks]:
                     if j < m:
@@ -629,11 +615,6 @@ class RecToolsIRCuPy:
                     print("SPDHG epoch (", epoch + 1, ") using", r.get("method"), "regularisation")
                 if mon.stop(epoch + 1, x):
                     break
-        finally:
-            A.set_residual_layout("planar")
-            if planar_volume is not None:
-                planar_volume("planar")
-            A.invalidate()
         return self._finalise(x, a)
 
     # ------------------------------------------------------------------ simple iterative methods
